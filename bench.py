@@ -7,7 +7,7 @@ inference forward (the mode the reference's own benchmark.py times), synthetic "
 (10 m x 10 m column), random-init weights (xavier, non-trivial BN stats).
 One step = one forward pass of the stack over one batch already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 N > 1 = one process per GPU over RCCL.  Started under torch.distributed.run (RANK / WORLD_SIZE in the
 environment, the driver's way) the process is one rank; started bare with --gpus N > 1 it launches
@@ -19,13 +19,20 @@ itself and exits with that job's status.  Either way the line is only printed by
 `--dry-run` (tests/test_dist_cpu.py) runs launcher, rendezvous (gloo), barriers, max-over-ranks and the JSON line
 WITHOUT the GPU workload: the N > 1 plumbing checked on a CPU-only box.
 
+A plain run sets up (captures the graphs, then SETUP_STEPS = 40 untimed pipeline steps: no first launch or cold start in the
+timed steps), warms up (W steps), times ONE region of exactly K steps and prints the line: the contract keys, `config`,
+`regimes.throughput`, `streams_verified_concurrent`, `per_rank_points_per_s`.  `--full` adds everything listed below (and makes
+`value` the median of `--regions` 5 regions after one untimed region).  `--dump-outputs DIR` writes what the last timed step
+returned (the (B, N, 128) features; a seeded sample of their rows above 32 MiB) as DIR/features.npy, float32; the inputs and
+weights are seeded, so two builds given the same arguments can be compared output for output.
+
 Prints ONE JSON line (rank 0).  `value` / `ms_per_step` are the THROUGHPUT regime: `config.batches_in_flight`
 (default 6) independent B=16 batches in flight on `config.streams` (4) streams -- runtime.StaggeredPipeline: a batch is
 two hipGraphs (SA1's sampling | everything else) on its ONE stream, two of the four streams keep one sampled batch
 ahead of their dense work so that a region that starts with empty queues does not run its batches in lockstep
 (`--stagger off`: one graph per batch on `--pipeline` streams, the r01-r04 execution).  A step is still one full batch
 through the whole stack, submitted and completed inside the timed region.  The LATENCY regime (one batch in flight, what the reference's benchmark.py
-times) is reported next to it under `regimes`.  Besides the contract keys the line carries
+times) is reported next to it under `regimes` (--full).  With --full, besides the contract keys the line carries
   regimes       {"throughput": {...}, "latency": {...}}: ms per step and points/s of both regimes, each timed
                 over the same K steps with barrier + synchronize on both sides; "throughput_steady_state": the throughput
                 regime over 10 x K steps (K = 20 is a 9 ms region that starts with empty queues) -- never `value`
@@ -121,15 +128,41 @@ def cpu_baseline(pn2, store, pc, hp):
                       % (passes, pc.shape[0], pc.shape[1])}
 
 
+DUMP_BYTES = 32 << 20  # --dump-outputs: the most one run writes
+SETUP_STEPS = 40       # untimed pipeline steps of the set-up, before the --warmup steps
+
+
+def dump_outputs(path, arrays):
+    """{name: tensor} -> path/<name>.npy in float32.  Each array is viewed as rows of its last dimension; beyond its share of
+    DUMP_BYTES it is cut to a sample of rows drawn with a fixed seed (sorted: the same rows for the same shape, run to run)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            keep = max(1, share // rows[0].nbytes)
+            a = rows[np.sort(np.random.RandomState(0).choice(rows.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / timing plumbing only, gloo on CPU, no GPU work (tests/test_dist_cpu.py)")
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--regions", type=int, default=5,
-                    help="timed regions of exactly --steps steps each; `value` / `ms_per_step` are the median region's")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of exactly --steps steps each; `value` / `ms_per_step` are the median region's "
+                         "(default: 1; 5 with --full)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: one untimed region before the timed ones, the latency and steady-state "
+                         "regimes, per-kernel accounting and roofline, other inputs, north star, other configs, CPU baseline "
+                         "(each can be skipped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; an output larger "
+                         "than %d MiB is cut to a fixed, seeded sample of its rows)" % (DUMP_BYTES >> 20))
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--points", type=int, default=8192)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -164,6 +197,8 @@ def main():
                          "batches ahead of its dense work (two graphs per batch on ONE stream; breaks the lockstep of a region that "
                          "starts with empty queues); off = one graph per batch on --pipeline streams (the r01-r04 execution)")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
     if args.stagger is None:  # the default throughput execution, unless a script asks for the old one by naming --pipeline
         args.stagger = "off" if args.pipeline is not None else "0,0,1,1"
     if args.pipeline is None:
@@ -260,7 +295,8 @@ def main():
             backlog = [int(v) for v in args.stagger.split(",")]
             pipe = pn2.runtime.StaggeredPipeline(lambda x: pn2.model.sa1_samples(x, hp, bins=not args.no_binned_bq),
                                                  lambda x, s: pn2.model.get_sa_fp_features(x, False, hp, sa1=s)[0], mk, backlog)
-            caps = [pn2.runtime.CapturedForward(fwd, pc)]  # the latency regime: one graph, one batch in flight
+            # the latency regime (--full): one graph, one batch in flight
+            caps = [pn2.runtime.CapturedForward(fwd, pc)] if args.full else []
             step = lambda: (lambda r: None if r is None else r[1])(pipe.step())  # noqa: E731
 
             def eager_on(x):  # the instrumented passes launch what the pipeline's two graphs hold  # noqa: F811
@@ -280,6 +316,13 @@ def main():
                 with torch.cuda.stream(streams[i]):
                     return caps[i].replay()
             thr_inputs, n_streams, n_flight = [c_.static_inputs[0] for c_ in caps], P, P
+    # set-up: every captured graph launched (each slot's sampler and dense half) and the pipeline run for SETUP_STEPS untimed
+    # steps, so that neither a first launch nor a cold start falls into the timed steps (what the untimed region of --full does)
+    if not args.eager:
+        for _ in range(max(SETUP_STEPS, n_flight + n_streams)):
+            step()
+        flush()
+        torch.cuda.synchronize()
     for _ in range(args.warmup):
         step()
     flush()
@@ -306,13 +349,20 @@ def main():
     # a K-step region is ~8 ms and starts with empty queues; ONE draw of it moved by +-3 % with the hardware-queue
     # mapping and the submission phase.  The headline is the MEDIAN of `--regions` such regions (each exactly K steps, each
     # bracketed as the contract says, each the maximum over ranks), after one untimed region; min / max / all of them are printed.
-    timed_region()
+    # A plain run (no --full) times ONE region of exactly K steps right after the warm-up.
+    if args.full:
+        timed_region()
     regions = []
     for _ in range(max(1, args.regions)):
         el, out = timed_region()
         per_rank = pn2.dist.gather_over_ranks(el, device=dev)
         regions.append((max(per_rank), per_rank))  # the slowest rank defines a region's time
+    if out is None:
+        raise SystemExit("bench.py: the timed steps returned no output (--steps %d)" % args.steps)
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received from its last step, before anything below replays a graph into it
+        dump_outputs(args.dump_outputs, {"features": out})
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     elapsed, per_rank_el = regions[order[(len(order) - 1) // 2]]  # the median region (lower median for an even count)
     per_rank_pps = [B * N * args.steps / v for v in per_rank_el]
@@ -324,7 +374,7 @@ def main():
     # ---- latency regime: ONE batch in flight (what the reference's benchmark.py times), same K steps, bracketed the
     #      same way: replay -> synchronize per step
     latency_ms = None
-    if not args.eager:
+    if args.full and not args.eager:
         torch.cuda.synchronize()
         if dist_on:
             dist.barrier()
@@ -340,7 +390,7 @@ def main():
     # ---- the same throughput regime over a 10x longer region (K = 20 steps is a 9 ms region that starts
     #      with empty queues; this figure says how far `value` is from the steady state) -- never `value`
     steady_ms = None
-    if not args.eager and world == 1:
+    if args.full and not args.eager and world == 1:
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         for _ in range(10 * args.steps):
@@ -351,40 +401,31 @@ def main():
 
     # ---- instrumented pass: same steps, every launch bracketed by HIP events on its stream ----
     trace_steps = min(args.steps, 10)
-    pn2._lib.lib.trace = []
-    for _ in range(trace_steps):
-        eager_step()  # eager launches (a graph replay cannot be bracketed per kernel); same kernels, same stream
-    torch.cuda.synchronize()
-    trace, pn2._lib.lib.trace = pn2._lib.lib.trace, None
-    kernels = summarize_trace(trace, trace_steps)
+    kernels = None
+    if args.full:
+        pn2._lib.lib.trace = []
+        for _ in range(trace_steps):
+            eager_step()  # eager launches (a graph replay cannot be bracketed per kernel); same kernels, same stream
+        torch.cuda.synchronize()
+        trace, pn2._lib.lib.trace = pn2._lib.lib.trace, None
+        kernels = summarize_trace(trace, trace_steps)
 
     if rank == 0:
         total_points = world * B * N * args.steps
         ms_per_step = elapsed / args.steps * 1e3
         P_eff = 1 if args.eager else n_flight
-        is_fps = lambda k: k["kernel"] in LATENCY_KERNELS  # noqa: E731
-        dense = [k for k in kernels if not is_fps(k)]
-        fps = [k for k in kernels if is_fps(k)]
-        sum_all = sum(k["ms_per_step"] for k in kernels)
-        sum_dense = sum(k["ms_per_step"] for k in dense)
-        mfma = [k for k in kernels if k["bound"] == "mfma"]
-        flops_step = sum(k["algorithmic_units"] * k["launches_per_step"] for k in mfma)
-        # the timed regime decides which kernel set bounds the step: with >1 batch in flight the FPS chains (16 CUs
-        # each) hide behind the other batches, the step is the serial sum of the chip-filling kernels
-        timed = dense if P_eff > 1 else kernels
-        dom = max(timed, key=lambda k: k["ms_per_step"])
-        agg_tf = flops_step / (ms_per_step * 1e-3) / 1e12
-        ref_flops = reference_flops(pn2, hp, B, N)
-        eff_tf = ref_flops / (ms_per_step * 1e-3) / 1e12
         res = {
             "metric": "points/sec through SA+FP stack (B=16,N=8192)",
             "value": round(total_points / elapsed, 1), "unit": "points/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "value_statistic": "median of %d timed regions of exactly %d steps each (barrier + synchronize on both sides of every "
-                               "region, maximum over ranks per region), after %d warm-up steps and one untimed region"
-                               % (len(regions), args.steps, args.warmup),
-            "timed_regions": len(regions), "ms_per_step_regions": region_ms,
+            "value_statistic": ("median of %d timed regions of exactly %d steps each (barrier + synchronize on both sides of every "
+                                "region, maximum over ranks per region), after %d warm-up steps" % (len(regions), args.steps, args.warmup)
+                                if len(regions) > 1 else
+                                "one timed region of exactly %d steps (barrier + synchronize on both sides, maximum over ranks), after "
+                                "%d warm-up steps" % (args.steps, args.warmup)) + (" and one untimed region" if args.full else "") +
+                               ("" if args.eager else "; set-up ran %d untimed steps" % max(SETUP_STEPS, n_flight + n_streams)),
+            "full": bool(args.full), "timed_regions": len(regions), "ms_per_step_regions": region_ms,
             "value_min": round(total_points / max(r_[0] for r_ in regions), 1),
             "value_max": round(total_points / min(r_[0] for r_ in regions), 1),
             "streams_verified_concurrent": verified_per_rank,
@@ -416,37 +457,52 @@ def main():
                     "steps": 10 * args.steps, "ms_per_step": round(steady_ms, 4),
                     "points_per_s": round(B * N / (steady_ms * 1e-3), 1),
                     "note": "the throughput regime over a 10x longer timed region (not `value`)"}},
-            "roofline": {"regime": "throughput" if P_eff > 1 else "latency",
-                         "kernel": dom["kernel"], "args": dom["args"], "bound": dom["bound"],
-                         "achieved": dom["achieved"], "peak": dom["peak"], "unit": dom["unit"], "frac": dom["frac"],
-                         "traffic": pmc_traffic(dom["kernel"]), "traffic_source": PMC_FILE,
-                         "algorithmic_units": dom["algorithmic_units"], "avg_us": dom["avg_us"],
-                         "ms_per_step": dom["ms_per_step"],
-                         "share_of_timed_kernels": round(dom["ms_per_step"] / max(1e-9, sum(k["ms_per_step"] for k in timed)), 3),
-                         "flops_counted": "EXECUTED MFMA flops of the launch (a *_pre kernel runs its first layer only on the "
-                                          "channels that were not hoisted onto the source rows; the hoisted product is its own "
-                                          "linear launch in 'kernels')",
-                         "aggregate": {"what": "all EXECUTED MFMA flops of one step / ms_per_step of the timed regime",
-                                       "flops_per_step": int(flops_step), "achieved": round(agg_tf, 2),
-                                       "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s", "frac": round(agg_tf / MFMA_F32_PEAK_TF, 4)},
-                         "aggregate_reference_formulation": {
-                             "what": "flops the reference's formulation spends on the same step (SURVEY 8d: every conv on the "
-                                     "grouped tensor) / ms_per_step: the rate a kernel set without hoisting would need",
-                             "flops_per_step": int(ref_flops), "effective": round(eff_tf, 2), "unit": "TFLOP/s",
-                             "frac_of_peak_equivalent": round(eff_tf / MFMA_F32_PEAK_TF, 4)},
-                         "kernel_time_sums_ms": {"all": round(sum_all, 4), "without_fps": round(sum_dense, 4),
-                                                 "fps": round(sum(k["ms_per_step"] for k in fps if k["kernel"] in FPS_KERNELS), 4),
-                                                 "coarse_geometry": round(sum(k["ms_per_step"] for k in fps
-                                                                              if k["kernel"] == "coarse_geometry"), 4),
-                                                 "note": "without_fps = the chip-filling kernels: everything but the samplers "
-                                                         "and pn2_coarse_geometry (latency-bound, a few workgroups per cloud)"}},
             "per_rank_points_per_s": [round(v, 1) for v in per_rank_pps],
-            "kernels": kernels,
             "single_batch_latency_ms": None if latency_ms is None else round(latency_ms, 4),
-            "gpu_ms_per_step_sum_of_kernels": round(sum_all, 4),
         }
+        if kernels is not None:  # --full: the instrumented pass
+            is_fps = lambda k: k["kernel"] in LATENCY_KERNELS  # noqa: E731
+            dense = [k for k in kernels if not is_fps(k)]
+            fps = [k for k in kernels if is_fps(k)]
+            sum_all = sum(k["ms_per_step"] for k in kernels)
+            sum_dense = sum(k["ms_per_step"] for k in dense)
+            mfma = [k for k in kernels if k["bound"] == "mfma"]
+            flops_step = sum(k["algorithmic_units"] * k["launches_per_step"] for k in mfma)
+            # the timed regime decides which kernel set bounds the step: with >1 batch in flight the FPS chains (16 CUs
+            # each) hide behind the other batches, the step is the serial sum of the chip-filling kernels
+            timed = dense if P_eff > 1 else kernels
+            dom = max(timed, key=lambda k: k["ms_per_step"])
+            agg_tf = flops_step / (ms_per_step * 1e-3) / 1e12
+            ref_flops = reference_flops(pn2, hp, B, N)
+            eff_tf = ref_flops / (ms_per_step * 1e-3) / 1e12
+            res["roofline"] = {"regime": "throughput" if P_eff > 1 else "latency",
+                               "kernel": dom["kernel"], "args": dom["args"], "bound": dom["bound"],
+                               "achieved": dom["achieved"], "peak": dom["peak"], "unit": dom["unit"], "frac": dom["frac"],
+                               "traffic": pmc_traffic(dom["kernel"]), "traffic_source": PMC_FILE,
+                               "algorithmic_units": dom["algorithmic_units"], "avg_us": dom["avg_us"],
+                               "ms_per_step": dom["ms_per_step"],
+                               "share_of_timed_kernels": round(dom["ms_per_step"] / max(1e-9, sum(k["ms_per_step"] for k in timed)), 3),
+                               "flops_counted": "EXECUTED MFMA flops of the launch (a *_pre kernel runs its first layer only on the "
+                                                "channels that were not hoisted onto the source rows; the hoisted product is its own "
+                                                "linear launch in 'kernels')",
+                               "aggregate": {"what": "all EXECUTED MFMA flops of one step / ms_per_step of the timed regime",
+                                             "flops_per_step": int(flops_step), "achieved": round(agg_tf, 2),
+                                             "peak": MFMA_F32_PEAK_TF, "unit": "TFLOP/s", "frac": round(agg_tf / MFMA_F32_PEAK_TF, 4)},
+                               "aggregate_reference_formulation": {
+                                   "what": "flops the reference's formulation spends on the same step (SURVEY 8d: every conv on the "
+                                           "grouped tensor) / ms_per_step: the rate a kernel set without hoisting would need",
+                                   "flops_per_step": int(ref_flops), "effective": round(eff_tf, 2), "unit": "TFLOP/s",
+                                   "frac_of_peak_equivalent": round(eff_tf / MFMA_F32_PEAK_TF, 4)},
+                               "kernel_time_sums_ms": {"all": round(sum_all, 4), "without_fps": round(sum_dense, 4),
+                                                       "fps": round(sum(k["ms_per_step"] for k in fps if k["kernel"] in FPS_KERNELS), 4),
+                                                       "coarse_geometry": round(sum(k["ms_per_step"] for k in fps
+                                                                                    if k["kernel"] == "coarse_geometry"), 4),
+                                                       "note": "without_fps = the chip-filling kernels: everything but the samplers "
+                                                               "and pn2_coarse_geometry (latency-bound, a few workgroups per cloud)"}}
+            res["kernels"] = kernels
+            res["gpu_ms_per_step_sum_of_kernels"] = round(sum_all, 4)
         res.update(rccl_info(world))
-        if fps:
+        if kernels is not None and fps:
             f0 = max([k for k in fps if k["kernel"] in FPS_KERNELS], key=lambda k: k["ms_per_step"])
             fb, fn, fm = f0["args"][:3]
             res["latency_limiter"] = {
@@ -460,7 +516,7 @@ def main():
                 "hbm_frac": f0["frac"],
                 "note": "a round is a dependent chain (LDS read -> distance -> max tree -> 6 DPP steps -> LDS atomic -> "
                         "barrier -> read) of ~250-330 ns whatever the block shape (profiles/r02_fps_experiments.txt)"}
-        if world == 1 and not args.eager and not args.no_other_inputs:
+        if args.full and world == 1 and not args.eager and not args.no_other_inputs:
             # the data-dependent kernels (lazy FPS pruning, the grid ball query's >64-hit path, three_nn's
             # overflow rescan) on the reference benchmark's own input and on a duplicate-heavy cloud: SAME graphs (the
             # static input buffers are overwritten), same K, both regimes, per-kernel times from an eager pass
@@ -508,14 +564,14 @@ def main():
             caps[0].static_inputs[0].copy_(pc)  # back to S-scene for whatever follows
             for n_, d_ in enumerate(thr_inputs):
                 d_.copy_(mk(n_))
-        if not args.no_north_star:
+        if args.full and not args.no_north_star:
             try:
                 res["north_star"] = north_star_kernels(pn2, dev)
             except Exception as ex:  # keep the headline line alive
                 res["north_star"] = {"error": repr(ex)}
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             res["other_configs"] = other_configs(pn2, dev, hp, args.steps)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(pn2, store, pc_np, hp)
             except Exception as ex:

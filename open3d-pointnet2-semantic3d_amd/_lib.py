@@ -7,6 +7,7 @@ tensors and streams are then shared with torch without copies.
 """
 import ctypes
 import os
+import sys
 
 import torch  # noqa: F401  (must precede CDLL: maps torch's libamdhip64.so.7)
 
@@ -174,16 +175,22 @@ def _load():
     # Build in-tree with hipcc when the library is missing OR older than its sources (cross-compiles without a GPU);
     # never fall back to CPU code.  One process per GPU may import concurrently (torch.distributed.run): the check
     # and the build run under a file lock, and build.py links to a temporary file that is renamed into place, so no
-    # rank can dlopen a half-written library.
+    # rank can dlopen a half-written library.  An up-to-date library is loaded without touching the tree (it may be
+    # read-only to the user who runs it); the lock is taken only when a build may be needed.
     import fcntl
     from . import build as _build
-    with open(os.path.join(_HERE, ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not os.environ.get("PN2_HIP_LIBRARY") and _build._stale():
-                _build.build()
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
+    if not os.environ.get("PN2_HIP_LIBRARY") and _build._stale():
+        if not os.access(_HERE, os.W_OK) and os.path.exists(_build.LIB):
+            sys.stderr.write("pn2: %s is older than its sources but %s is not writable: loading the library as built\n"
+                             % (_build.LIB, _HERE))
+        else:
+            with open(os.path.join(_HERE, ".build.lock"), "a") as lock:
+                fcntl.flock(lock, fcntl.LOCK_EX)
+                try:
+                    if _build._stale():  # another process may have built it while this one waited
+                        _build.build()
+                finally:
+                    fcntl.flock(lock, fcntl.LOCK_UN)
     try:
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover

@@ -1,9 +1,10 @@
-"""bench.py prints ONE JSON line that carries the driver's contract keys plus `roofline` and `cpu_baseline`."""
+"""bench.py prints ONE JSON line that carries the driver's contract keys; with --full also `roofline`, `cpu_baseline` and the rest."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,7 +15,7 @@ def test_bench_json_contract():
     env = dict(os.environ)
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-                          "--batch", "4", "--points", "2048", "--no-north-star", "--no-other-configs"],
+                          "--batch", "4", "--points", "2048", "--full", "--no-north-star", "--no-other-configs"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -66,7 +67,7 @@ def test_bench_other_configs_carry_both_regimes():
     env = dict(os.environ)
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-                          "--no-north-star", "--no-cpu-baseline", "--no-other-inputs"],
+                          "--full", "--no-north-star", "--no-cpu-baseline", "--no-other-inputs"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=850)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
@@ -80,3 +81,32 @@ def test_bench_other_configs_carry_both_regimes():
         assert 0 < thr["ms_per_step"] <= reg["latency"]["ms_per_step"], (key, reg)   # several batches in flight never cost more per batch
         assert thr["ms_per_step"] == sorted(thr["ms_per_step_regions"])[(len(thr["ms_per_step_regions"]) - 1) // 2]
     assert oc["configs[3]@1gpu"]["ms_per_step"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_exactly_k_steps_and_dumps_outputs(tmp_path):
+    """a plain run (no --full): one timed region of exactly --steps steps, the contract keys, none of the --full extras; and
+    --dump-outputs writes the last step's features, identical for identical arguments (seeded inputs and weights)"""
+    env = dict(os.environ)
+    env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
+    got = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                              "--batch", "4", "--points", "2048", "--dump-outputs", str(d)],
+                             cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        r = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+            assert k in r, k
+        assert r["steps"] == 7 and r["warmup"] == 2 and r["full"] is False and r["timed_regions"] == 1
+        assert abs(r["value"] - 4 * 2048 * 7 / (r["ms_per_step"] * 7 * 1e-3)) < 1e-3 * r["value"]
+        for k in ("roofline", "kernels", "cpu_baseline", "other_inputs", "other_configs", "north_star"):
+            assert k not in r, k
+        assert sorted(os.listdir(d)) == ["features.npy"]
+        got.append(np.load(d / "features.npy"))
+    a, b = got
+    assert a.dtype == np.float32 and a.shape == (4, 2048, 128) and np.isfinite(a).all()
+    assert np.allclose(a, b, rtol=1e-5, atol=1e-5), float(np.abs(a - b).max())

@@ -300,3 +300,21 @@ def test_bench_never_reports_fewer_ranks_than_requested():
                    env_extra=dict(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port())))
     assert r.returncode != 0 and "{" not in r.stdout
     assert "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_keeps_a_fixed_bounded_sample(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files; an output above the budget is cut to the same seeded rows every time"""
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    small = torch.arange(24, dtype=torch.float64).reshape(2, 3, 4)
+    big = torch.randn(bench.DUMP_BYTES // (4 * 64) + 1000, 64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s_, b_ = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s_.dtype == np.float32 and np.array_equal(s_, small.numpy().astype(np.float32))
+    assert b_.dtype == np.float32 and b_.shape[1] == 64 and b_.nbytes <= bench.DUMP_BYTES // 2
+    assert np.array_equal(b_, np.load(tmp_path / "b" / "big.npy"))
+    assert all(np.all(big.numpy() == r, axis=1).any() for r in b_[:3])  # whole rows of the output

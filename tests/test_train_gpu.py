@@ -609,7 +609,9 @@ def _two_rank_once(pn2, cuda):
     ndiff = int((cap[0]["p"] != cap[1]["p"]).sum())
     assert ndiff == 0, "captured replicas differ in %d parameters (max %g): a collective / replay ordering error" % (
         ndiff, float(np.abs(cap[0]["p"] - cap[1]["p"]).max()))
-    assert np.array_equal(eag[0]["p"], eag[1]["p"]), "eager replicas differ"
+    ndiff = int((eag[0]["p"] != eag[1]["p"]).sum())
+    assert ndiff == 0, "eager replicas differ in %d parameters (first at %s, max %g)" % (
+        ndiff, np.flatnonzero(eag[0]["p"] != eag[1]["p"])[:8].tolist(), float(np.abs(eag[0]["p"] - eag[1]["p"]).max()))
     np.testing.assert_allclose(cap[0]["losses"][:2], eag[0]["losses"][:2], rtol=1e-4,
                                err_msg="the eager warm-up steps of both jobs are the same code")
     np.testing.assert_allclose(cap[0]["losses"], eag[0]["losses"], rtol=3e-2, err_msg="captured vs eager loss trajectory")

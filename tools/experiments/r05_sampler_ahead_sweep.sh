@@ -4,7 +4,7 @@
 # usage: gpurun --timeout 1500 -- 'bash tools/sampler_ahead_sweep.sh > gpurun_out/sa_sweep.txt 2>&1'
 run() {  # $1 = env assignments, rest = bench flags
   local envs="$1"; shift
-  env $envs python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-north-star --no-other-configs --no-other-inputs "$@" 2>/tmp/err.txt \
+  env $envs python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-north-star --no-other-configs --no-other-inputs "$@" 2>/tmp/err.txt \
    | python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%-70s %.4f  %.4f  %s' % ('$envs $*', r['ms_per_step'], r['single_batch_latency_ms'], (r['regimes'].get('throughput_steady_state') or {}).get('ms_per_step')))" \
    || { echo "FAILED: $envs $*"; tail -5 /tmp/err.txt; }
 }

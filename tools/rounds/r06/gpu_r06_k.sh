@@ -1,6 +1,6 @@
 #!/bin/bash
 OUT=gpurun_out/r06k; mkdir -p $OUT
-timeout 1200 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 1200 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06k/bench.json').read().strip().split('\n')[-1])
