@@ -473,6 +473,19 @@ int pn2_weighted_ce_backward(int rows, int num_class, const float *logits, const
                              const float *weights, const float *lse, const double *acc, const float *gout,
                              float *dlogits, void *stream);
 
+/* The per-batch metrics of the reference's train_one_epoch / eval_one_epoch (train.py:199-331, util/metric.py) on the
+ * device.  logits (rows,num_class) f32 contiguous, labels (rows) int32 (label64 = 0) or int64 (label64 = 1).  Per row the
+ * argmax with np.argmax semantics (first maximal index wins ties, a NaN counts as the maximum and the first NaN wins, +-inf
+ * compare normally); every output is optional:
+ *   pred (rows) int32         <- the argmax;
+ *   confusion (num_class^2)   += 1 at [label * num_class + pred] (accumulates across calls, never zeroed here); a label
+ *                                outside [0, num_class) is left out and counted in *invalid;
+ *   loss_acc (2 doubles)      += {*loss, 1} (loss: device f32 scalar; both or neither).
+ * PN2_EINVAL: rows <= 0, num_class <= 0, no output requested, or only one of loss / loss_acc; PN2_EUNSUP: num_class > 64;
+ * PN2_ENULL: logits or labels NULL.  No host synchronisation, no allocation: capturable into a graph. */
+int pn2_confusion_update(int rows, int num_class, const float *logits, const void *labels, int label64, int *pred,
+                         long long *confusion, long long *invalid, const float *loss, double *loss_acc, void *stream);
+
 /* tf_util.dropout  util/tf_util.py:646-665 (tf.nn.dropout): y = x / keep_prob where kept, else 0; mask (n bytes) for the
  * backward.  state: device int64[2] = {seed, step}; the draw is a pure function of (seed, step, element index), so a
  * captured graph can be replayed while the caller advances `step` in device memory. */

@@ -135,6 +135,8 @@ SIGNATURES = {
     "pn2_weighted_ce_forward": [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "pn2_weighted_ce_backward": [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p],
+    "pn2_confusion_update": [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p],
     "pn2_dropout": [ctypes.c_longlong, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "pn2_dropout_grad": [ctypes.c_longlong, c_void_p, c_void_p, c_float, c_void_p, c_void_p],
     "pn2_relu_grad": [ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p],

@@ -11,7 +11,7 @@ import torch
 from . import dist as pdist
 from . import model
 from ._lib import check, lib, ptr, stream_ptr
-from .util import tf_util
+from .util import metric, tf_util
 
 
 def learning_rate(step, batch_size, base_lr=1e-3, decay_step=200000, decay_rate=0.7, floor=1e-5):
@@ -39,12 +39,18 @@ class Trainer:
     `warmup_eager` ordinary steps the step is captured and replayed: on one GPU as ONE hipGraph; with several ranks as three
     (forward + head/FP backward | SA backward | Adam) with the two buckets' all-reduces between them, the first one
     asynchronous so that it travels while the second graph replays -- no collective inside a captured region.  Eager steps
-    (the warm-up, capture=False) launch the first bucket's all-reduce from inside backward (dist.OverlappedGradAllReduce)."""
+    (the warm-up, capture=False) launch the first bucket's all-reduce from inside backward (dist.OverlappedGradAllReduce).
+
+    Metrics (the reference's train_one_epoch / eval_one_epoch, train.py:199-331): with track_metrics=True every training step
+    also counts the argmax of its logits against the labels into `train_confusion` (util.metric.ConfusionMatrix on the device)
+    and adds its loss to a device [sum, count] -- one pn2_confusion_update launch right after the loss, inside whichever graphs
+    the step is captured into; `train_metrics()` reads them (the one synchronisation), `reset_metrics()` starts an epoch.
+    `eval_step` is the validation forward (inference mode) + loss + the same counting into `eval_confusion`."""
 
     BETA1, BETA2, EPS = 0.9, 0.999, 1e-8  # tf.train.AdamOptimizer defaults (train.py:381-384)
 
     def __init__(self, hyperparams, num_class, store=None, device="cuda", capture=True, warmup_eager=3,
-                 split_capture=None, overlap_collective=True):
+                 split_capture=None, overlap_collective=True, track_metrics=False):
         self.hp = dict(hyperparams)
         # schedule / optimizer keys of the reference's semantic.json (train.py:80-119, 380-386); its defaults when absent
         opt = str(self.hp.get("optimizer", "adam")).lower()
@@ -81,6 +87,11 @@ class Trainer:
         # trainer's stream: early bucket launched | SA backward graph done | both buckets reduced
         self.comm_events = None
         self._world0 = None
+        # metrics: off by default (the step and its graphs are then exactly what they are without this code)
+        self.track_metrics = bool(track_metrics)
+        self.train_confusion, self._train_loss_acc, self.last_logits = None, None, None
+        self.eval_confusion, self._eval_loss_acc, self.last_eval_logits = None, None, None
+        self._eval_graph, self._eval_static, self._eval_key, self._eval_warm_key = None, None, None, None
 
     # ---- set-up ------------------------------------------------------------------------------------------------
     def _lazy_init(self, pc):
@@ -130,6 +141,10 @@ class Trainer:
         self._world0 = self.bucket.world()  # frozen into grad_scale above: a process group created later would mis-scale
         self._stream = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
         self._geo_stream = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
+        if self.track_metrics:
+            # fixed device buffers: a captured step adds into these addresses on every replay (reset zeroes them in place)
+            self.train_confusion = metric.ConfusionMatrix(self.num_class, device=dev)
+            self._train_loss_acc = torch.zeros(2, dtype=torch.float64, device=dev)
 
     def _learning_rate(self, step, batch_size):
         c = self.sched
@@ -153,6 +168,8 @@ class Trainer:
         try:
             logits, _ = model.get_model(pc, True, self.num_class, self.hp, bn_decay=decay, geometry=geometry)
             loss = model.get_loss(logits, labels, smpw)
+            if self.track_metrics:
+                self._count_train(logits, labels, loss)
             self.bucket.begin()
             loss.backward()
         finally:
@@ -174,6 +191,8 @@ class Trainer:
         try:
             logits, ep = model.get_model(pc, True, self.num_class, self.hp, bn_decay=decay, geometry=geometry, cut_sa_fp=True)
             loss = model.get_loss(logits, labels, smpw)
+            if self.track_metrics:
+                self._count_train(logits, labels, loss)
             early = list(self.bucket.params[self.bucket.split:])
             cut = list(ep["sa_features_cut"])
             grads = torch.autograd.grad(loss, early + cut, allow_unused=True)
@@ -184,6 +203,13 @@ class Trainer:
         self.bucket.pack_early()
         self._cut = [(t, g) for t, g in zip(ep["sa_features"][1:], grads[len(early):]) if g is not None]
         return loss.detach()
+
+    def _count_train(self, logits, labels, loss):
+        """the step's metrics: argmax of the training-mode logits vs the labels into train_confusion, loss into [sum, count].
+        last_logits keeps the logits alive (and, while capturing, keeps the graph pool from reusing their memory)."""
+        self.last_logits = logits.detach()
+        metric.confusion_update(self.last_logits, labels, confusion=self.train_confusion.matrix_tensor,
+                                invalid=self.train_confusion.invalid_tensor, loss=loss.detach(), loss_acc=self._train_loss_acc)
 
     def _backward_late(self):
         """second piece: the SA modules' backward pass from the gradients at the cut; the late bucket is packed"""
@@ -424,3 +450,120 @@ class Trainer:
                 tf_util.multi_copy_(dsts, srcs)
             self._copy_graph, self._staging = gc, stg
         # the capture itself executed nothing: the replay that follows is this step
+
+    # ---- metrics and validation ----------------------------------------------------------------------------------------------
+    def _on_trainer_stream(self, fn):
+        """run fn() on the trainer's stream, ordered after the caller's work so far and before the caller's later work (the
+        replays of train_step / eval_step run on that stream too)"""
+        caller = torch.cuda.current_stream()
+        st = self._stream if self._stream is not None else caller
+        st.wait_stream(caller)
+        with torch.cuda.stream(st):
+            out = fn()
+        caller.wait_stream(st)
+        return out
+
+    def reset_metrics(self):
+        """start a training epoch: zero train_confusion and the loss sums, behind every step enqueued so far and in front of
+        every later one (a fill on the trainer's stream; no synchronisation)"""
+        if self.train_confusion is None:
+            raise RuntimeError("this trainer was built with track_metrics=False")
+        self._on_trainer_stream(lambda: (self.train_confusion.reset(), self._train_loss_acc.zero_()))
+
+    def reset_eval_metrics(self):
+        """start a validation pass: zero eval_confusion and its loss sums (ordered as reset_metrics)"""
+        if self.eval_confusion is not None:
+            self._on_trainer_stream(lambda: (self.eval_confusion.reset(), self._eval_loss_acc.zero_()))
+
+    def train_metrics(self):
+        """{mean_loss, accuracy, mean_iou, per_class_iou} of the training steps since the last reset_metrics (plus
+        confusion_matrix, num_invalid, steps), summed over the ranks when there are several.  The one synchronisation."""
+        if self.train_confusion is None:
+            raise RuntimeError("this trainer was built with track_metrics=False")
+        return self._read_metrics(self.train_confusion, self._train_loss_acc)
+
+    def eval_metrics(self):
+        """the same for the eval_step calls since the last reset_eval_metrics"""
+        if self.eval_confusion is None:
+            raise RuntimeError("no eval_step has run")
+        return self._read_metrics(self.eval_confusion, self._eval_loss_acc)
+
+    def _read_metrics(self, cm, acc):
+        import numpy as np
+        c = self.num_class
+        caller = torch.cuda.current_stream()
+        if self._stream is not None:
+            caller.wait_stream(self._stream)
+        # counts and loss sums in ONE float64 buffer (counts below 2^53 are exact): one all-reduce, one read-back
+        packed = torch.cat([cm.counts[:c * c + 1].double(), acc])
+        if self.bucket is not None and self.bucket.world() > 1:
+            import torch.distributed as tdist
+            tdist.all_reduce(packed)
+        host = packed.cpu().numpy()
+        out_cm = metric.ConfusionMatrix(c)
+        out_cm.confusion_matrix = np.rint(host[:c * c]).astype(np.int64).reshape(c, c)
+        ious = out_cm.get_per_class_ious()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            accuracy = float(out_cm.get_accuracy())
+        steps = int(round(host[c * c + 2]))
+        return {"mean_loss": float(host[c * c + 1] / steps) if steps else float("nan"), "accuracy": accuracy,
+                "mean_iou": float(np.sum(ious) / len(ious)) if ious else float("nan"), "per_class_iou": ious,
+                "confusion_matrix": out_cm.confusion_matrix, "num_invalid": int(round(host[c * c])), "steps": steps}
+
+    def _eval_body(self, pc, labels, smpw):
+        with torch.no_grad():
+            logits, _ = model.get_model(pc, False, self.num_class, self.hp)
+            loss = model.get_loss(logits, labels, smpw)
+            self.last_eval_logits = logits
+            metric.confusion_update(logits, labels, confusion=self.eval_confusion.matrix_tensor,
+                                    invalid=self.eval_confusion.invalid_tensor, loss=loss, loss_acc=self._eval_loss_acc)
+        return loss
+
+    def eval_step(self, pc, labels, smpw, sync=True):
+        """The body of the reference's eval_one_epoch (train.py:262-331) for one batch: the inference forward (is_training=False:
+        moving averages, no dropout), the weighted cross-entropy, and the argmax / confusion-matrix update into eval_confusion
+        and its loss sums (eval_metrics(), reset_eval_metrics()).  Parameters, moving averages and Adam's moments are not
+        touched.  -> loss (python float; with sync=False the device scalar, overwritten by the next eval_step).
+
+        The first call for a given set of weights and shapes runs eagerly (it also fills the folded-inference-weight cache); the
+        next captures the pass into a graph and later calls replay it.  Any training step changes the weights (VariableStore
+        .train_epoch): the graph, which reads the folded weights of its capture, is then dropped and built again.
+
+        The reference's validation split has all-zero label weights (dataset/semantic_dataset.py), so the loss it logs for
+        validation is 0 under SUM_BY_NONZERO_WEIGHTS (0 / max(1, 0)); pass the weights you want the loss computed with."""
+        tf_util.set_default_store(self.store)
+        if self.bucket is None:
+            self._lazy_init(pc)
+        if self.eval_confusion is None:
+            dev = self.flat_p.device
+            self.eval_confusion = metric.ConfusionMatrix(self.num_class, device=dev)
+            self._eval_loss_acc = torch.zeros(2, dtype=torch.float64, device=dev)
+
+        def run():
+            if not (self.capture and pc.is_cuda):
+                return self._eval_body(pc, labels, smpw)
+            key = (self.store.train_epoch,) + tuple((tuple(t.shape), t.dtype) for t in (pc, labels, smpw))
+            if self._eval_key != key:  # weights (folded inference weights) or shapes changed since the capture
+                self._eval_graph, self._eval_static, self._eval_key = None, None, None
+            if self._eval_graph is None and self._eval_warm_key == key:
+                self._capture_eval(pc, labels, smpw)
+                self._eval_key = key
+            if self._eval_graph is None:
+                self._eval_warm_key = key
+                return self._eval_body(pc, labels, smpw)
+            for d, s_ in zip(self._eval_static[:3], (pc, labels, smpw)):
+                if d.data_ptr() != s_.data_ptr():
+                    d.copy_(s_, non_blocking=True)
+            self._eval_graph.replay()
+            return self._eval_static[3]
+
+        loss = self._on_trainer_stream(run)
+        return float(loss) if sync else loss
+
+    def _capture_eval(self, pc, labels, smpw):
+        torch.cuda.synchronize()
+        st = [t.contiguous().clone() for t in (pc, labels, smpw)]
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            loss = self._eval_body(*st)
+        self._eval_graph, self._eval_static = g, st + [loss]
