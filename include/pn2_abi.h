@@ -542,6 +542,33 @@ int pn2_voxel_downsample(int n, const double *points, const double *colors, cons
                          double *out_points, double *out_colors, int *out_labels, int *out_count, int *status,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* SemanticDataset.sample_batch_in_all_files  dataset/semantic_dataset.py:214-343 + util/provider.py rotate_*point_cloud,
+ * on a device-resident multi-scene store, in four launches (csrc/pn2_dataset.hip).
+ * Store: points (total,3) float64, every scene x-sorted in its segment [scene_offsets[k], scene_offsets[k+1]);
+ * colors (total,3) float32 or NULL (zeros), labels (total) uint8 or NULL (zeros); scene_cdf (num_scenes) float64 =
+ * cumsum(p) / its last entry; scene_z_size (num_scenes) = max z - min z; label_weights (num_label_weights) float32
+ * (weight of a label >= num_label_weights: 0).  max_chunks >= ceil(largest scene / 1024).
+ * Draws: draw_scene == NULL -> device random numbers from seed and *counter (device int64, advanced by one per call by the
+ * last launch, so a captured call replays into fresh batches); else replay: draw_scene / draw_center (b) int32 (centre
+ * relative to its scene), draw_mask (b,mask_cap) bytes = the reference's shuffled boolean mask for columns larger than
+ * npts, draw_rot (b,3) float64 = angle, cos, sin (required with augment).
+ * Workspace: 256-byte aligned, pn2_dataset_workspace_size(b, max_chunks) bytes, zero before the first call (calls keep it
+ * zero; one call at a time per workspace).
+ * Outputs: out_info (b,8) int32 = scene, centre, column count, slab lo, slab hi, key bin, candidates needed, status
+ * (0 ok, 1 empty column or bad draw, 2 column wider than mask_cap, 3 mask does not select npts, 4 candidate list full,
+ * 5 slab longer than max_chunks: such a sample is zero-filled); out_finfo (b,3) float64 = angle, cos, sin;
+ * out_sel (b,npts) int32 store indices of the chosen points in scene order, repeated i mod count when count <= npts (-1
+ * for a rejected sample);
+ * out_data (b,npts,6|3) float32 rows [xyz | rgb]; out_labels (b,npts) int32; out_weights (b,npts) float32. */
+int pn2_dataset_workspace_size(int b, int max_chunks, unsigned long long *bytes);
+int pn2_dataset_sample(int b, int npts, int num_scenes, int max_chunks, int use_color, int augment, const double *points,
+                       const float *colors, const unsigned char *labels, const int *scene_offsets, const double *scene_cdf,
+                       const double *scene_z_size, const float *label_weights, int num_label_weights, double half_x,
+                       double half_y, unsigned long long seed, long long *counter, const int *draw_scene,
+                       const int *draw_center, const unsigned char *draw_mask, int mask_cap, const double *draw_rot,
+                       void *workspace, size_t workspace_bytes, int *out_info, double *out_finfo, int *out_sel,
+                       float *out_data, int *out_labels, float *out_weights, void *stream);
+
 /* pn2_fp_mlp_fused with the first layer's product with the INTERPOLATED channels hoisted out by linearity:
  * three_interpolate(points2) @ W1a == three_interpolate(points2 @ W1a) (pointnet_util.py:300-311 followed by the first conv
  * of :312-325), and z = points2 @ W1a has the m known rows per cloud instead of the n unknown ones.  z (b*m, widths[0])

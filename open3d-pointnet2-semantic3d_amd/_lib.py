@@ -165,6 +165,11 @@ SIGNATURES = {
     "pn2_group_pool_grad": [ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "pn2_voxel_downsample": [c_int, c_void_p, c_void_p, c_void_p, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, ctypes.c_size_t, c_void_p],
+    "pn2_dataset_workspace_size": [c_int, c_int, c_void_p],
+    "pn2_dataset_sample": [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p],
 }
 PN2_EUNSUP = -4
 
