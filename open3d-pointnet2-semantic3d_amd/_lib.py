@@ -172,6 +172,25 @@ SIGNATURES = {
                            c_void_p, c_void_p, c_void_p],
 }
 PN2_EUNSUP = -4
+# workspace-size queries (-> size_t): name -> number of int arguments
+_SIZE_QUERIES = {"pn2_fps_large_workspace_bytes": 2, "pn2_ball_query_bin_bytes": 1, "pn2_interpolate_label_workspace_bytes": 1,
+                 "pn2_three_interpolate_grad_workspace_bytes": 3, "pn2_scatter_plan_bytes": 3,
+                 "pn2_group_point_grad_workspace_bytes": 4, "pn2_voxel_downsample_workspace_bytes": 1, "pn2_bn_workspace_bytes": 1}
+# What the benchmark trace decodes besides the numeric arguments: entry point -> (index of nlayers, index of the host widths[]
+# array in the argument list -- both None when there is none --, trace key, positions AMONG THE NUMERIC ARGUMENTS to drop).  An
+# in-place (row-strided) *_ld call is the dense entry point's kernel: recorded under the dense name with its strides dropped.
+_TRACE_ARGS = {"pn2_sa_mlp_max_fused": (9, 10, None, ()), "pn2_sa_mlp_rows_fused": (9, 10, None, ()),
+               "pn2_sa_mlp_max_fused_bf16": (9, 10, None, ()), "pn2_fp_mlp_fused": (9, 10, None, ()),
+               "pn2_fp_mlp_wide_pre": (8, 9, None, ()), "pn2_sa_mlp_wide_pre": (8, 9, None, ()),
+               "pn2_sa_mlp_fused_pre": (8, 9, None, ()), "pn2_fp_mlp_fused_pre": (8, 9, None, ()),
+               "pn2_fp_mlp_fused_pre_schedule": (8, 9, None, ()), "pn2_mlp_chain": (3, 4, None, ()),
+               "pn2_mlp_wide": (4, 5, None, ()), "pn2_fp_mlp_wide": (9, 10, None, ()), "pn2_sa_mlp_wide": (9, 10, None, ()),
+               "pn2_fps_nested_ld": (None, None, "pn2_fps_nested", (3,)),
+               "pn2_query_ball_point_ld": (None, None, "pn2_query_ball_point", (5,)),
+               "pn2_three_nn_ld": (None, None, "pn2_three_nn", (3,)),
+               "pn2_ball_query_bin_ld": (None, None, "pn2_ball_query_bin", (3,)),
+               "pn2_sa_mlp_max_fused_ld": (11, 12, "pn2_sa_mlp_max_fused", (5, 6)),
+               "pn2_fp_mlp_fused_pre_ld": (9, 10, "pn2_fp_mlp_fused_pre", (4,))}
 
 
 class Pn2Error(RuntimeError):
@@ -207,22 +226,10 @@ def _load():
         fn = getattr(lib, name)  # AttributeError if the ABI and the library disagree
         fn.argtypes = argtypes
         fn.restype = c_int
-    lib.pn2_fps_large_workspace_bytes.argtypes = [c_int, c_int]
-    lib.pn2_fps_large_workspace_bytes.restype = ctypes.c_size_t
-    lib.pn2_ball_query_bin_bytes.argtypes = [c_int]
-    lib.pn2_ball_query_bin_bytes.restype = ctypes.c_size_t
-    lib.pn2_interpolate_label_workspace_bytes.argtypes = [c_int]
-    lib.pn2_interpolate_label_workspace_bytes.restype = ctypes.c_size_t
-    lib.pn2_three_interpolate_grad_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    lib.pn2_three_interpolate_grad_workspace_bytes.restype = ctypes.c_size_t
-    lib.pn2_scatter_plan_bytes.argtypes = [c_int, c_int, c_int]
-    lib.pn2_scatter_plan_bytes.restype = ctypes.c_size_t
-    lib.pn2_group_point_grad_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    lib.pn2_group_point_grad_workspace_bytes.restype = ctypes.c_size_t
-    lib.pn2_voxel_downsample_workspace_bytes.argtypes = [c_int]
-    lib.pn2_voxel_downsample_workspace_bytes.restype = ctypes.c_size_t
-    lib.pn2_bn_workspace_bytes.argtypes = [c_int]
-    lib.pn2_bn_workspace_bytes.restype = ctypes.c_size_t
+    for name, nargs in _SIZE_QUERIES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = [c_int] * nargs
+        fn.restype = ctypes.c_size_t
     lib.pn2_abi_version.restype = c_int
     lib.pn2_build_info.restype = ctypes.c_char_p
     lib.pn2_strerror.restype = ctypes.c_char_p
@@ -270,59 +277,23 @@ class _LibProxy:
             rc = fn(*args)
             e.record()
             ints = [a for a in args if isinstance(a, (int, float))]
-            if name in _LD_TRACE:  # an in-place (row-strided) call is the dense entry point's kernel: same trace key, strides dropped
-                base, drop, nl_at, w_at = _LD_TRACE[name]
+            key = name
+            if name in _TRACE_ARGS:
+                nl_at, w_at, dense, drop = _TRACE_ARGS[name]
+                key = dense or name
                 ints = [v for i, v in enumerate(ints) if i not in drop]
-                if w_at is not None:
+                if w_at is not None:  # decode the host-side widths[] array for flop accounting
                     wp = ctypes.cast(args[w_at], ctypes.POINTER(c_int))
                     ints += [wp[i] for i in range(args[nl_at])]
-                self.trace.append((base, tuple(ints), s, e))
-                return rc
-            if name in ("pn2_sa_mlp_max_fused", "pn2_sa_mlp_rows_fused", "pn2_sa_mlp_max_fused_bf16"):  # decode the host-side widths[] array for flop accounting
-                wp = ctypes.cast(args[10], ctypes.POINTER(c_int))
-                ints += [wp[i] for i in range(args[9])]
-            elif name == "pn2_fp_mlp_fused":
-                wp = ctypes.cast(args[10], ctypes.POINTER(c_int))
-                ints += [wp[i] for i in range(args[9])]
-            elif name in ("pn2_fp_mlp_wide_pre", "pn2_sa_mlp_wide_pre"):  # (..4 ints.., 4 pointers, nlayers, widths, ...)
-                wp = ctypes.cast(args[9], ctypes.POINTER(c_int))
-                ints += [wp[i] for i in range(args[8])]
-            elif name == "pn2_sa_mlp_fused_pre":  # (b, n, m, nsample, xyz, new_xyz, zf, idx, nlayers, widths, w, bias, pool, ...)
-                wp = ctypes.cast(args[9], ctypes.POINTER(c_int))
-                ints += [wp[i] for i in range(args[8])]
-            elif name in ("pn2_fp_mlp_fused_pre", "pn2_fp_mlp_fused_pre_schedule"):  # (b, n, m, c1, dist, idx, points1, z, nlayers, widths, ...)
-                wp = ctypes.cast(args[9], ctypes.POINTER(c_int))
-                ints += [wp[i] for i in range(args[8])]
             elif name == "pn2_coarse_geometry":  # (b, n0, nlev, npoint[], radius[], nsample[], ...): decode the host arrays
                 ints += list(args[3]) + list(args[5])
-            elif name == "pn2_mlp_chain":
-                wp = ctypes.cast(args[4], ctypes.POINTER(c_int))
-                ints += [wp[i] for i in range(args[3])]
-            elif name == "pn2_mlp_wide":     # (rows, cin, x_stride, x, nlayers, widths, ...)
-                wp = ctypes.cast(args[5], ctypes.POINTER(c_int))
-                ints += [wp[i] for i in range(args[4])]
-            elif name == "pn2_fp_mlp_wide":  # (b, n, m, c1, c2, dist, idx, points1, points2, nlayers, widths, ...)
-                wp = ctypes.cast(args[10], ctypes.POINTER(c_int))
-                ints += [wp[i] for i in range(args[9])]
-            elif name == "pn2_sa_mlp_wide":  # (b, n, m, nsample, c, xyz, new_xyz, points, idx, nlayers, widths, ...)
-                wp = ctypes.cast(args[10], ctypes.POINTER(c_int))
-                ints += [wp[i] for i in range(args[9])]
-            self.trace.append((name, tuple(ints), s, e))
+            self.trace.append((key, tuple(ints), s, e))
             return rc
 
         call.__name__ = name
         setattr(self, name, call)  # cache
         return call
 
-
-# *_ld entry point -> (dense entry point, positions of the stride arguments among the numeric arguments, index of nlayers /
-# widths[] in the argument list or None)
-_LD_TRACE = {"pn2_fps_nested_ld": ("pn2_fps_nested", (3,), None, None),
-             "pn2_query_ball_point_ld": ("pn2_query_ball_point", (5,), None, None),
-             "pn2_three_nn_ld": ("pn2_three_nn", (3,), None, None),
-             "pn2_ball_query_bin_ld": ("pn2_ball_query_bin", (3,), None, None),
-             "pn2_sa_mlp_max_fused_ld": ("pn2_sa_mlp_max_fused", (5, 6), 11, 12),
-             "pn2_fp_mlp_fused_pre_ld": ("pn2_fp_mlp_fused_pre", (4,), 9, 10)}
 
 lib = _LibProxy(_raw)
 
@@ -336,9 +307,9 @@ def check(code, what):
         raise Pn2Error("%s failed: %s (code %d)" % (what, strerror(code), code))
 
 
-def ptr(t):
-    """device pointer of a tensor (None -> NULL)."""
-    return None if t is None else c_void_p(t.data_ptr())
+def ptr(t, byte_offset=0):
+    """device pointer of a tensor (None -> NULL), optionally `byte_offset` bytes into it."""
+    return None if t is None else c_void_p(t.data_ptr() + byte_offset)
 
 
 def rows_in_place(t):
@@ -355,6 +326,48 @@ def rows_in_place(t):
 
 def stream_ptr():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def launch(name, where, *args, may_refuse=False, stream=True):
+    """Call entry point `name` with `args` + torch's current stream (stream=False: a host-side query that takes none), on the
+    device of `where` (a tensor or a device).  The entry point is looked up on `lib` at call time (the trace / dup hooks see it).
+    -> True; with may_refuse, False when the library reports the configuration as unsupported (PN2_EUNSUP).  Every other failure
+    raises Pn2Error naming the entry point."""
+    with torch.cuda.device(getattr(where, "device", where)):
+        rc = getattr(lib, name)(*args, stream_ptr()) if stream else getattr(lib, name)(*args)
+    if may_refuse and rc == PN2_EUNSUP:
+        return False
+    check(rc, name)
+    return True
+
+
+def nbytes(t):
+    return t.numel() * t.element_size()
+
+
+# Host arrays for the entry points that read widths[] / pointer tables: ctypes arrays, accepted as they are where the argtype is
+# c_void_p.  The caller holds them until the call has returned (the library reads them before it returns).
+def int_array(values):
+    return (c_int * len(values))(*[int(v) for v in values])
+
+
+def float_array(values):
+    return (c_float * len(values))(*[float(v) for v in values])
+
+
+def u64_array(values):
+    """64-bit unsigned: byte counts and offsets (size_t), raw 64-bit payloads"""
+    return (ctypes.c_uint64 * len(values))(*[int(v) for v in values])
+
+
+def ptr_table(tensors):
+    """host table of device pointers (None -> NULL)"""
+    return (c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def layer_arrays(ws, bs):
+    """-> nlayers, widths[], weight pointers, bias pointers of a stack of dense layers (ws[i]: (cin_i, cout_i))"""
+    return len(ws), int_array([w.shape[1] for w in ws]), ptr_table(ws), ptr_table(bs)
 
 
 def require_cuda(*tensors):

@@ -19,14 +19,13 @@ The host-side attributes (scene_probas, label_weights, counts, the split table) 
 first sample call.  Call it once eagerly before capturing it in a graph.  One call at a time per dataset object: the
 workspace is shared between calls.
 """
-import ctypes
 import json
 import os
 
 import numpy as np
 import torch
 
-from .._lib import check, lib, ptr, stream_ptr
+from .._lib import launch, ptr, u64_array
 from ..util.metric import SEMANTIC3D_LABELS_NAMES
 from ..util.point_cloud_util import load_labels, read_point_cloud_pcd
 
@@ -156,10 +155,9 @@ class SemanticDataset:
                      offsets=t(self.scene_offsets, np.int32), cdf=t(self.scene_cdf, np.float64),
                      zsize=t(self.scene_z_size, np.float64), lw=t(self.label_weights, np.float32),
                      counter=torch.zeros(1, dtype=torch.int64, device=dev))
-        nbytes = ctypes.c_ulonglong(0)
-        check(lib.pn2_dataset_workspace_size(batch_size, self.max_chunks, ctypes.c_void_p(ctypes.addressof(nbytes))),
-              "pn2_dataset_workspace_size")
-        d["workspace"] = torch.zeros(nbytes.value + 256, dtype=torch.uint8, device=dev)  # kept zero by the kernels
+        nbytes = u64_array([0])  # written by the query
+        launch("pn2_dataset_workspace_size", dev, batch_size, self.max_chunks, nbytes, stream=False)
+        d["workspace"] = torch.zeros(nbytes[0] + 256, dtype=torch.uint8, device=dev)  # kept zero by the kernels
         d["b"] = batch_size
         self._dev = d
         return d
@@ -214,13 +212,12 @@ class SemanticDataset:
                 rot = torch.from_numpy(np.stack([ang, np.cos(ang), np.sin(ang)], 1)).to(dev)
         ws = d["workspace"]
         base = (-ws.data_ptr()) % 256
-        with torch.cuda.device(dev):
-            check(lib.pn2_dataset_sample(
-                b, n, self.num_scenes, self.max_chunks, int(self.use_color), int(bool(augment)), ptr(d["points"]),
-                ptr(d["colors"]), ptr(d["labels"]), ptr(d["offsets"]), ptr(d["cdf"]), ptr(d["zsize"]), ptr(d["lw"]),
-                int(d["lw"].numel()), self.box_size_x / 2, self.box_size_y / 2, self.seed, ptr(d["counter"]), ptr(scene),
-                ptr(center), ptr(mask), cap, ptr(rot), ptr(ws[base:]), ws.numel() - base, ptr(info), ptr(finfo), ptr(sel),
-                ptr(data), ptr(label), ptr(weights), stream_ptr()), "pn2_dataset_sample")
+        launch("pn2_dataset_sample", dev,
+               b, n, self.num_scenes, self.max_chunks, int(self.use_color), int(bool(augment)), ptr(d["points"]),
+               ptr(d["colors"]), ptr(d["labels"]), ptr(d["offsets"]), ptr(d["cdf"]), ptr(d["zsize"]), ptr(d["lw"]),
+               int(d["lw"].numel()), self.box_size_x / 2, self.box_size_y / 2, self.seed, ptr(d["counter"]), ptr(scene),
+               ptr(center), ptr(mask), cap, ptr(rot), ptr(ws[base:]), ws.numel() - base, ptr(info), ptr(finfo), ptr(sel),
+               ptr(data), ptr(label), ptr(weights))
         self.last_scene, self.last_center, self.last_cnt = info[:, 0], info[:, 1], info[:, 2]
         self.last_status, self.last_sel, self.last_angle = info[:, 7], sel, finfo[:, 0]
         return data, label, weights

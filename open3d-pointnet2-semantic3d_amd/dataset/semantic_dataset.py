@@ -10,7 +10,7 @@ to float32, the dtype the network is fed with.
 """
 import torch
 
-from .._lib import check, lib, ptr, require_cuda, stream_ptr
+from .._lib import launch, ptr, require_cuda
 from ..util.point_cloud_util import load_labels, read_point_cloud_pcd
 
 
@@ -55,10 +55,8 @@ class SemanticFileData:
         cap = int(capacity or len(self))
         idx = torch.empty((b, cap), dtype=torch.int32, device=self.points.device)
         cnt = torch.empty((b,), dtype=torch.int32, device=self.points.device)
-        with torch.cuda.device(self.points.device):
-            check(lib.pn2_scene_extract_z_box(len(self), ptr(self.points), b, ptr(c), self.box_size_x / 2, self.box_size_y / 2,
-                                              self.scene_z_size, cap, ptr(idx), ptr(cnt), stream_ptr()),
-                  "pn2_scene_extract_z_box")
+        launch("pn2_scene_extract_z_box", self.points, len(self), ptr(self.points), b, ptr(c), self.box_size_x / 2, self.box_size_y / 2,
+               self.scene_z_size, cap, ptr(idx), ptr(cnt))
         return idx, cnt
 
     def sample_batch(self, batch_size, num_points_per_sample, center_indices=None, sample_masks=None, capacity=None):
@@ -91,10 +89,9 @@ class SemanticFileData:
         labels = torch.zeros((batch_size, npts), dtype=torch.int32, device=dev)
         colors = torch.zeros((batch_size, npts, 3), dtype=torch.float32, device=dev)
         status = torch.zeros((batch_size,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            check(lib.pn2_scene_sample(batch_size, npts, cap, ptr(self.points), ptr(self.labels), ptr(self.colors), ptr(idx),
-                                       ptr(cnt), ptr(mask), self.box_size_x / 2, self.box_size_y / 2, ptr(sel), ptr(centered),
-                                       ptr(raw), ptr(labels), ptr(colors), ptr(status), stream_ptr()), "pn2_scene_sample")
+        launch("pn2_scene_sample", dev, batch_size, npts, cap, ptr(self.points), ptr(self.labels), ptr(self.colors), ptr(idx), ptr(cnt),
+               ptr(mask), self.box_size_x / 2, self.box_size_y / 2, ptr(sel), ptr(centered), ptr(raw), ptr(labels), ptr(colors),
+               ptr(status))
         self.last_status, self.last_sel, self.last_cnt = status, sel, cnt
         if self.strict:
             self.check_last()  # one host synchronisation per batch; strict=False leaves the check to the caller

@@ -7,7 +7,7 @@ Points / colours float64 like the reference's Open3D arrays; output voxels sorte
 the iteration order of a std::unordered_map, i.e. unspecified)."""
 import torch
 
-from ._lib import check, lib, ptr, require_cuda, stream_ptr
+from ._lib import launch, lib, ptr, require_cuda
 
 
 def down_sample_arrays(points, colors=None, labels=None, voxel_size=0.05, skip_label_zero=True):
@@ -31,10 +31,8 @@ def down_sample_arrays(points, colors=None, labels=None, voxel_size=0.05, skip_l
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
     ws = torch.empty((lib.pn2_voxel_downsample_workspace_bytes(n) + 255,), dtype=torch.uint8, device=dev)
     off = (-ws.data_ptr()) % 256
-    with torch.cuda.device(dev):
-        check(lib.pn2_voxel_downsample(n, ptr(points), ptr(colors), ptr(labels), float(voxel_size), ptr(out_p), ptr(out_c),
-                                       ptr(out_l), ptr(count), ptr(status), ws.data_ptr() + off, ws.numel() - off,
-                                       stream_ptr()), "pn2_voxel_downsample")
+    launch("pn2_voxel_downsample", dev, n, ptr(points), ptr(colors), ptr(labels), float(voxel_size), ptr(out_p), ptr(out_c), ptr(out_l),
+           ptr(count), ptr(status), ws.data_ptr() + off, ws.numel() - off)
     st, m = int(status.item()), int(count.item())
     if st:
         raise ValueError("pn2_voxel_downsample: %s" % {1: "voxel index exceeds 21 bits per axis", 2: "label outside [0,64)"}[st])

@@ -216,27 +216,25 @@ def get_model(point_cloud, is_training, num_class, hyperparams, bn_decay=None, g
 class _WeightedCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred2d, label, w):
-        from ._lib import check, lib, ptr, stream_ptr
+        from ._lib import launch, ptr
         rows, c = pred2d.shape
         lse = torch.empty((rows,), dtype=torch.float32, device=pred2d.device)
         acc = torch.empty((2,), dtype=torch.float64, device=pred2d.device)
         loss = torch.empty((), dtype=torch.float32, device=pred2d.device)
-        with torch.cuda.device(pred2d.device):
-            check(lib.pn2_weighted_ce_forward(rows, c, ptr(pred2d), ptr(label), int(label.dtype == torch.int64), ptr(w),
-                                              ptr(lse), ptr(acc), ptr(loss), stream_ptr()), "pn2_weighted_ce_forward")
+        launch("pn2_weighted_ce_forward", pred2d, rows, c, ptr(pred2d), ptr(label), int(label.dtype == torch.int64), ptr(w), ptr(lse),
+               ptr(acc), ptr(loss))
         ctx.save_for_backward(pred2d, label, w, lse, acc)
         return loss
 
     @staticmethod
     def backward(ctx, gout):
-        from ._lib import check, lib, ptr, stream_ptr
+        from ._lib import launch, ptr
         pred2d, label, w, lse, acc = ctx.saved_tensors
         rows, c = pred2d.shape
         d = torch.empty_like(pred2d)
         g = gout.contiguous().float()
-        with torch.cuda.device(pred2d.device):
-            check(lib.pn2_weighted_ce_backward(rows, c, ptr(pred2d), ptr(label), int(label.dtype == torch.int64), ptr(w),
-                                               ptr(lse), ptr(acc), ptr(g), ptr(d), stream_ptr()), "pn2_weighted_ce_backward")
+        launch("pn2_weighted_ce_backward", pred2d, rows, c, ptr(pred2d), ptr(label), int(label.dtype == torch.int64), ptr(w), ptr(lse),
+               ptr(acc), ptr(g), ptr(d))
         return d, None, None
 
 

@@ -8,7 +8,7 @@ knn_point / select_top_k (tf_grouping.py:31-43,64-89) are not on the model's pat
 import torch
 
 from .. import config
-from .._lib import PN2_EUNSUP, check, lib, ptr, require_cuda, rows_in_place, stream_ptr
+from .._lib import float_array, int_array, launch, lib, ptr, ptr_table, require_cuda, rows_in_place
 
 
 def query_ball_point(radius, nsample, xyz1, xyz2, kernel=0, arith_mode=None):
@@ -35,22 +35,17 @@ def query_ball_point(radius, nsample, xyz1, xyz2, kernel=0, arith_mode=None):
     m = xyz2.shape[1]
     idx = torch.empty((b, m, nsample), dtype=torch.int32, device=xyz1.device)
     cnt = torch.empty((b, m), dtype=torch.int32, device=xyz1.device)
-    with torch.cuda.device(xyz1.device):
-        if ld1 != 3:
-            rc = PN2_EUNSUP if kernel else lib.pn2_query_ball_point_ld(
-                b, n, m, float(radius), int(nsample), ptr(xyz1), ld1, ptr(xyz2), ptr(idx), ptr(cnt),
-                config.bq_mode(arith_mode), stream_ptr())
-            if rc != PN2_EUNSUP:
-                check(rc, "pn2_query_ball_point_ld")
-                return idx, cnt
-            xyz1 = xyz1.contiguous()  # no strided kernel for this shape: query a dense copy
-        if kernel:
-            check(lib.pn2_query_ball_point_kernel(b, n, m, float(radius), int(nsample), ptr(xyz1), ptr(xyz2), ptr(idx),
-                                                  ptr(cnt), config.bq_mode(arith_mode), int(kernel), stream_ptr()),
-                  "pn2_query_ball_point_kernel")
-        else:
-            check(lib.pn2_query_ball_point(b, n, m, float(radius), int(nsample), ptr(xyz1), ptr(xyz2), ptr(idx),
-                                           ptr(cnt), config.bq_mode(arith_mode), stream_ptr()), "pn2_query_ball_point")
+    if ld1 != 3:
+        if not kernel and launch("pn2_query_ball_point_ld", xyz1, b, n, m, float(radius), int(nsample), ptr(xyz1), ld1, ptr(xyz2),
+                                 ptr(idx), ptr(cnt), config.bq_mode(arith_mode), may_refuse=True):
+            return idx, cnt
+        xyz1 = xyz1.contiguous()  # no strided kernel for this shape: query a dense copy
+    if kernel:
+        launch("pn2_query_ball_point_kernel", xyz1, b, n, m, float(radius), int(nsample), ptr(xyz1), ptr(xyz2), ptr(idx), ptr(cnt),
+               config.bq_mode(arith_mode), int(kernel))
+    else:
+        launch("pn2_query_ball_point", xyz1, b, n, m, float(radius), int(nsample), ptr(xyz1), ptr(xyz2), ptr(idx), ptr(cnt),
+               config.bq_mode(arith_mode))
     return idx, cnt
 
 
@@ -92,9 +87,7 @@ def ball_query_bin(radius, xyz1, out=None):
     # a column block of a wider batch (point_cloud[:, :, 0:3]) is read where it lies; other layouts are copied dense
     xyz1, ld1 = rows_in_place(xyz1)
     bins = out if out is not None else ball_query_bin_alloc(xyz1)  # `out`: allocated by the caller (on ITS stream)
-    with torch.cuda.device(xyz1.device):
-        check(lib.pn2_ball_query_bin_ld(b, n, float(radius), ptr(xyz1), ld1, ptr(bins), bins.numel(), stream_ptr()),
-              "pn2_ball_query_bin_ld")
+    launch("pn2_ball_query_bin_ld", xyz1, b, n, float(radius), ptr(xyz1), ld1, ptr(bins), bins.numel())
     # what the bins describe: the C entry point takes an opaque pointer and cannot check it -- bins of a smaller
     # cloud would be read out of bounds, bins of a smaller radius would silently miss neighbours
     # ... and bins of ANOTHER cloud of the same shape (a reused `out=` workspace after the input batch changed) would return wrong
@@ -128,9 +121,8 @@ def query_ball_point_binned(radius, nsample, xyz1, xyz2, bins, arith_mode=None):
         raise ValueError("bins: expected a 256-byte aligned uint8 tensor of b * pn2_ball_query_bin_bytes(n) bytes")
     idx = torch.empty((b, m, nsample), dtype=torch.int32, device=xyz1.device)
     cnt = torch.empty((b, m), dtype=torch.int32, device=xyz1.device)
-    with torch.cuda.device(xyz1.device):
-        check(lib.pn2_query_ball_point_binned(b, n, m, float(radius), int(nsample), ptr(xyz1), ptr(xyz2), ptr(bins), ptr(idx),
-                                              ptr(cnt), config.bq_mode(arith_mode), stream_ptr()), "pn2_query_ball_point_binned")
+    launch("pn2_query_ball_point_binned", xyz1, b, n, m, float(radius), int(nsample), ptr(xyz1), ptr(xyz2), ptr(bins), ptr(idx),
+           ptr(cnt), config.bq_mode(arith_mode))
     return idx, cnt
 
 
@@ -138,8 +130,6 @@ def query_ball_point_multi(radius_list, nsample_list, xyz1, xyz2, arith_mode=Non
     """[(idx, pts_cnt) for each (radius, nsample)] from ONE scan of xyz1 (pn2_query_ball_point_multi): what
     pointnet_sa_module_msg needs (util/pointnet_util.py:245-250 runs query_ball_point once per radius).
     Bit-identical to separate query_ball_point calls; falls back to them when the configuration is unsupported."""
-    import ctypes
-    from .._lib import PN2_EUNSUP
     if len(radius_list) != len(nsample_list) or len(radius_list) == 0:
         raise ValueError("radius_list and nsample_list must have the same non-zero length")
     for radius, nsample in zip(radius_list, nsample_list):
@@ -155,16 +145,8 @@ def query_ball_point_multi(radius_list, nsample_list, xyz1, xyz2, arith_mode=Non
         m = x2.shape[1]
         idxs = [torch.empty((b, m, int(k)), dtype=torch.int32, device=x1.device) for k in nsample_list]
         cnts = [torch.empty((b, m), dtype=torch.int32, device=x1.device) for _ in nsample_list]
-        radii = (ctypes.c_float * R)(*[float(r) for r in radius_list])
-        nss = (ctypes.c_int * R)(*[int(k) for k in nsample_list])
-        ip = (ctypes.c_void_p * R)(*[t.data_ptr() for t in idxs])
-        cp = (ctypes.c_void_p * R)(*[t.data_ptr() for t in cnts])
-        with torch.cuda.device(x1.device):
-            rc = lib.pn2_query_ball_point_multi(b, n, m, R, ctypes.cast(radii, ctypes.c_void_p), ctypes.cast(nss, ctypes.c_void_p),
-                                                ptr(x1), ptr(x2), ctypes.cast(ip, ctypes.c_void_p),
-                                                ctypes.cast(cp, ctypes.c_void_p), config.bq_mode(arith_mode), stream_ptr())
-        if rc != PN2_EUNSUP:
-            check(rc, "pn2_query_ball_point_multi")
+        if launch("pn2_query_ball_point_multi", x1, b, n, m, R, float_array(radius_list), int_array(nsample_list), ptr(x1), ptr(x2),
+                  ptr_table(idxs), ptr_table(cnts), config.bq_mode(arith_mode), may_refuse=True):
             return list(zip(idxs, cnts))
     return [query_ball_point(r, k, xyz1, xyz2, arith_mode=arith_mode) for r, k in zip(radius_list, nsample_list)]
 
@@ -175,9 +157,7 @@ class _GroupPoint(torch.autograd.Function):
         b, n, c = points.shape
         _, m, ns = idx.shape
         out = torch.empty((b, m, ns, c), dtype=torch.float32, device=points.device)
-        with torch.cuda.device(points.device):
-            check(lib.pn2_group_point(b, n, c, m, ns, ptr(points), ptr(idx), ptr(out), stream_ptr()),
-                  "pn2_group_point")
+        launch("pn2_group_point", points, b, n, c, m, ns, ptr(points), ptr(idx), ptr(out))
         ctx.save_for_backward(idx)
         ctx.n = n
         return out
@@ -190,9 +170,7 @@ class _GroupPoint(torch.autograd.Function):
         gp = torch.empty((b, ctx.n, c), dtype=torch.float32, device=grad_out.device)
         nbytes = lib.pn2_group_point_grad_workspace_bytes(b, ctx.n, m, ns)
         ws = torch.empty(nbytes // 4, dtype=torch.int32, device=grad_out.device)
-        with torch.cuda.device(grad_out.device):
-            check(lib.pn2_group_point_grad_ws(b, ctx.n, c, m, ns, ptr(grad_out), ptr(idx), ptr(gp), ptr(ws), nbytes,
-                                              stream_ptr()), "pn2_group_point_grad_ws")
+        launch("pn2_group_point_grad_ws", grad_out, b, ctx.n, c, m, ns, ptr(grad_out), ptr(idx), ptr(gp), ptr(ws), nbytes)
         return gp, None
 
 
@@ -222,9 +200,7 @@ def select_top_k(k, dist):
     b, m, n = dist.shape
     outi = torch.empty((b, m, n), dtype=torch.int32, device=dist.device)
     out = torch.empty((b, m, n), dtype=torch.float32, device=dist.device)
-    with torch.cuda.device(dist.device):
-        check(lib.pn2_selection_sort(b, n, m, int(k), ptr(dist), ptr(outi), ptr(out), stream_ptr()),
-              "pn2_selection_sort")
+    launch("pn2_selection_sort", dist, b, n, m, int(k), ptr(dist), ptr(outi), ptr(out))
     return outi, out
 
 

@@ -5,11 +5,10 @@ Same names, argument order and shapes as the reference wrappers
 :62-72).  The reference runs these on the CPU (tf_interpolate.cpp:184,283,378,482
 DEVICE_CPU); here they stay on the GPU.
 """
-import ctypes
 
 import torch
 
-from .._lib import check, lib, ptr, require_cuda, rows_in_place, stream_ptr
+from .._lib import launch, lib, ptr, require_cuda, rows_in_place
 
 
 def three_nn(xyz1, xyz2):
@@ -29,11 +28,10 @@ def three_nn(xyz1, xyz2):
     m = xyz2.shape[1]
     dist = torch.empty((b, n, 3), dtype=torch.float32, device=xyz1.device)
     idx = torch.empty((b, n, 3), dtype=torch.int32, device=xyz1.device)
-    with torch.cuda.device(xyz1.device):
-        if ld1 == 3:
-            check(lib.pn2_three_nn(b, n, m, ptr(xyz1), ptr(xyz2), ptr(dist), ptr(idx), stream_ptr()), "pn2_three_nn")
-        else:
-            check(lib.pn2_three_nn_ld(b, n, m, ptr(xyz1), ld1, ptr(xyz2), ptr(dist), ptr(idx), stream_ptr()), "pn2_three_nn_ld")
+    if ld1 == 3:
+        launch("pn2_three_nn", xyz1, b, n, m, ptr(xyz1), ptr(xyz2), ptr(dist), ptr(idx))
+    else:
+        launch("pn2_three_nn_ld", xyz1, b, n, m, ptr(xyz1), ld1, ptr(xyz2), ptr(dist), ptr(idx))
     return dist, idx
 
 
@@ -43,9 +41,7 @@ class _ThreeInterpolate(torch.autograd.Function):
         b, m, c = points.shape
         n = idx.shape[1]
         out = torch.empty((b, n, c), dtype=torch.float32, device=points.device)
-        with torch.cuda.device(points.device):
-            check(lib.pn2_three_interpolate(b, m, c, n, ptr(points), ptr(idx), ptr(weight), ptr(out),
-                                            stream_ptr()), "pn2_three_interpolate")
+        launch("pn2_three_interpolate", points, b, m, c, n, ptr(points), ptr(idx), ptr(weight), ptr(out))
         ctx.save_for_backward(idx, weight)
         ctx.m = m
         return out
@@ -63,9 +59,7 @@ def three_interpolate_grad(grad_out, idx, weight, m):
     gp = torch.empty((b, m, c), dtype=torch.float32, device=grad_out.device)
     nbytes = lib.pn2_three_interpolate_grad_workspace_bytes(b, n, m)
     ws = torch.empty(nbytes // 4, dtype=torch.int32, device=grad_out.device)
-    with torch.cuda.device(grad_out.device):
-        check(lib.pn2_three_interpolate_grad_ws(b, n, c, m, ptr(grad_out), ptr(idx), ptr(weight), ptr(gp), ptr(ws),
-                                                nbytes, stream_ptr()), "pn2_three_interpolate_grad_ws")
+    launch("pn2_three_interpolate_grad_ws", grad_out, b, n, c, m, ptr(grad_out), ptr(idx), ptr(weight), ptr(gp), ptr(ws), nbytes)
     return gp
 
 
@@ -109,8 +103,6 @@ def interpolate_label_with_color(sparse_points, sparse_labels, dense_points, knn
     wbytes = int(lib.pn2_interpolate_label_workspace_bytes(ns))
     ws = torch.empty((wbytes + 256,), dtype=torch.uint8, device=dev)
     off = (-ws.data_ptr()) % 256
-    with torch.cuda.device(dev):
-        check(lib.pn2_interpolate_label_with_color(ns, nd, ptr(sp), ptr(sl), ptr(dp), ptr(labels), ptr(colors), knn,
-                                                   ctypes.c_void_p(ws.data_ptr() + off), wbytes, stream_ptr()),
-              "pn2_interpolate_label_with_color")
+    launch("pn2_interpolate_label_with_color", dev, ns, nd, ptr(sp), ptr(sl), ptr(dp), ptr(labels), ptr(colors), knn, ptr(ws, off),
+           wbytes)
     return labels, colors

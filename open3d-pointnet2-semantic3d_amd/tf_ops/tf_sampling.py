@@ -8,7 +8,7 @@ C ABI of libpn2_hip.so instead of tf.load_op_library.
 import torch
 
 from .. import config
-from .._lib import check, lib, ptr, require_cuda, rows_in_place, stream_ptr
+from .._lib import launch, lib, ptr, require_cuda, rows_in_place
 
 
 def _chk_xyz(t, name, op):
@@ -76,16 +76,13 @@ FPS_REG_MAX, FPS_BUCKET_MAX = 16384, 131072
 
 
 def _fps_large(npoint, inp, want_xyz, arith_mode=None):
-    import ctypes
     b, n, _ = inp.shape
     out = torch.empty((b, npoint), dtype=torch.int32, device=inp.device)
     new_xyz = torch.empty((b, npoint, 3), dtype=torch.float32, device=inp.device) if want_xyz else None
     wbytes = int(lib.pn2_fps_large_workspace_bytes(b, n))
     ws = torch.empty((wbytes + 256,), dtype=torch.uint8, device=inp.device)
     off = (-ws.data_ptr()) % 256
-    with torch.cuda.device(inp.device):
-        check(lib.pn2_fps_large(b, n, int(npoint), ptr(inp), ctypes.c_void_p(ws.data_ptr() + off), wbytes, ptr(out),
-                                ptr(new_xyz), config.fps_mode(arith_mode), stream_ptr()), "pn2_fps_large")
+    launch("pn2_fps_large", inp, b, n, int(npoint), ptr(inp), ptr(ws, off), wbytes, ptr(out), ptr(new_xyz), config.fps_mode(arith_mode))
     return out, new_xyz
 
 
@@ -110,13 +107,12 @@ def farthest_point_sample_with_ties(npoint, inp, arith_mode=None, want_xyz=False
         out = torch.empty((b, npoint), dtype=torch.int32, device=inp.device)
         new_xyz = torch.empty((b, npoint, 3), dtype=torch.float32, device=inp.device) if want_xyz else None
         tie = torch.empty((b,), dtype=torch.int32, device=inp.device) if USE_NESTED_FPS else None
-        with torch.cuda.device(inp.device):
-            if ld == 3:
-                check(lib.pn2_fps_nested(b, n, int(npoint), ptr(inp), None, ptr(out), ptr(new_xyz), ptr(tie_in), ptr(tie),
-                                         config.fps_mode(arith_mode), stream_ptr()), "pn2_fps_nested")
-            else:
-                check(lib.pn2_fps_nested_ld(b, n, int(npoint), ptr(inp), ld, ptr(out), ptr(new_xyz), ptr(tie_in), ptr(tie),
-                                            config.fps_mode(arith_mode), stream_ptr()), "pn2_fps_nested_ld")
+        if ld == 3:
+            launch("pn2_fps_nested", inp, b, n, int(npoint), ptr(inp), None, ptr(out), ptr(new_xyz), ptr(tie_in), ptr(tie),
+                   config.fps_mode(arith_mode))
+        else:
+            launch("pn2_fps_nested_ld", inp, b, n, int(npoint), ptr(inp), ld, ptr(out), ptr(new_xyz), ptr(tie_in), ptr(tie),
+                   config.fps_mode(arith_mode))
         return out, tie, new_xyz
     inp = inp.detach().contiguous()
     if USE_BUCKET_FPS and FPS_REG_MAX < n <= FPS_BUCKET_MAX:
@@ -128,9 +124,8 @@ def farthest_point_sample_with_ties(npoint, inp, arith_mode=None, want_xyz=False
     temp = None
     if n > 16384:  # PN2_FPS_MAX_REG_POINTS: the streaming kernel needs the reference's (32,n) scratch
         temp = torch.empty((min(b, 32), n), dtype=torch.float32, device=inp.device)
-    with torch.cuda.device(inp.device):
-        check(lib.pn2_fps_nested(b, n, int(npoint), ptr(inp), ptr(temp), ptr(out), ptr(new_xyz), ptr(tie_in), ptr(tie),
-                                 config.fps_mode(arith_mode), stream_ptr()), "pn2_fps_nested")
+    launch("pn2_fps_nested", inp, b, n, int(npoint), ptr(inp), ptr(temp), ptr(out), ptr(new_xyz), ptr(tie_in), ptr(tie),
+           config.fps_mode(arith_mode))
     return out, tie, new_xyz
 
 
@@ -140,8 +135,7 @@ class _GatherPoint(torch.autograd.Function):
         b, n, _ = inp.shape
         m = idx.shape[1]
         out = torch.empty((b, m, 3), dtype=torch.float32, device=inp.device)
-        with torch.cuda.device(inp.device):
-            check(lib.pn2_gather_point(b, n, m, ptr(inp), ptr(idx), ptr(out), stream_ptr()), "pn2_gather_point")
+        launch("pn2_gather_point", inp, b, n, m, ptr(inp), ptr(idx), ptr(out))
         ctx.save_for_backward(idx)
         ctx.n = n
         return out
@@ -152,9 +146,7 @@ class _GatherPoint(torch.autograd.Function):
         out_g = out_g.contiguous()
         b, m, _ = out_g.shape
         inp_g = torch.empty((b, ctx.n, 3), dtype=torch.float32, device=out_g.device)
-        with torch.cuda.device(out_g.device):
-            check(lib.pn2_gather_point_grad(b, ctx.n, m, ptr(out_g), ptr(idx), ptr(inp_g), stream_ptr()),
-                  "pn2_gather_point_grad")
+        launch("pn2_gather_point_grad", out_g, b, ctx.n, m, ptr(out_g), ptr(idx), ptr(inp_g))
         return inp_g, None
 
 
@@ -191,6 +183,5 @@ def prob_sample(inp, inpr):
     inp, inpr = inp.detach().contiguous(), inpr.detach().contiguous()
     temp = torch.empty((b, n), dtype=torch.float32, device=inp.device)
     out = torch.empty((b, m), dtype=torch.int32, device=inp.device)
-    with torch.cuda.device(inp.device):
-        check(lib.pn2_prob_sample(b, n, m, ptr(inp), ptr(inpr), ptr(temp), ptr(out), stream_ptr()), "pn2_prob_sample")
+    launch("pn2_prob_sample", inp, b, n, m, ptr(inp), ptr(inpr), ptr(temp), ptr(out))
     return out

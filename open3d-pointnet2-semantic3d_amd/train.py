@@ -10,7 +10,7 @@ import torch
 
 from . import dist as pdist
 from . import model
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import launch, ptr
 from .util import metric, tf_util
 
 
@@ -222,9 +222,8 @@ class Trainer:
         return self.bucket.pack_late_and_bind()
 
     def _adam(self, flat_g):
-        with torch.cuda.device(self.flat_p.device):
-            check(lib.pn2_adam_step(self.flat_p.numel(), ptr(self.flat_p), ptr(flat_g), ptr(self.flat_m), ptr(self.flat_v),
-                                    ptr(self.hyper), stream_ptr()), "pn2_adam_step")
+        launch("pn2_adam_step", self.flat_p, self.flat_p.numel(), ptr(self.flat_p), ptr(flat_g), ptr(self.flat_m), ptr(self.flat_v),
+               ptr(self.hyper))
 
     def _step_body(self, pc, labels, smpw, decay, geometry=None):
         loss, flat_g = self._forward_backward(pc, labels, smpw, decay, geometry)

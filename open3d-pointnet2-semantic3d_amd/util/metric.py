@@ -40,7 +40,7 @@ def confusion_update(logits, labels, confusion=None, invalid=None, pred=None, lo
     confusion: int64 tensor of C*C elements (added to), invalid: int64 tensor of one element (added to: labels outside
     [0, C)), pred: int32 tensor of rows elements (written: the argmax), loss / loss_acc: device f32 scalar and float64 [sum,
     count] (added to).  Every output is optional; at least one must be given."""
-    from .._lib import check, lib, ptr, require_cuda, stream_ptr
+    from .._lib import launch, ptr, require_cuda
     require_cuda(logits, labels)
     c = int(logits.shape[-1])
     z = logits.detach().reshape(-1, c)
@@ -55,9 +55,8 @@ def confusion_update(logits, labels, confusion=None, invalid=None, pred=None, lo
                            ("loss_acc", loss_acc, 2, torch.float64)):
         if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != z.device):
             raise ValueError("%s: a contiguous %s tensor of %d elements on %s expected" % (name, dt, n, z.device))
-    with torch.cuda.device(z.device):
-        check(lib.pn2_confusion_update(rows, c, ptr(z), ptr(lab), int(lab.dtype == torch.int64), ptr(pred), ptr(confusion),
-                                       ptr(invalid), ptr(loss), ptr(loss_acc), stream_ptr()), "pn2_confusion_update")
+    launch("pn2_confusion_update", z, rows, c, ptr(z), ptr(lab), int(lab.dtype == torch.int64), ptr(pred), ptr(confusion), ptr(invalid),
+           ptr(loss), ptr(loss_acc))
 
 
 class ConfusionMatrix:

@@ -11,12 +11,11 @@ Inference (is_training=False) never materialises the grouped (B,M,K,C) tensor
 when the fused kernel applies; training uses the HIP index/gather ops with
 autograd plus differentiable torch layers.
 """
-import ctypes
 
 import torch
 
 from . import tf_util
-from .._lib import PN2_EUNSUP, check, lib, ptr, require_cuda, rows_in_place, stream_ptr
+from .._lib import float_array, int_array, launch, lib, ptr, ptr_table, require_cuda, rows_in_place, u64_array
 from ..tf_ops import tf_grouping
 from ..tf_ops.tf_grouping import query_ball_point_multi, group_point, knn_point, query_ball_point
 from ..tf_ops.tf_interpolate import three_interpolate, three_nn
@@ -101,7 +100,7 @@ def _sa_fused_inference(xyz, new_xyz, points, idx, mlp, bn, conv_scope_fmt, pool
         bs.append(b2)
         cin = cout
     L = len(mlp)
-    widths = (ctypes.c_int * L)(*mlp)
+    widths, bptrs = int_array(mlp), ptr_table(bs)
     oshape = (b, m, mlp[-1]) if pool else (b, m, nsample, mlp[-1])
     out = torch.empty(oshape, dtype=torch.float32, device=xyz.device)
     if (USE_HOISTED_SA and not bf16 and nsample == 32 and c >= 32 and c % 4 == 0
@@ -111,40 +110,23 @@ def _sa_fused_inference(xyz, new_xyz, points, idx, mlp, bn, conv_scope_fmt, pool
         w1x, w1f = tf_util.split_first_layer(ws[0], 3, c, "sa_pre")   # rows [0,3) = xyz, [3, 3+c) = features
         xyz, points = xyz.contiguous(), points.contiguous()
         zf = tf_util.hoist_gemm(points.reshape(b * n, c), w1f)
-        wl = [w1x] + ws[1:]
-        wptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in wl])
-        bptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in bs])
-        with torch.cuda.device(xyz.device):
-            rc = lib.pn2_sa_mlp_fused_pre(b, n, m, nsample, ptr(xyz), ptr(new_xyz), ptr(zf), ptr(idx), L,
-                                          ctypes.cast(widths, ctypes.c_void_p), ctypes.cast(wptrs, ctypes.c_void_p),
-                                          ctypes.cast(bptrs, ctypes.c_void_p), int(bool(pool)), ptr(out), stream_ptr())
-        if rc != PN2_EUNSUP:
-            check(rc, "pn2_sa_mlp_fused_pre")
+        if launch("pn2_sa_mlp_fused_pre", xyz, b, n, m, nsample, ptr(xyz), ptr(new_xyz), ptr(zf), ptr(idx), L, widths,
+                  ptr_table([w1x] + ws[1:]), bptrs, int(bool(pool)), ptr(out), may_refuse=True):
             return out
-    wptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in ws])
-    bptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in bs])
+    wptrs = ptr_table(ws)
     xyz_v, ldx = rows_in_place(xyz)
     pts, ldp = (None, 0) if points is None else rows_in_place(points)
     if pool and not bf16 and (ldx != 3 or (points is not None and ldp != c)):
         # column blocks of a wider batch (model.get_sa_fp_features: the xyz / rgb halves of point_cloud (b,n,6)) gathered in place
-        with torch.cuda.device(xyz.device):
-            rc = lib.pn2_sa_mlp_max_fused_ld(b, n, m, nsample, c, ptr(xyz_v), ldx, ptr(new_xyz), ptr(pts), ldp, ptr(idx), L,
-                                             ctypes.cast(widths, ctypes.c_void_p), ctypes.cast(wptrs, ctypes.c_void_p),
-                                             ctypes.cast(bptrs, ctypes.c_void_p), ptr(out), stream_ptr())
-        if rc != PN2_EUNSUP:
-            check(rc, "pn2_sa_mlp_max_fused_ld")
+        if launch("pn2_sa_mlp_max_fused_ld", xyz, b, n, m, nsample, c, ptr(xyz_v), ldx, ptr(new_xyz), ptr(pts), ldp, ptr(idx), L,
+                  widths, wptrs, bptrs, ptr(out), may_refuse=True):
             return out
     xyz_v = xyz_v.contiguous()
     pts = None if pts is None else pts.contiguous()
-    fn = lib.pn2_sa_mlp_max_fused_bf16 if bf16 else (lib.pn2_sa_mlp_max_fused if pool else lib.pn2_sa_mlp_rows_fused)
-    with torch.cuda.device(xyz.device):
-        rc = fn(b, n, m, nsample, c, ptr(xyz_v), ptr(new_xyz), ptr(pts), ptr(idx), L,
-                                      ctypes.cast(widths, ctypes.c_void_p), ctypes.cast(wptrs, ctypes.c_void_p),
-                                      ctypes.cast(bptrs, ctypes.c_void_p), ptr(out), stream_ptr())
-    if rc == PN2_EUNSUP:
-        return None
-    check(rc, "pn2_sa_mlp_max_fused")
-    return out
+    name = "pn2_sa_mlp_max_fused_bf16" if bf16 else ("pn2_sa_mlp_max_fused" if pool else "pn2_sa_mlp_rows_fused")
+    ok = launch(name, xyz, b, n, m, nsample, c, ptr(xyz_v), ptr(new_xyz), ptr(pts), ptr(idx), L, widths, wptrs, bptrs, ptr(out),
+                may_refuse=True)
+    return out if ok else None
 
 
 def _sa_group_concat(xyz, new_xyz, points, idx):
@@ -153,9 +135,7 @@ def _sa_group_concat(xyz, new_xyz, points, idx):
     c = 0 if points is None else points.shape[2]
     out = torch.empty((b, m, nsample, 3 + c), dtype=torch.float32, device=xyz.device)
     pts = None if points is None else points.contiguous()
-    with torch.cuda.device(xyz.device):
-        check(lib.pn2_sa_group_concat(b, n, m, nsample, c, ptr(xyz), ptr(new_xyz), ptr(pts), ptr(idx), ptr(out),
-                                      stream_ptr()), "pn2_sa_group_concat")
+    launch("pn2_sa_group_concat", xyz, b, n, m, nsample, c, ptr(xyz), ptr(new_xyz), ptr(pts), ptr(idx), ptr(out))
     return out
 
 
@@ -170,9 +150,7 @@ def scatter_plan(idx, nsrc, weight=None, weight_kind=None):
     kind = (1 if weight_kind is None else weight_kind) if weight is not None else 0
     nbytes = lib.pn2_scatter_plan_bytes(b, nent, nsrc)
     plan = torch.empty(nbytes, dtype=torch.uint8, device=idx.device)
-    with torch.cuda.device(idx.device):
-        check(lib.pn2_scatter_plan_build(b, nent, div, nsrc, ptr(idx), ptr(weight), kind, ptr(plan), nbytes, stream_ptr()),
-              "pn2_scatter_plan_build")
+    launch("pn2_scatter_plan_build", idx, b, nent, div, nsrc, ptr(idx), ptr(weight), kind, ptr(plan), nbytes)
     return plan
 
 
@@ -201,12 +179,8 @@ def scatter_plans(specs):
             offs.append(total)
             total += (lib.pn2_scatter_plan_bytes(b, ne, int(ns)) + 15) // 16 * 16
         buf = torch.empty(total, dtype=torch.uint8, device=dev)
-        k = len(chunk)
-        ia = lambda v: (ctypes.c_int * k)(*v)  # noqa: E731
-        pa = lambda ts: (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in ts])  # noqa: E731
-        with torch.cuda.device(dev):
-            check(lib.pn2_scatter_plan_build_multi(k, b, ia(nent), ia(div), ia(nsrc), pa(idxs), pa(ws), ia(kinds), ptr(buf),
-                                                   (ctypes.c_size_t * k)(*offs), total, stream_ptr()), "pn2_scatter_plan_build_multi")
+        launch("pn2_scatter_plan_build_multi", dev, len(chunk), b, int_array(nent), int_array(div), int_array(nsrc), ptr_table(idxs),
+               ptr_table(ws), int_array(kinds), ptr(buf), u64_array(offs), total)
         for j, (i, _) in enumerate(chunk):
             out[i] = buf[offs[j]:offs[j] + lib.pn2_scatter_plan_bytes(b, nent[j], nsrc[j])]
     return out
@@ -218,9 +192,7 @@ def _scatter_plan_apply(plan, rows_in, col0, c, nent, div, nsrc):
     if not rows_in.is_contiguous():
         rows_in = rows_in.contiguous()
     out = torch.empty((b, nsrc, c), dtype=torch.float32, device=rows_in.device)
-    with torch.cuda.device(rows_in.device):
-        check(lib.pn2_scatter_plan_apply(b, nent, div, c, nsrc, ctypes.c_void_p(rows_in.data_ptr() + 4 * col0), width,
-                                         ptr(plan), plan.numel(), ptr(out), stream_ptr()), "pn2_scatter_plan_apply")
+    launch("pn2_scatter_plan_apply", rows_in, b, nent, div, c, nsrc, ptr(rows_in, 4 * col0), width, ptr(plan), plan.numel(), ptr(out))
     return out
 
 
@@ -252,9 +224,7 @@ class _SAGroupConcat(torch.autograd.Function):
         gp = torch.empty((b, ctx.n, ctx.c), dtype=torch.float32, device=g.device)
         nbytes = lib.pn2_group_point_grad_workspace_bytes(b, ctx.n, m, ns)
         ws = torch.empty(nbytes // 4, dtype=torch.int32, device=g.device)
-        with torch.cuda.device(g.device):
-            check(lib.pn2_group_point_grad_ws(b, ctx.n, ctx.c, m, ns, ptr(g), ptr(idx), ptr(gp), ptr(ws), nbytes,
-                                              stream_ptr()), "pn2_group_point_grad_ws")
+        launch("pn2_group_point_grad_ws", g, b, ctx.n, ctx.c, m, ns, ptr(g), ptr(idx), ptr(gp), ptr(ws), nbytes)
         return None, None, gp, None, None
 
 
@@ -357,16 +327,11 @@ def coarse_geometry(xyz0, npoints, radii, nsamples, want_nn=True, fps_arith_mode
         out.append(lv)
         n = m
     tie_out = torch.empty((b,), dtype=torch.int32, device=dev)
-    ia = lambda vals: (ctypes.c_int * nlev)(*[int(v) for v in vals])  # noqa: E731
-    pa = lambda ts: (ctypes.c_void_p * nlev)(*[None if t is None else t.data_ptr() for t in ts])  # noqa: E731
-    with torch.cuda.device(dev):
-        check(lib.pn2_coarse_geometry(b, n0, nlev, ia(npoints), (ctypes.c_float * nlev)(*[float(r) for r in radii]), ia(nsamples),
-                                      ptr(xyz0), ptr(tie_in), pa([lv["fps_idx"] for lv in out]), pa([lv["new_xyz"] for lv in out]),
-                                      pa([lv["idx"] for lv in out]), pa([lv["cnt"] for lv in out]),
-                                      pa([lv["nn"][0] if want_nn else None for lv in out]),
-                                      pa([lv["nn"][1] if want_nn else None for lv in out]), ptr(tie_out),
-                                      config.fps_mode(fps_arith_mode), config.bq_mode(bq_arith_mode), stream_ptr()),
-              "pn2_coarse_geometry")
+    launch("pn2_coarse_geometry", dev, b, n0, nlev, int_array(npoints), float_array(radii), int_array(nsamples), ptr(xyz0), ptr(tie_in),
+           ptr_table([lv["fps_idx"] for lv in out]), ptr_table([lv["new_xyz"] for lv in out]), ptr_table([lv["idx"] for lv in out]),
+           ptr_table([lv["cnt"] for lv in out]), ptr_table([lv["nn"][0] if want_nn else None for lv in out]),
+           ptr_table([lv["nn"][1] if want_nn else None for lv in out]), ptr(tie_out), config.fps_mode(fps_arith_mode),
+           config.bq_mode(bq_arith_mode))
     tag_fps_output(out[-1]["new_xyz"], tie_out, fps_arith_mode)  # a further level may nest on the last one
     return out
 
@@ -430,26 +395,22 @@ _POOL_MODES = {"max": 0, "avg": 1, "weighted_avg": 2, "max_and_avg": 3}
 class _GroupPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gxyz, mode):
-        from .._lib import check, lib, ptr, stream_ptr
         b, m, k, c = x.shape
         x = x.contiguous()
         gxyz = gxyz.contiguous() if gxyz is not None else None
         out = torch.empty((b, m, 1, 2 * c if mode == 3 else c), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            check(lib.pn2_group_pool(b * m, k, c, mode, ptr(x), ptr(gxyz), ptr(out), stream_ptr()), "pn2_group_pool")
+        launch("pn2_group_pool", x, b * m, k, c, mode, ptr(x), ptr(gxyz), ptr(out))
         ctx.save_for_backward(x, gxyz if gxyz is not None else x.new_empty(0))
         ctx.mode = mode
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        from .._lib import check, lib, ptr, stream_ptr
         x, gxyz = ctx.saved_tensors
         b, m, k, c = x.shape
         dx = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            check(lib.pn2_group_pool_grad(b * m, k, c, ctx.mode, ptr(x), ptr(gxyz if gxyz.numel() else None),
-                                          ptr(dout.contiguous()), ptr(dx), stream_ptr()), "pn2_group_pool_grad")
+        launch("pn2_group_pool_grad", x, b * m, k, c, ctx.mode, ptr(x), ptr(gxyz if gxyz.numel() else None), ptr(dout.contiguous()),
+               ptr(dx))
         return dx, None, None
 
 
@@ -606,9 +567,7 @@ def _fp_interp_concat(dist, idx, points1, points2, pad_to=1):
     out = torch.empty((b, n, cw), dtype=torch.float32, device=dist.device)
     p1 = None if points1 is None else points1.contiguous()
     p2 = points2.contiguous()
-    with torch.cuda.device(dist.device):
-        check(lib.pn2_fp_interp_concat(b, n, m, c1, c2, ptr(dist), ptr(idx), ptr(p1), ptr(p2), ptr(out), cw,
-                                       stream_ptr()), "pn2_fp_interp_concat")
+    launch("pn2_fp_interp_concat", dist, b, n, m, c1, c2, ptr(dist), ptr(idx), ptr(p1), ptr(p2), ptr(out), cw)
     return out
 
 

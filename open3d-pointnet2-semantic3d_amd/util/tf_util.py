@@ -22,8 +22,7 @@ import weakref
 import torch
 import torch.nn.functional as F
 
-from .._lib import PN2_EUNSUP as PN2_EUNSUP_CODE
-from .._lib import check, lib, ptr, require_cuda, rows_in_place, stream_ptr
+from .._lib import int_array, launch, layer_arrays, lib, nbytes, ptr, ptr_table, require_cuda, rows_in_place, u64_array
 
 BN_EPSILON = 1e-3  # tf.contrib.layers.batch_norm default (tf_util.py:571-581)
 
@@ -250,34 +249,20 @@ def hip_linear(x2d, w, b, relu=True, pool=0):
     x2d = x2d.contiguous()
     orows = rows // pool if pool and pool > 1 else rows
     y = torch.empty((orows, cout), dtype=torch.float32, device=x2d.device)
-    with torch.cuda.device(x2d.device):
-        check(lib.pn2_linear(rows, cin, cout, ptr(x2d), ptr(w), ptr(b), int(bool(relu)), int(pool or 0), ptr(y),
-                             stream_ptr()), "pn2_linear")
+    launch("pn2_linear", x2d, rows, cin, cout, ptr(x2d), ptr(w), ptr(b), int(bool(relu)), int(pool or 0), ptr(y))
     return y
 
 
 def hip_mlp_chain(x2d, ws, bs, pool=0):
     """relu(relu(x @ W0 + b0) @ W1 + b1) with LDS-resident weights (pn2_mlp_chain).  Returns None
     when the library reports the configuration as unsupported (caller falls back to hip_linear)."""
-    import ctypes
-    from .._lib import PN2_EUNSUP
     require_cuda(x2d)
     rows, cin = x2d.shape
     x2d = x2d.contiguous()
-    L = len(ws)
-    widths = (ctypes.c_int * L)(*[w.shape[1] for w in ws])
-    wptrs = (ctypes.c_void_p * L)(*[w.data_ptr() for w in ws])
-    bptrs = (ctypes.c_void_p * L)(*[b.data_ptr() for b in bs])
+    L, widths, wptrs, bptrs = layer_arrays(ws, bs)
     orows = rows // pool if pool else rows
     y = torch.empty((orows, ws[-1].shape[1]), dtype=torch.float32, device=x2d.device)
-    with torch.cuda.device(x2d.device):
-        rc = lib.pn2_mlp_chain(rows, cin, ptr(x2d), L, ctypes.cast(widths, ctypes.c_void_p),
-                               ctypes.cast(wptrs, ctypes.c_void_p), ctypes.cast(bptrs, ctypes.c_void_p), int(pool),
-                               ptr(y), stream_ptr())
-    if rc == PN2_EUNSUP:
-        return None
-    check(rc, "pn2_mlp_chain")
-    return y
+    return y if launch("pn2_mlp_chain", x2d, rows, cin, ptr(x2d), L, widths, wptrs, bptrs, int(pool), ptr(y), may_refuse=True) else None
 
 
 def multi_copy_(dsts, srcs, fills=()):
@@ -285,13 +270,12 @@ def multi_copy_(dsts, srcs, fills=()):
     torch._foreach_copy_ issues one memcpy per tensor when the dtypes are mixed.  fills = [(one-element float32 / int64 tensor,
     python value), ...] (<= 4): scalars stored by the same launch, their values travelling in the launch arguments
     (pn2_multi_copy_fill) -- a training step's lr_t and dropout step ride with its input copy."""
-    import ctypes
     import struct
     n = len(dsts)
     if n != len(srcs):
         raise ValueError("multi_copy_: list lengths differ")
     for d, s in zip(dsts, srcs):
-        if d.numel() * d.element_size() != s.numel() * s.element_size() or not d.is_contiguous() or not s.is_contiguous():
+        if nbytes(d) != nbytes(s) or not d.is_contiguous() or not s.is_contiguous():
             raise ValueError("multi_copy_: contiguous tensors of equal byte size expected")
     from ..tf_ops.tf_sampling import drop_fps_tag
     for d in dsts:
@@ -302,68 +286,44 @@ def multi_copy_(dsts, srcs, fills=()):
     for i0 in range(0, n, 48):
         dd, ss = dsts[i0:i0 + 48], srcs[i0:i0 + 48]
         k = len(dd)
-        sp = (ctypes.c_void_p * k)(*[t.data_ptr() for t in ss])
-        dp = (ctypes.c_void_p * k)(*[t.data_ptr() for t in dd])
-        nb = (ctypes.c_ulonglong * k)(*[t.numel() * t.element_size() for t in dd])
-        with torch.cuda.device(dd[0].device):
-            if fills and i0 == 0:
-                nf = len(fills)
-                vals, sizes = [], []
-                for t, v in fills:
-                    if t.numel() != 1 or t.dtype not in (torch.float32, torch.int64):
-                        raise ValueError("multi_copy_: a fill target is one float32 or int64 element")
-                    if t.dtype == torch.float32:
-                        vals.append(struct.unpack("<I", struct.pack("<f", float(v)))[0])
-                        sizes.append(4)
-                    else:
-                        vals.append(int(v) & 0xFFFFFFFFFFFFFFFF)
-                        sizes.append(8)
-                fp = (ctypes.c_void_p * nf)(*[t.data_ptr() for t, _ in fills])
-                fv = (ctypes.c_ulonglong * nf)(*vals)
-                fb = (ctypes.c_int * nf)(*sizes)
-                check(lib.pn2_multi_copy_fill(k, ctypes.cast(sp, ctypes.c_void_p), ctypes.cast(dp, ctypes.c_void_p),
-                                              ctypes.cast(nb, ctypes.c_void_p), nf, ctypes.cast(fp, ctypes.c_void_p),
-                                              ctypes.cast(fv, ctypes.c_void_p), ctypes.cast(fb, ctypes.c_void_p), stream_ptr()),
-                      "pn2_multi_copy_fill")
-            else:
-                check(lib.pn2_multi_copy(k, ctypes.cast(sp, ctypes.c_void_p), ctypes.cast(dp, ctypes.c_void_p),
-                                         ctypes.cast(nb, ctypes.c_void_p), stream_ptr()), "pn2_multi_copy")
-
-
-def _layer_arrays(ws, bs):
-    import ctypes
-    L = len(ws)
-    widths = (ctypes.c_int * L)(*[w.shape[1] for w in ws])
-    wptrs = (ctypes.c_void_p * L)(*[w.data_ptr() for w in ws])
-    bptrs = (ctypes.c_void_p * L)(*[b.data_ptr() for b in bs])
-    return L, ctypes.cast(widths, ctypes.c_void_p), ctypes.cast(wptrs, ctypes.c_void_p), ctypes.cast(bptrs, ctypes.c_void_p), (widths, wptrs, bptrs)
+        sp, dp = ptr_table(ss), ptr_table(dd)
+        nb = u64_array([nbytes(t) for t in dd])
+        if fills and i0 == 0:
+            vals, sizes = [], []
+            for t, v in fills:
+                if t.numel() != 1 or t.dtype not in (torch.float32, torch.int64):
+                    raise ValueError("multi_copy_: a fill target is one float32 or int64 element")
+                if t.dtype == torch.float32:
+                    vals.append(struct.unpack("<I", struct.pack("<f", float(v)))[0])  # the float's bits, widened
+                    sizes.append(4)
+                else:
+                    vals.append(int(v) & 0xFFFFFFFFFFFFFFFF)
+                    sizes.append(8)
+            launch("pn2_multi_copy_fill", dd[0], k, sp, dp, nb, len(fills), ptr_table([t for t, _ in fills]), u64_array(vals),
+                   int_array(sizes))
+        else:
+            launch("pn2_multi_copy", dd[0], k, sp, dp, nb)
 
 
 def hip_mlp_wide(x2d, ws, bs, relu_last=True, pool=0):
     """up to three dense layers of width 128 / 256 / 512 in ONE launch (pn2_mlp_wide: a workgroup carries a 32-row tile
     through all layers); pool = 32 adds the max over each group of 32 rows.  None when the library reports the
     configuration as unsupported (caller falls back to hip_linear per layer)."""
-    from .._lib import PN2_EUNSUP
     require_cuda(x2d)
     x2d = x2d.contiguous()
     rows, cin = x2d.shape
     if ws[0].shape[0] < -(-cin // 8) * 8:  # the kernel reads W0 in groups of 8 rows
         ws = [F.pad(ws[0], (0, 0, 0, -(-cin // 8) * 8 - ws[0].shape[0])).contiguous()] + list(ws[1:])
-    L, widths, wptrs, bptrs, keep = _layer_arrays(ws, bs)
+    L, widths, wptrs, bptrs = layer_arrays(ws, bs)
     y = torch.empty((rows // pool if pool else rows, ws[-1].shape[1]), dtype=torch.float32, device=x2d.device)
-    with torch.cuda.device(x2d.device):
-        rc = lib.pn2_mlp_wide(rows, cin, cin, ptr(x2d), L, widths, wptrs, bptrs, int(bool(relu_last)), int(pool), ptr(y),
-                              stream_ptr())
-    if rc == PN2_EUNSUP:
-        return None
-    check(rc, "pn2_mlp_wide")
-    return y
+    ok = launch("pn2_mlp_wide", x2d, rows, cin, cin, ptr(x2d), L, widths, wptrs, bptrs, int(bool(relu_last)), int(pool), ptr(y),
+                may_refuse=True)
+    return y if ok else None
 
 
 def hip_fp_mlp_wide(dist, idx, points1, points2, ws, bs):
     """[three_interpolate(points2) | points1] -> up to three wide dense layers in ONE launch (pn2_fp_mlp_wide);
     -> (b*n, w_last) or None when the library reports the configuration as unsupported."""
-    from .._lib import PN2_EUNSUP
     require_cuda(dist, idx, points1, points2)
     b, n, _ = dist.shape
     m, c2 = points2.shape[1], points2.shape[2]
@@ -371,16 +331,12 @@ def hip_fp_mlp_wide(dist, idx, points1, points2, ws, bs):
     need = -(-(c1 + c2) // 8) * 8
     if ws[0].shape[0] < need:
         ws = [F.pad(ws[0], (0, 0, 0, need - ws[0].shape[0])).contiguous()] + list(ws[1:])
-    L, widths, wptrs, bptrs, keep = _layer_arrays(ws, bs)
+    L, widths, wptrs, bptrs = layer_arrays(ws, bs)
     y = torch.empty((b * n, ws[-1].shape[1]), dtype=torch.float32, device=dist.device)
     p1 = None if points1 is None else points1.contiguous()
-    with torch.cuda.device(dist.device):
-        rc = lib.pn2_fp_mlp_wide(b, n, m, c1, c2, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(p1), ptr(points2.contiguous()),
-                                 L, widths, wptrs, bptrs, ptr(y), stream_ptr())
-    if rc == PN2_EUNSUP:
-        return None
-    check(rc, "pn2_fp_mlp_wide")
-    return y
+    ok = launch("pn2_fp_mlp_wide", dist, b, n, m, c1, c2, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(p1),
+                ptr(points2.contiguous()), L, widths, wptrs, bptrs, ptr(y), may_refuse=True)
+    return y if ok else None
 
 
 def sa_wide_first_layer(w0):
@@ -395,27 +351,21 @@ def hip_sa_mlp_wide(xyz, new_xyz, points, idx, ws, bs, pool=True):
     """SA front end (gather, centre, concat) + up to three wide dense layers + max over the 32 neighbours in ONE launch
     (pn2_sa_mlp_wide).  ws[0] in the kernel's row order (sa_wide_first_layer / folded_dense(rotate_rows, pad_in)).
     -> (b, m, w_last) (pool) or (b, m, 32, w_last); None when unsupported."""
-    from .._lib import PN2_EUNSUP
     require_cuda(xyz, new_xyz, points, idx)
     b, n, _ = xyz.shape
     m, ns = idx.shape[1], idx.shape[2]
     c = points.shape[2]
-    L, widths, wptrs, bptrs, keep = _layer_arrays(ws, bs)
+    L, widths, wptrs, bptrs = layer_arrays(ws, bs)
     wl = ws[-1].shape[1]
     y = torch.empty((b, m, wl) if pool else (b, m, ns, wl), dtype=torch.float32, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        rc = lib.pn2_sa_mlp_wide(b, n, m, ns, c, ptr(xyz.contiguous()), ptr(new_xyz.contiguous()), ptr(points.contiguous()),
-                                 ptr(idx.contiguous()), L, widths, wptrs, bptrs, int(bool(pool)), ptr(y), stream_ptr())
-    if rc == PN2_EUNSUP:
-        return None
-    check(rc, "pn2_sa_mlp_wide")
-    return y
+    ok = launch("pn2_sa_mlp_wide", xyz, b, n, m, ns, c, ptr(xyz.contiguous()), ptr(new_xyz.contiguous()), ptr(points.contiguous()),
+                ptr(idx.contiguous()), L, widths, wptrs, bptrs, int(bool(pool)), ptr(y), may_refuse=True)
+    return y if ok else None
 
 
 def hip_fp_mlp_wide_pre(dist, idx, points1, points2, ws, bs):
     """pn2_fp_mlp_wide with the first layer hoisted by linearity (see hip_fp_mlp_fused_pre): z = points2 @ W0[:c2] on the
     known points; the kernel's layer-0 tile holds only the skip-link channels.  -> (b*n, w_last) or None when unsupported."""
-    from .._lib import PN2_EUNSUP
     require_cuda(dist, idx, points1, points2)
     if points1 is None:
         return None
@@ -424,63 +374,44 @@ def hip_fp_mlp_wide_pre(dist, idx, points1, points2, ws, bs):
     c1 = points1.shape[2]
     w0a, w0b = split_first_layer(ws[0], c2, c1, "fp_wide_pre", pad_b_rows=8)
     z = hoist_gemm(points2.reshape(b * m, c2), w0a)
-    L, widths, wptrs, bptrs, keep = _layer_arrays([w0b] + list(ws[1:]), bs)
+    L, widths, wptrs, bptrs = layer_arrays([w0b] + list(ws[1:]), bs)
     y = torch.empty((b * n, ws[-1].shape[1]), dtype=torch.float32, device=dist.device)
-    with torch.cuda.device(dist.device):
-        rc = lib.pn2_fp_mlp_wide_pre(b, n, m, c1, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(points1.contiguous()), ptr(z),
-                                     L, widths, wptrs, bptrs, ptr(y), stream_ptr())
-    if rc == PN2_EUNSUP:
-        return None
-    check(rc, "pn2_fp_mlp_wide_pre")
-    return y
+    ok = launch("pn2_fp_mlp_wide_pre", dist, b, n, m, c1, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(points1.contiguous()),
+                ptr(z), L, widths, wptrs, bptrs, ptr(y), may_refuse=True)
+    return y if ok else None
 
 
 def hip_sa_mlp_wide_pre(xyz, new_xyz, points, idx, ws, bs, pool=True):
     """pn2_sa_mlp_wide with the feature part of the first layer hoisted: zf = points @ W0[feature rows] on the source points.
     ws[0] in the wide kernel's row order [features (c) | xyz (3) | zero pad].  -> (b, m, w_last) or None when unsupported."""
-    from .._lib import PN2_EUNSUP
     require_cuda(xyz, new_xyz, points, idx)
     b, n, _ = xyz.shape
     m, ns = idx.shape[1], idx.shape[2]
     c = points.shape[2]
     w0f, w0x = split_first_layer(ws[0], c, 3, "sa_wide_pre", pad_b_rows=8)
     zf = hoist_gemm(points.reshape(b * n, c), w0f)
-    L, widths, wptrs, bptrs, keep = _layer_arrays([w0x] + list(ws[1:]), bs)
+    L, widths, wptrs, bptrs = layer_arrays([w0x] + list(ws[1:]), bs)
     wl = ws[-1].shape[1]
     y = torch.empty((b, m, wl) if pool else (b, m, ns, wl), dtype=torch.float32, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        rc = lib.pn2_sa_mlp_wide_pre(b, n, m, ns, ptr(xyz.contiguous()), ptr(new_xyz.contiguous()), ptr(zf), ptr(idx.contiguous()),
-                                     L, widths, wptrs, bptrs, int(bool(pool)), ptr(y), stream_ptr())
-    if rc == PN2_EUNSUP:
-        return None
-    check(rc, "pn2_sa_mlp_wide_pre")
-    return y
+    ok = launch("pn2_sa_mlp_wide_pre", xyz, b, n, m, ns, ptr(xyz.contiguous()), ptr(new_xyz.contiguous()), ptr(zf),
+                ptr(idx.contiguous()), L, widths, wptrs, bptrs, int(bool(pool)), ptr(y), may_refuse=True)
+    return y if ok else None
 
 
 def hip_fp_mlp_fused(dist, idx, points1, points2, ws, bs):
     """[three_interpolate(points2) | points1] -> up to two dense layers in ONE kernel (pn2_fp_mlp_fused);
     returns (b*n, w_last) or None when the library reports the configuration as unsupported."""
-    import ctypes
-    from .._lib import PN2_EUNSUP
     require_cuda(dist, idx, points1, points2)
     b, n, _ = dist.shape
     m, c2 = points2.shape[1], points2.shape[2]
     c1 = 0 if points1 is None else points1.shape[2]
     p1 = None if points1 is None else points1.contiguous()
     p2 = points2.contiguous()
-    L = len(ws)
-    widths = (ctypes.c_int * L)(*[w.shape[1] for w in ws])
-    wptrs = (ctypes.c_void_p * L)(*[w.data_ptr() for w in ws])
-    bptrs = (ctypes.c_void_p * L)(*[bb.data_ptr() for bb in bs])
+    L, widths, wptrs, bptrs = layer_arrays(ws, bs)
     y = torch.empty((b * n, ws[-1].shape[1]), dtype=torch.float32, device=dist.device)
-    with torch.cuda.device(dist.device):
-        rc = lib.pn2_fp_mlp_fused(b, n, m, c1, c2, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(p1), ptr(p2), L,
-                                  ctypes.cast(widths, ctypes.c_void_p), ctypes.cast(wptrs, ctypes.c_void_p),
-                                  ctypes.cast(bptrs, ctypes.c_void_p), ptr(y), stream_ptr())
-    if rc == PN2_EUNSUP:
-        return None
-    check(rc, "pn2_fp_mlp_fused")
-    return y
+    ok = launch("pn2_fp_mlp_fused", dist, b, n, m, c1, c2, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(p1), ptr(p2), L, widths,
+                wptrs, bptrs, ptr(y), may_refuse=True)
+    return y if ok else None
 
 
 _zero_bias = {}
@@ -526,8 +457,6 @@ def hip_fp_mlp_fused_pre(dist, idx, points1, points2, ws, bs, schedule=None):
     schedule (tests, A/B): 0 = the lockstep kernel, 1 = the software-pipelined one (pn2_fp_mlp_fused_pre_schedule); None = the
     library's choice.  Same bits either way.
     Returns (b*n, w_last), or None when the library reports the configuration as unsupported."""
-    import ctypes
-    from .._lib import PN2_EUNSUP
     require_cuda(dist, idx, points1, points2)
     b, n, _ = dist.shape
     m, c2 = points2.shape[1], points2.shape[2]
@@ -541,25 +470,16 @@ def hip_fp_mlp_fused_pre(dist, idx, points1, points2, ws, bs, schedule=None):
     p1, ld1 = (None, 0) if points1 is None else rows_in_place(points1)
     if schedule is not None and p1 is not None:
         p1, ld1 = p1.contiguous(), c1
-    widths = (ctypes.c_int * L)(*[w.shape[1] for w in ws])
-    wlist = [w1b] + list(ws[1:])
-    wptrs = (ctypes.c_void_p * L)(*[(w.data_ptr() if w is not None else None) for w in wlist])
-    bptrs = (ctypes.c_void_p * L)(*[bb.data_ptr() for bb in bs])
+    widths, wptrs, bptrs = int_array([w.shape[1] for w in ws]), ptr_table([w1b] + list(ws[1:])), ptr_table(bs)  # w1b: None when c1 == 0
     y = torch.empty((b * n, ws[-1].shape[1]), dtype=torch.float32, device=dist.device)
-    with torch.cuda.device(dist.device):
-        common = (b, n, m, c1, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(p1), ptr(z), L,
-                  ctypes.cast(widths, ctypes.c_void_p), ctypes.cast(wptrs, ctypes.c_void_p),
-                  ctypes.cast(bptrs, ctypes.c_void_p), ptr(y))
-        if schedule is None and p1 is not None and ld1 != c1:
-            rc = lib.pn2_fp_mlp_fused_pre_ld(*common[:7], ld1, *common[7:], stream_ptr())
-        elif schedule is None:
-            rc = lib.pn2_fp_mlp_fused_pre(*common, stream_ptr())
-        else:
-            rc = lib.pn2_fp_mlp_fused_pre_schedule(*common, int(schedule), stream_ptr())
-    if rc == PN2_EUNSUP:
-        return None
-    check(rc, "pn2_fp_mlp_fused_pre")
-    return y
+    common = (b, n, m, c1, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(p1), ptr(z), L, widths, wptrs, bptrs, ptr(y))
+    if schedule is None and p1 is not None and ld1 != c1:
+        ok = launch("pn2_fp_mlp_fused_pre_ld", dist, *common[:7], ld1, *common[7:], may_refuse=True)
+    elif schedule is None:
+        ok = launch("pn2_fp_mlp_fused_pre", dist, *common, may_refuse=True)
+    else:
+        ok = launch("pn2_fp_mlp_fused_pre_schedule", dist, *common, int(schedule), may_refuse=True)
+    return y if ok else None
 
 
 def hip_linear_narrow(x2d, w, b=None):
@@ -572,13 +492,9 @@ def hip_linear_narrow(x2d, w, b=None):
         return None
     x2d = x2d.contiguous()
     y = torch.empty((rows, cout), dtype=torch.float32, device=x2d.device)
-    with torch.cuda.device(x2d.device):
-        rc = lib.pn2_linear_narrow(rows, cin, cout, ptr(x2d), ptr(w.contiguous()), ptr(None if b is None else b.contiguous()), ptr(y),
-                                   stream_ptr())
-    if rc == PN2_EUNSUP_CODE:
-        return None
-    check(rc, "pn2_linear_narrow")
-    return y
+    ok = launch("pn2_linear_narrow", x2d, rows, cin, cout, ptr(x2d), ptr(w.contiguous()), ptr(None if b is None else b.contiguous()),
+                ptr(y), may_refuse=True)
+    return y if ok else None
 
 
 def hip_matmul(x2d, w):
@@ -603,9 +519,7 @@ def hip_matmul_bn_stats(x2d, w, ws):
     rows, cin = x2d.shape
     cout = w.shape[1]
     y = torch.empty((rows, cout), dtype=torch.float32, device=x2d.device)
-    with torch.cuda.device(x2d.device):
-        check(lib.pn2_linear_bn_stats(rows, cin, cout, ptr(x2d.contiguous()), ptr(w.contiguous()), ptr(y), ptr(ws),
-                                      ws.numel() * ws.element_size(), stream_ptr()), "pn2_linear_bn_stats")
+    launch("pn2_linear_bn_stats", x2d, rows, cin, cout, ptr(x2d.contiguous()), ptr(w.contiguous()), ptr(y), ptr(ws), nbytes(ws))
     return y
 
 
@@ -615,10 +529,8 @@ def hip_matmul_bn_stats_xf(x_raw, w, ws, sc, sh, relu):
     rows, cin = x_raw.shape
     cout = w.shape[1]
     y = torch.empty((rows, cout), dtype=torch.float32, device=x_raw.device)
-    with torch.cuda.device(x_raw.device):
-        check(lib.pn2_linear_bn_stats_xf(rows, cin, cout, ptr(x_raw.contiguous()), ptr(w.contiguous()), ptr(y), ptr(ws),
-                                         ws.numel() * ws.element_size(), ptr(sc), ptr(sh), int(relu), stream_ptr()),
-              "pn2_linear_bn_stats_xf")
+    launch("pn2_linear_bn_stats_xf", x_raw, rows, cin, cout, ptr(x_raw.contiguous()), ptr(w.contiguous()), ptr(y), ptr(ws), nbytes(ws),
+           ptr(sc), ptr(sh), int(relu))
     return y
 
 
@@ -629,13 +541,12 @@ def hip_linear_dgrad(dy, w):
     cin = w.shape[0]
     dy = dy.contiguous()
     dx = torch.empty((rows, cin), dtype=torch.float32, device=dy.device)
-    with torch.cuda.device(dy.device):
-        check(lib.pn2_linear_dgrad(rows, cin, cout, ptr(dy), ptr(w.contiguous()), ptr(dx), stream_ptr()), "pn2_linear_dgrad")
+    launch("pn2_linear_dgrad", dy, rows, cin, cout, ptr(dy), ptr(w.contiguous()), ptr(dx))
     return dx
 
 
 def _bn_scratch(c, device, fn, fn_ws0):
-    """batch-norm accumulators: a slice of the step's zero arena (+ the entry point that trusts it) when there is one"""
+    """batch-norm accumulators: a slice of the step's zero arena (+ the NAME of the entry point that trusts it) when there is one"""
     nbytes = lib.pn2_bn_workspace_bytes(c)
     arena = get_default_store().zero_arena
     v = arena.take(nbytes) if arena is not None else None
@@ -652,6 +563,12 @@ USE_GEMM_BN_STATS = True  # batch statistics from the forward GEMM's epilogue (s
 USE_BN_FINISH_IN_PRODUCER = True
 
 
+def _bn_consts_out(c, device):
+    """uninitialised (save_mean, save_invstd, scale, shift) for a launch that publishes a deferred batch norm's constants"""
+    save_mean = torch.empty(c, dtype=torch.float32, device=device)
+    return save_mean, torch.empty_like(save_mean), torch.empty_like(save_mean), torch.empty_like(save_mean)
+
+
 def hip_matmul_bn_stats_fin(x2d, w, ws, xf, finish, gamma=None, beta=None, b=None, decay=0.0, running_mean=None, running_var=None):
     """hip_matmul_bn_stats (xf None) / hip_matmul_bn_stats_xf (xf = (scale, shift, relu)) whose last workgroup also folds the
     statistics (finish 1) or folds them and publishes the deferred batch norm's constants (finish 2, pn2_linear_bn_stats_fin).
@@ -660,17 +577,12 @@ def hip_matmul_bn_stats_fin(x2d, w, ws, xf, finish, gamma=None, beta=None, b=Non
     rows, cin = x2d.shape
     cout = w.shape[1]
     y = torch.empty((rows, cout), dtype=torch.float32, device=x2d.device)
-    consts = None
-    if finish == 2:
-        save_mean = torch.empty(cout, dtype=torch.float32, device=x2d.device)
-        consts = (save_mean, torch.empty_like(save_mean), torch.empty_like(save_mean), torch.empty_like(save_mean))
+    consts = _bn_consts_out(cout, x2d.device) if finish == 2 else None
     sc, sh, xrelu = xf if xf is not None else (None, None, 0)
     cs = consts if consts is not None else (None, None, None, None)
-    with torch.cuda.device(x2d.device):
-        check(lib.pn2_linear_bn_stats_fin(rows, cin, cout, ptr(x2d.contiguous()), ptr(w.contiguous()), ptr(y), ptr(ws),
-                                          ws.numel() * ws.element_size(), ptr(sc), ptr(sh), int(xrelu), int(finish), ptr(gamma),
-                                          ptr(beta), ptr(b), BN_EPSILON, float(decay), ptr(running_mean), ptr(running_var),
-                                          ptr(cs[0]), ptr(cs[1]), ptr(cs[2]), ptr(cs[3]), stream_ptr()), "pn2_linear_bn_stats_fin")
+    launch("pn2_linear_bn_stats_fin", x2d, rows, cin, cout, ptr(x2d.contiguous()), ptr(w.contiguous()), ptr(y), ptr(ws), nbytes(ws),
+           ptr(sc), ptr(sh), int(xrelu), int(finish), ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, float(decay), ptr(running_mean),
+           ptr(running_var), ptr(cs[0]), ptr(cs[1]), ptr(cs[2]), ptr(cs[3]))
     return y, consts
 
 
@@ -682,35 +594,33 @@ def _bn_zeroed_scratch(c, device):
     return v if v is not None else torch.zeros(nbytes // 8, dtype=torch.float64, device=device)
 
 
+def _wgrad_out(w, fresh=True):
+    """the ZERO-STARTED tensor a kernel accumulates dW into: the parameter's slice of the trainer's (zero-filled) flat gradient, else
+    a slice of the step's zero arena, else a fresh zero tensor (fresh False: None)"""
+    st = get_default_store()
+    dw = st.grad_view(w)
+    if dw is None:
+        v = st.zero_arena.take(w.numel() * 4) if st.zero_arena is not None else None
+        if v is not None:
+            dw = v[:w.numel() * 4].view(torch.float32).view_as(w)
+        elif fresh:
+            dw = torch.zeros_like(w)
+    return dw
+
+
 def _hip_wgrad(x2d, dy, w, xf=None):
     """dW = x2d^T @ dy on pn2_linear_wgrad; the tile is added to with atomics, so it starts from the zero arena when the
     step has one (no memset of its own).  xf = (scale, shift, relu): x2d is the producer's un-normalised output, the
     kernel applies its batch norm while loading (pn2_linear_wgrad_accumulate_xf)."""
-    gv = get_default_store().grad_view(w)  # the parameter's slice of the trainer's (zero-filled) flat gradient
-    if gv is not None:
-        with torch.cuda.device(w.device):
-            if xf is not None:
-                check(lib.pn2_linear_wgrad_accumulate_xf(x2d.shape[0], w.shape[0], w.shape[1], ptr(x2d), ptr(dy), ptr(gv), ptr(xf[0]),
-                                                         ptr(xf[1]), int(xf[2]), stream_ptr()), "pn2_linear_wgrad_accumulate_xf")
-            else:
-                check(lib.pn2_linear_wgrad_accumulate(x2d.shape[0], w.shape[0], w.shape[1], ptr(x2d), ptr(dy), ptr(gv), stream_ptr()),
-                      "pn2_linear_wgrad_accumulate")
-        return gv
-    arena = get_default_store().zero_arena
-    v = arena.take(w.numel() * 4) if arena is not None else None
-    with torch.cuda.device(w.device):
-        if xf is not None:
-            dw = v[:w.numel() * 4].view(torch.float32).view_as(w) if v is not None else torch.zeros_like(w)
-            check(lib.pn2_linear_wgrad_accumulate_xf(x2d.shape[0], w.shape[0], w.shape[1], ptr(x2d), ptr(dy), ptr(dw), ptr(xf[0]),
-                                                     ptr(xf[1]), int(xf[2]), stream_ptr()), "pn2_linear_wgrad_accumulate_xf")
-        elif v is not None:
-            dw = v[:w.numel() * 4].view(torch.float32).view_as(w)
-            check(lib.pn2_linear_wgrad_accumulate(x2d.shape[0], w.shape[0], w.shape[1], ptr(x2d), ptr(dy), ptr(dw), stream_ptr()),
-                  "pn2_linear_wgrad_accumulate")
-        else:
-            dw = torch.empty_like(w)
-            check(lib.pn2_linear_wgrad(x2d.shape[0], w.shape[0], w.shape[1], ptr(x2d), ptr(dy), ptr(dw), stream_ptr()),
-                  "pn2_linear_wgrad")
+    dw = _wgrad_out(w, fresh=xf is not None)
+    dims = (x2d.shape[0], w.shape[0], w.shape[1], ptr(x2d), ptr(dy))
+    if xf is not None:
+        launch("pn2_linear_wgrad_accumulate_xf", w, *dims, ptr(dw), ptr(xf[0]), ptr(xf[1]), int(xf[2]))
+    elif dw is not None:
+        launch("pn2_linear_wgrad_accumulate", w, *dims, ptr(dw))
+    else:  # nothing zero-filled at hand: the entry point that clears the tile itself
+        dw = torch.empty_like(w)
+        launch("pn2_linear_wgrad", w, *dims, ptr(dw))
     return dw
 
 
@@ -782,8 +692,7 @@ class _TrainDenseRelu(torch.autograd.Function):
         x2d, w, z = ctx.saved_tensors
         dz = dz.contiguous()
         dy = torch.empty_like(dz)
-        with torch.cuda.device(dz.device):
-            check(lib.pn2_relu_grad(dz.numel(), ptr(z), ptr(dz), ptr(dy), stream_ptr()), "pn2_relu_grad")
+        launch("pn2_relu_grad", dz, dz.numel(), ptr(z), ptr(dz), ptr(dy))
         dx = hip_linear_dgrad(dy, w) if ctx.needs_input_grad[0] else None
         dw = _hip_wgrad(x2d, dy, w) if ctx.needs_input_grad[1] else None
         db = None
@@ -865,11 +774,8 @@ def hip_linear_dgrad_linked(dy, w, link):
     rows, cin = dy.shape[0], w.shape[0]
     pws = _bn_zeroed_scratch(cin, dy.device)
     dx = torch.empty((rows, cin), dtype=torch.float32, device=dy.device)
-    with torch.cuda.device(dy.device):
-        check(lib.pn2_linear_dgrad_bn_grad_stats(rows, cin, w.shape[1], ptr(dy), ptr(w.contiguous()), ptr(dx), ptr(link.y),
-                                                 ptr(link.gamma), ptr(link.beta), ptr(link.mean), ptr(link.invstd),
-                                                 int(link.relu), ptr(pws), pws.numel() * pws.element_size(), stream_ptr()),
-              "pn2_linear_dgrad_bn_grad_stats")
+    launch("pn2_linear_dgrad_bn_grad_stats", dy, rows, cin, w.shape[1], ptr(dy), ptr(w.contiguous()), ptr(dx), ptr(link.y),
+           ptr(link.gamma), ptr(link.beta), ptr(link.mean), ptr(link.invstd), int(link.relu), ptr(pws), nbytes(pws))
     link.ws, link.dz_ptr, link.dz_keep = pws, dx.data_ptr(), dx
     return dx
 
@@ -879,33 +785,28 @@ def _bn_train_forward(y, b, gamma, beta, running_mean, running_var, decay, relu,
     workspace pn2_linear_bn_stats has already left the column sums in.  -> z, ties, save_mean, save_invstd"""
     rows, c = y.shape
     if stats_ws is not None:
-        ws, fwd = stats_ws, lib.pn2_bn_relu_forward_stats
+        ws, fwd = stats_ws, "pn2_bn_relu_forward_stats"
     else:
-        ws, fwd = _bn_scratch(c, y.device, lib.pn2_bn_relu_forward, lib.pn2_bn_relu_forward_ws0)
+        ws, fwd = _bn_scratch(c, y.device, "pn2_bn_relu_forward", "pn2_bn_relu_forward_ws0")
     pooled = pool > 1
     z = torch.empty((rows // pool, c) if pooled else (rows, c), dtype=y.dtype, device=y.device)
     save_mean = torch.empty(c, dtype=torch.float32, device=y.device)
     save_invstd = torch.empty_like(save_mean)
     ties = None
-    with torch.cuda.device(y.device):
-        if pooled:
-            # ties = [tie counts | ysel]: ysel = the pre-normalisation value of the first row attaining each maximum, which lets the
-            # backward take its reduction from the pooled tensors (pn2_bn_grad_constants) instead of a pass over y
-            ties = torch.empty((2,) + tuple(z.shape), dtype=y.dtype, device=y.device)
-            mode = (3 if folded else 2) if stats_ws is not None else (1 if fwd is lib.pn2_bn_relu_forward_ws0 else 0)
-            check(lib.pn2_bn_relu_forward_pool(rows, c, ptr(y), ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, decay, int(relu), int(pool),
-                                               ptr(running_mean), ptr(running_var), ptr(ws), ws.numel() * ws.element_size(), mode,
-                                               ptr(save_mean), ptr(save_invstd), ptr(z), ptr(ties[0]), ptr(ties[1]), stream_ptr()),
-                  "pn2_bn_relu_forward_pool")
-        elif folded and stats_ws is not None:  # the GEMM's last workgroup has folded the sums: only the normalisation pass is left
-            check(lib.pn2_bn_relu_forward_mode(rows, c, ptr(y), ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, decay, int(relu),
-                                               ptr(running_mean), ptr(running_var), ptr(ws), ws.numel() * ws.element_size(), 3,
-                                               ptr(save_mean), ptr(save_invstd), ptr(z), stream_ptr()), "pn2_bn_relu_forward_mode")
-        else:
-            check(fwd(rows, c, ptr(y), ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, decay, int(relu),
-                      int(pool), ptr(running_mean), ptr(running_var), ptr(ws), ws.numel() * ws.element_size(),
-                      ptr(save_mean), ptr(save_invstd), ptr(z), None, stream_ptr()),
-                  "pn2_bn_relu_forward")
+    head = (rows, c, ptr(y), ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, decay, int(relu))
+    if pooled:
+        # ties = [tie counts | ysel]: ysel = the pre-normalisation value of the first row attaining each maximum, which lets the
+        # backward take its reduction from the pooled tensors (pn2_bn_grad_constants) instead of a pass over y
+        ties = torch.empty((2,) + tuple(z.shape), dtype=y.dtype, device=y.device)
+        mode = (3 if folded else 2) if stats_ws is not None else (1 if fwd == "pn2_bn_relu_forward_ws0" else 0)
+        launch("pn2_bn_relu_forward_pool", y, *head, int(pool), ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), mode,
+               ptr(save_mean), ptr(save_invstd), ptr(z), ptr(ties[0]), ptr(ties[1]))
+    elif folded and stats_ws is not None:  # the GEMM's last workgroup has folded the sums: only the normalisation pass is left
+        launch("pn2_bn_relu_forward_mode", y, *head, ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), 3, ptr(save_mean),
+               ptr(save_invstd), ptr(z))
+    else:
+        launch(fwd, y, *head, int(pool), ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), ptr(save_mean), ptr(save_invstd),
+               ptr(z), None)
     return z, ties, save_mean, save_invstd
 
 
@@ -913,14 +814,10 @@ def _bn_train_forward_deferred(y, b, gamma, beta, running_mean, running_var, dec
     """the statistics half of _bn_train_forward only (pn2_bn_relu_forward_deferred) -> save_mean, save_invstd, scale, shift"""
     rows, c = y.shape
     ws = stats_ws if stats_ws is not None else _bn_zeroed_scratch(c, y.device)
-    save_mean = torch.empty(c, dtype=torch.float32, device=y.device)
-    save_invstd, sc, sh = torch.empty_like(save_mean), torch.empty_like(save_mean), torch.empty_like(save_mean)
-    with torch.cuda.device(y.device):
-        check(lib.pn2_bn_relu_forward_deferred(rows, c, ptr(y), ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, decay,
-                                               int(stats_ws is not None), ptr(running_mean), ptr(running_var), ptr(ws),
-                                               ws.numel() * ws.element_size(), ptr(save_mean), ptr(save_invstd), ptr(sc), ptr(sh),
-                                               stream_ptr()), "pn2_bn_relu_forward_deferred")
-    return save_mean, save_invstd, sc, sh
+    consts = _bn_consts_out(c, y.device)
+    launch("pn2_bn_relu_forward_deferred", y, rows, c, ptr(y), ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, decay,
+           int(stats_ws is not None), ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), *map(ptr, consts))
+    return consts
 
 
 def _bn_register_producer(z, y, gamma, beta, save_mean, save_invstd, relu, pooled, sc=None, sh=None, gx=False):
@@ -945,6 +842,18 @@ def _param_grad_out(p):
     return gv if gv is not None else torch.empty_like(p)
 
 
+def _bn_link_spend(lk):
+    """a layer's backward runs once: refuse a deferred output that no following conv2d consumed, then drop what its producer
+    record (lk, may be None) kept alive"""
+    if lk is None:
+        return
+    if lk.sc is not None and not lk.consumed:
+        # the un-normalised output went somewhere else than into the next dense layer: whatever read it saw wrong values
+        raise RuntimeError("a deferred batch-norm output (conv2d(..., defer_bn=True)) was not consumed by a following conv2d")
+    lk.ws = lk.dz_keep = lk.dz_ptr = lk.y = lk.gamma = lk.beta = lk.mean = lk.invstd = lk.sc = lk.sh = None
+    lk.coef = lk.dgamma = lk.dbeta = None
+
+
 def _bn_train_backward(dz, y, gamma, beta, save_mean, save_invstd, relu, pool, zmax, ties, lk):
     """gradient of _bn_train_forward on pn2_bn_relu_backward -> dy (rows, c), dgamma, dbeta.  lk: this layer's producer
     record; when the consumer's data-gradient GEMM has already left the two reduction sums there (and dz is that GEMM's
@@ -955,27 +864,18 @@ def _bn_train_backward(dz, y, gamma, beta, save_mean, save_invstd, relu, pool, z
     dgamma, dbeta = _param_grad_out(gamma), _param_grad_out(beta)
     mode3 = False
     if lk is not None and lk.ws is not None and lk.dz_ptr == dz.data_ptr() and dz.shape == y.shape:
-        ws, bwd, mode3 = lk.ws, lib.pn2_bn_relu_backward_stats, bool(lk.folded)
+        ws, bwd, mode3 = lk.ws, "pn2_bn_relu_backward_stats", bool(lk.folded)
     else:
-        ws, bwd = _bn_scratch(c, y.device, lib.pn2_bn_relu_backward, lib.pn2_bn_relu_backward_ws0)
-    if lk is not None and lk.sc is not None and not lk.consumed:
-        # the un-normalised output went somewhere else than into the next dense layer: whatever read it saw wrong values
-        raise RuntimeError("a deferred batch-norm output (conv2d(..., defer_bn=True)) was not consumed by a following conv2d")
-    if lk is not None:  # this layer's backward runs once: drop what the record kept alive
-        lk.ws = lk.dz_keep = lk.dz_ptr = lk.y = lk.gamma = lk.beta = lk.mean = lk.invstd = lk.sc = lk.sh = None
-        lk.coef = lk.dgamma = lk.dbeta = None
+        ws, bwd = _bn_scratch(c, y.device, "pn2_bn_relu_backward", "pn2_bn_relu_backward_ws0")
+    _bn_link_spend(lk)
     if ties is not None and ties.dim() == zmax.dim() + 1:
         ties = ties[0]  # [tie counts | ysel] of _bn_train_forward
-    with torch.cuda.device(y.device):
-        if mode3:  # the consumer's data-gradient GEMM has left the sums AND folded them (pn2_linear_dgrad_fin)
-            check(lib.pn2_bn_relu_backward_mode(rows, c, ptr(dz), ptr(y), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd),
-                                                int(relu), int(pool), ptr(zmax), ptr(ties), ptr(ws), ws.numel() * ws.element_size(),
-                                                3, ptr(dy), ptr(dgamma), ptr(dbeta), stream_ptr()), "pn2_bn_relu_backward_mode")
-        else:
-            check(bwd(rows, c, ptr(dz), ptr(y), ptr(gamma), ptr(beta), ptr(save_mean),
-                      ptr(save_invstd), int(relu), int(pool), ptr(zmax), ptr(ties), ptr(ws),
-                      ws.numel() * ws.element_size(), ptr(dy), ptr(dgamma), ptr(dbeta), stream_ptr()),
-                  "pn2_bn_relu_backward")
+    head = (rows, c, ptr(dz), ptr(y), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), int(relu), int(pool), ptr(zmax),
+            ptr(ties), ptr(ws), nbytes(ws))
+    if mode3:  # the consumer's data-gradient GEMM has left the sums AND folded them (pn2_linear_dgrad_fin)
+        launch("pn2_bn_relu_backward_mode", y, *head, 3, ptr(dy), ptr(dgamma), ptr(dbeta))
+    else:
+        launch(bwd, y, *head, ptr(dy), ptr(dgamma), ptr(dbeta))
     return dy, dgamma, dbeta
 
 
@@ -1007,11 +907,7 @@ def _bn_grad_constants(dz, y, gamma, beta, save_mean, save_invstd, relu, pool, z
             ready = (lk.coef, lk.dgamma, lk.dbeta)
     else:
         ws, done = _bn_zeroed_scratch(c, y.device), 0
-    if lk is not None and lk.sc is not None and not lk.consumed:
-        raise RuntimeError("a deferred batch-norm output (conv2d(..., defer_bn=True)) was not consumed by a following conv2d")
-    if lk is not None:
-        lk.ws = lk.dz_keep = lk.dz_ptr = lk.y = lk.gamma = lk.beta = lk.mean = lk.invstd = lk.sc = lk.sh = None
-        lk.coef = lk.dgamma = lk.dbeta = None
+    _bn_link_spend(lk)
     if ready is not None:
         return ready
     coef = torch.empty((6, c), dtype=torch.float32, device=y.device)
@@ -1019,11 +915,35 @@ def _bn_grad_constants(dz, y, gamma, beta, save_mean, save_invstd, relu, pool, z
     ysel = None
     if ties is not None and ties.dim() == zmax.dim() + 1:
         ties, ysel = ties[0], (ties[1] if USE_POOLED_BN_REDUCE else None)
-    with torch.cuda.device(y.device):
-        check(lib.pn2_bn_grad_constants(rows, c, ptr(dz), ptr(y), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), int(relu),
-                                        int(pool), ptr(zmax), ptr(ties), ptr(ysel), done, ptr(ws), ws.numel() * ws.element_size(),
-                                        ptr(coef), ptr(dgamma), ptr(dbeta), stream_ptr()), "pn2_bn_grad_constants")
+    launch("pn2_bn_grad_constants", y, rows, c, ptr(dz), ptr(y), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), int(relu),
+           int(pool), ptr(zmax), ptr(ties), ptr(ysel), done, ptr(ws), nbytes(ws), ptr(coef), ptr(dgamma), ptr(dbeta))
     return coef, dgamma, dbeta
+
+
+def _below_args(link, rows, cin, dx, fin):
+    """What a data-gradient GEMM with output dx (rows, cin) is handed to serve the layer below (link: its producer record, or
+    None): -> below (8 arguments: that layer's batch norm + a zeroed workspace for its two gradient sums), fin_out (4 arguments,
+    fin only: what the GEMM's last workgroup does with the sums -- 1 fold them, 3 publish the gradient constants, dgamma and
+    dbeta (link.gx) --), notes: what _note_on_link writes on the record once the launch has been accepted."""
+    if link is None:
+        return (None, None, None, None, None, 0, None, 0), (0, None, None, None), {}
+    pws = _bn_zeroed_scratch(cin, dx.device)
+    below = (ptr(link.y), ptr(link.gamma), ptr(link.beta), ptr(link.mean), ptr(link.invstd), int(link.relu), ptr(pws), nbytes(pws))
+    notes = dict(ws=pws, dz_ptr=dx.data_ptr(), dz_keep=dx)
+    fin_out = (1, None, None, None)
+    if fin:
+        notes["folded"] = True
+        if link.gx and _gx_usable(rows, cin, 0, dx, link.y):
+            coef = torch.empty((6, cin), dtype=torch.float32, device=dx.device)
+            dgamma, dbeta = _param_grad_out(link.gamma), _param_grad_out(link.beta)
+            notes.update(coef=coef, dgamma=dgamma, dbeta=dbeta)
+            fin_out = (3, ptr(coef), ptr(dgamma), ptr(dbeta))
+    return below, fin_out, notes
+
+
+def _note_on_link(link, notes):
+    for k, v in notes.items():
+        setattr(link, k, v)
 
 
 def _hip_dgrad_fin(dy, gx, w, link):
@@ -1034,28 +954,14 @@ def _hip_dgrad_fin(dy, gx, w, link):
     ref = dy if dy is not None else gx[0]
     rows, cin = ref.shape[0], w.shape[0]
     dx = torch.empty((rows, cin), dtype=torch.float32, device=ref.device)
-    below, fin_out = (None, None, None, None, None, 0, None, 0), (0, None, None, None)
-    pws = None
-    if link is not None:
-        pws = _bn_zeroed_scratch(cin, ref.device)
-        below = (ptr(link.y), ptr(link.gamma), ptr(link.beta), ptr(link.mean), ptr(link.invstd), int(link.relu), ptr(pws),
-                 pws.numel() * pws.element_size())
-        if link.gx and _gx_usable(rows, cin, 0, dx, link.y):
-            link.coef = torch.empty((6, cin), dtype=torch.float32, device=ref.device)
-            link.dgamma, link.dbeta = _param_grad_out(link.gamma), _param_grad_out(link.beta)
-            fin_out = (3, ptr(link.coef), ptr(link.dgamma), ptr(link.dbeta))
-        else:
-            fin_out = (1, None, None, None)
+    below, fin_out, notes = _below_args(link, rows, cin, dx, fin=True)
     if gx is not None:
         y, dz, coef, relu, pool, zmax, ties = gx
         up = (None, ptr(y), ptr(dz), ptr(coef), int(relu), int(pool), ptr(zmax), ptr(ties))
     else:
         up = (ptr(dy), None, None, None, 0, 0, None, None)
-    with torch.cuda.device(ref.device):
-        check(lib.pn2_linear_dgrad_fin(rows, cin, w.shape[1], *up, ptr(w.contiguous()), ptr(dx), *below, *fin_out, stream_ptr()),
-              "pn2_linear_dgrad_fin")
-    if link is not None:
-        link.ws, link.dz_ptr, link.dz_keep, link.folded = pws, dx.data_ptr(), dx, True
+    launch("pn2_linear_dgrad_fin", ref, rows, cin, w.shape[1], *up, ptr(w.contiguous()), ptr(dx), *below, *fin_out)
+    _note_on_link(link, notes)
     return dx
 
 
@@ -1070,36 +976,14 @@ def _hip_bwd_fused(x2d, xf, y, dz, coef, relu, pool, zmax, ties, w, link):
             and x2d.is_contiguous() and x2d.shape[1] == cin):
         return None
     dx = torch.empty((rows, cin), dtype=torch.float32, device=y.device)
-    dw = get_default_store().grad_view(w)
-    if dw is None:
-        arena = get_default_store().zero_arena
-        v = arena.take(w.numel() * 4) if arena is not None else None
-        dw = v[:w.numel() * 4].view(torch.float32).view_as(w) if v is not None else torch.zeros_like(w)
-    below, fin_out, pws = (None, None, None, None, None, 0, None, 0), (0, None, None, None), None
-    gxb = False
-    if link is not None:
-        pws = _bn_zeroed_scratch(cin, y.device)
-        below = (ptr(link.y), ptr(link.gamma), ptr(link.beta), ptr(link.mean), ptr(link.invstd), int(link.relu), ptr(pws),
-                 pws.numel() * pws.element_size())
-        gxb = bool(link.gx and _gx_usable(rows, cin, 0, dx, link.y))
-        if gxb:
-            cb = torch.empty((6, cin), dtype=torch.float32, device=y.device)
-            dgb, dbb = _param_grad_out(link.gamma), _param_grad_out(link.beta)
-            fin_out = (3, ptr(cb), ptr(dgb), ptr(dbb))
-        else:
-            fin_out = (1, None, None, None)
+    dw = _wgrad_out(w)
+    below, fin_out, notes = _below_args(link, rows, cin, dx, fin=True)
     sc, sh, xrelu = xf if xf is not None else (None, None, 0)
-    with torch.cuda.device(y.device):
-        rc = lib.pn2_linear_bwd_fused(rows, cin, cout, ptr(x2d), ptr(sc), ptr(sh), int(xrelu), ptr(y), ptr(dz), ptr(coef), int(relu),
-                                      int(pool), ptr(zmax), ptr(ties), ptr(w.contiguous()), ptr(dx), ptr(dw), *below, *fin_out,
-                                      stream_ptr())
-    if rc == PN2_EUNSUP_CODE:
+    ok = launch("pn2_linear_bwd_fused", y, rows, cin, cout, ptr(x2d), ptr(sc), ptr(sh), int(xrelu), ptr(y), ptr(dz), ptr(coef),
+                int(relu), int(pool), ptr(zmax), ptr(ties), ptr(w.contiguous()), ptr(dx), ptr(dw), *below, *fin_out, may_refuse=True)
+    if not ok:
         return None
-    check(rc, "pn2_linear_bwd_fused")
-    if link is not None:
-        if gxb:
-            link.coef, link.dgamma, link.dbeta = cb, dgb, dbb
-        link.ws, link.dz_ptr, link.dz_keep, link.folded = pws, dx.data_ptr(), dx, True
+    _note_on_link(link, notes)
     return dx, dw
 
 
@@ -1110,32 +994,19 @@ def _hip_dgrad_gx(y, dz, coef, relu, pool, zmax, ties, w, link):
         return _hip_dgrad_fin(None, (y, dz, coef, relu, pool, zmax, ties), w, link)
     rows, cin = y.shape[0], w.shape[0]
     dx = torch.empty((rows, cin), dtype=torch.float32, device=y.device)
-    pws = _bn_zeroed_scratch(cin, y.device) if link is not None else None
-    with torch.cuda.device(y.device):
-        if link is not None:
-            below = (ptr(link.y), ptr(link.gamma), ptr(link.beta), ptr(link.mean), ptr(link.invstd), int(link.relu), ptr(pws),
-                     pws.numel() * pws.element_size())
-        else:
-            below = (None, None, None, None, None, 0, None, 0)
-        check(lib.pn2_linear_dgrad_gx(rows, cin, w.shape[1], ptr(y), ptr(dz), ptr(coef), int(relu), int(pool), ptr(zmax), ptr(ties),
-                                      ptr(w.contiguous()), ptr(dx), *below, stream_ptr()), "pn2_linear_dgrad_gx")
-    if link is not None:
-        link.ws, link.dz_ptr, link.dz_keep = pws, dx.data_ptr(), dx
+    below, _, notes = _below_args(link, rows, cin, dx, fin=False)
+    launch("pn2_linear_dgrad_gx", y, rows, cin, w.shape[1], ptr(y), ptr(dz), ptr(coef), int(relu), int(pool), ptr(zmax), ptr(ties),
+           ptr(w.contiguous()), ptr(dx), *below)
+    _note_on_link(link, notes)
     return dx
 
 
 def _hip_wgrad_gx(x2d, xf, y, dz, coef, relu, pool, zmax, ties, w):
     """dW = x2d^T @ dy with dy formed on load (pn2_linear_wgrad_gx); xf as in _hip_wgrad"""
-    dw = get_default_store().grad_view(w)
-    if dw is None:
-        arena = get_default_store().zero_arena
-        v = arena.take(w.numel() * 4) if arena is not None else None
-        dw = v[:w.numel() * 4].view(torch.float32).view_as(w) if v is not None else torch.zeros_like(w)
+    dw = _wgrad_out(w)
     sc, sh, xrelu = xf if xf is not None else (None, None, 0)
-    with torch.cuda.device(w.device):
-        check(lib.pn2_linear_wgrad_gx(x2d.shape[0], w.shape[0], w.shape[1], ptr(x2d), ptr(sc), ptr(sh), int(xrelu), ptr(y), ptr(dz),
-                                      ptr(coef), int(relu), int(pool), ptr(zmax), ptr(ties), ptr(dw), stream_ptr()),
-              "pn2_linear_wgrad_gx")
+    launch("pn2_linear_wgrad_gx", w, x2d.shape[0], w.shape[0], w.shape[1], ptr(x2d), ptr(sc), ptr(sh), int(xrelu), ptr(y), ptr(dz),
+           ptr(coef), int(relu), int(pool), ptr(zmax), ptr(ties), ptr(dw))
     return dw
 
 
@@ -1170,15 +1041,11 @@ class _TrainDenseBnRelu(torch.autograd.Function):
             y = torch.empty((bsz * m * ns, c), dtype=torch.float32, device=xyz.device)
             x2d = torch.empty((bsz * m * ns, 3 + cpts), dtype=torch.float32, device=xyz.device)
             if defer:
-                save_mean = torch.empty(c, dtype=torch.float32, device=xyz.device)
-                consts = (save_mean, torch.empty_like(save_mean), torch.empty_like(save_mean), torch.empty_like(save_mean))
+                consts = _bn_consts_out(c, xyz.device)
             cs = consts if consts is not None else (None, None, None, None)
-            with torch.cuda.device(xyz.device):
-                check(lib.pn2_sa_first_layer_bn(bsz, n, m, ns, cpts, c, ptr(xyz), ptr(new_xyz), ptr(points), ptr(idx), ptr(w.contiguous()),
-                                                ptr(y), ptr(x2d), ptr(ws), ws.numel() * ws.element_size(), 2 if defer else 1,
-                                                ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, float(decay), ptr(running_mean),
-                                                ptr(running_var), ptr(cs[0]), ptr(cs[1]), ptr(cs[2]), ptr(cs[3]), stream_ptr()),
-                      "pn2_sa_first_layer_bn")
+            launch("pn2_sa_first_layer_bn", xyz, bsz, n, m, ns, cpts, c, ptr(xyz), ptr(new_xyz), ptr(points), ptr(idx),
+                   ptr(w.contiguous()), ptr(y), ptr(x2d), ptr(ws), nbytes(ws), 2 if defer else 1, ptr(gamma), ptr(beta), ptr(b),
+                   BN_EPSILON, float(decay), ptr(running_mean), ptr(running_var), ptr(cs[0]), ptr(cs[1]), ptr(cs[2]), ptr(cs[3]))
             folded = True
         elif (xf or (USE_GEMM_BN_STATS and c % 32 == 0)) and USE_BN_FINISH_IN_PRODUCER:
             # ONE launch: GEMM (batch norm of the layer below applied on load when it was deferred) + column sums of y + -- in the
@@ -1285,9 +1152,7 @@ USE_HOISTED_TRAIN = True  # first layer of SA2-SA4 / FP4 with its feature half a
 
 def _hip_wgrad_into(x2d, dy, dw_rows):
     """dw_rows (a zero-filled row block of a weight-gradient tile) += x2d^T @ dy on pn2_linear_wgrad_accumulate"""
-    with torch.cuda.device(dy.device):
-        check(lib.pn2_linear_wgrad_accumulate(x2d.shape[0], x2d.shape[1], dy.shape[1], ptr(x2d), ptr(dy), ptr(dw_rows), stream_ptr()),
-              "pn2_linear_wgrad_accumulate")
+    launch("pn2_linear_wgrad_accumulate", dy, x2d.shape[0], x2d.shape[1], dy.shape[1], ptr(x2d), ptr(dy), ptr(dw_rows))
 
 
 class _TrainHoistedBnRelu(torch.autograd.Function):
@@ -1328,22 +1193,19 @@ class _TrainHoistedBnRelu(torch.autograd.Function):
         bn_args = ()
         if fused_stats:
             ws = _bn_zeroed_scratch(cout, src.device)
-            save_mean = torch.empty(cout, dtype=torch.float32, device=src.device)
-            save_invstd, sc, sh = torch.empty_like(save_mean), torch.empty_like(save_mean), torch.empty_like(save_mean)
-            bn_args = (ptr(ws), ws.numel() * ws.element_size(), 2, ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, float(decay),
+            save_mean, save_invstd, sc, sh = _bn_consts_out(cout, src.device)
+            bn_args = (ptr(ws), nbytes(ws), 2, ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, float(decay),
                        ptr(running_mean), ptr(running_var), ptr(save_mean), ptr(save_invstd), ptr(sc), ptr(sh))
-        with torch.cuda.device(src.device):
-            if kind == "sa":
-                a = torch.empty((bsz * rows_b, 3), dtype=torch.float32, device=src.device)
-                fn, nm = (lib.pn2_sa_hoist_rows_bn, "pn2_sa_hoist_rows_bn") if fused_stats else (lib.pn2_sa_hoist_rows, "pn2_sa_hoist_rows")
-                check(fn(bsz, nsrc, m, ns, cout, ptr(xyz), ptr(new_xyz), ptr(idx), ptr(z), ptr(wa), ptr(y), ptr(a), *bn_args,
-                         stream_ptr()), nm)
-            else:
-                a = points1.reshape(-1, c1)
-                if c1 > 8:
-                    raise ValueError("the hoisted FP front end takes at most 8 skip-link channels")
-                fn, nm = (lib.pn2_fp_hoist_rows_bn, "pn2_fp_hoist_rows_bn") if fused_stats else (lib.pn2_fp_hoist_rows, "pn2_fp_hoist_rows")
-                check(fn(bsz, n, nsrc, c1, cout, ptr(dist), ptr(idx), ptr(a), ptr(z), ptr(wa), ptr(y), *bn_args, stream_ptr()), nm)
+        if kind == "sa":
+            a = torch.empty((bsz * rows_b, 3), dtype=torch.float32, device=src.device)
+            launch("pn2_sa_hoist_rows_bn" if fused_stats else "pn2_sa_hoist_rows", src, bsz, nsrc, m, ns, cout, ptr(xyz), ptr(new_xyz),
+                   ptr(idx), ptr(z), ptr(wa), ptr(y), ptr(a), *bn_args)
+        else:
+            a = points1.reshape(-1, c1)
+            if c1 > 8:
+                raise ValueError("the hoisted FP front end takes at most 8 skip-link channels")
+            launch("pn2_fp_hoist_rows_bn" if fused_stats else "pn2_fp_hoist_rows", src, bsz, n, nsrc, c1, cout, ptr(dist), ptr(idx),
+                   ptr(a), ptr(z), ptr(wa), ptr(y), *bn_args)
         ctx.relu, ctx.pool, ctx.kind, ctx.dims = bool(relu), int(pool), kind, (bsz, nsrc, rows_b, c)
         if defer and not pooled:
             if not fused_stats:
@@ -1373,11 +1235,7 @@ class _TrainHoistedBnRelu(torch.autograd.Function):
         dsrc = hip_linear_dgrad(dzs2d, wb).view(bsz, nsrc, c) if ctx.needs_input_grad[0] else None
         dw = None
         if ctx.needs_input_grad[1]:
-            dw = get_default_store().grad_view(w)
-            if dw is None:
-                arena = get_default_store().zero_arena
-                v = arena.take(w.numel() * 4) if arena is not None else None
-                dw = v[:w.numel() * 4].view(torch.float32).view_as(w) if v is not None else torch.zeros_like(w)
+            dw = _wgrad_out(w)
             dwa, dwb = (dw[:3], dw[3:]) if sa else (dw[c:], dw[:c])
             _hip_wgrad_into(src2d, dzs2d, dwb)
             _hip_wgrad_into(a, dy, dwa)
@@ -1515,9 +1373,7 @@ class _Dropout(torch.autograd.Function):
         x = x.contiguous()
         y = torch.empty_like(x)
         mask = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            check(lib.pn2_dropout(x.numel(), ptr(x), float(keep_prob), ptr(state), ptr(y), ptr(mask), stream_ptr()),
-                  "pn2_dropout")
+        launch("pn2_dropout", x, x.numel(), ptr(x), float(keep_prob), ptr(state), ptr(y), ptr(mask))
         ctx.save_for_backward(mask)
         ctx.keep = float(keep_prob)
         return y
@@ -1527,8 +1383,7 @@ class _Dropout(torch.autograd.Function):
         (mask,) = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(dy)
-        with torch.cuda.device(dy.device):
-            check(lib.pn2_dropout_grad(dy.numel(), ptr(dy), ptr(mask), ctx.keep, ptr(dx), stream_ptr()), "pn2_dropout_grad")
+        launch("pn2_dropout_grad", dy, dy.numel(), ptr(dy), ptr(mask), ctx.keep, ptr(dx))
         return dx, None, None
 
 

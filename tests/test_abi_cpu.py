@@ -45,6 +45,49 @@ def test_python_signatures_cover_the_header(pn2):
     assert pn2._lib.lib.pn2_interpolate_label_workspace_bytes(1000) > 2 * (1 << 21) * 4  # two cell tables + lists
 
 
+def test_trace_table_positions_match_the_signatures(pn2):
+    """_lib._TRACE_ARGS tells the benchmark trace where an entry point keeps nlayers and the host widths[] array, and which dense
+    entry point an in-place (*_ld) form is recorded as: every position is checked against the bound signature."""
+    L = pn2._lib
+    assert L._TRACE_ARGS
+    for name, (nl_at, w_at, dense, drop) in L._TRACE_ARGS.items():
+        sig = L.SIGNATURES[name]  # KeyError: the table names an entry point that is not bound
+        assert (nl_at is None) == (w_at is None), name
+        if w_at is not None:
+            assert sig[nl_at] is ctypes.c_int, name
+            assert sig[w_at] is ctypes.c_void_p, name
+        numeric = [i for i, t in enumerate(sig) if t is not ctypes.c_void_p]
+        if name.endswith("_ld"):
+            assert dense in L.SIGNATURES and dense == name[:-3], name
+            assert drop, name
+            # dropping the strides leaves the dense form's numeric arguments, type by type
+            kept = [sig[i] for k, i in enumerate(numeric) if k not in drop]
+            assert kept == [t for t in L.SIGNATURES[dense] if t is not ctypes.c_void_p], name
+            for k in drop:
+                assert sig[numeric[k]] is ctypes.c_int, name
+        else:
+            assert dense is None and drop == (), name
+    # every *_ld entry point is in the table: none is recorded under its own name
+    assert {n for n in L.SIGNATURES if n.endswith("_ld")} <= set(L._TRACE_ARGS)
+    # the size_t queries are bound from their table
+    for name, nargs in L._SIZE_QUERIES.items():
+        fn = getattr(L._raw, name)
+        assert fn.restype is ctypes.c_size_t and fn.argtypes == [ctypes.c_int] * nargs, name
+
+
+def test_launch_helper_host_arrays(pn2):
+    L = pn2._lib
+    a = L.int_array([3, 4.0, True])
+    assert list(a) == [3, 4, 1] and isinstance(a, ctypes.Array)
+    assert list(L.float_array([1, 0.5])) == [1.0, 0.5]
+    assert list(L.u64_array([0, 2 ** 64 - 1])) == [0, 2 ** 64 - 1]
+    t = L.ptr_table([None])
+    assert len(t) == 1 and t[0] is None
+    # accepted as they are where the argtype is c_void_p
+    assert ctypes.c_void_p.from_param(a) is not None and ctypes.c_void_p.from_param(t) is not None
+    assert L.ptr(None) is None
+
+
 def test_argument_validation_needs_no_gpu(pn2):
     L = pn2._lib.lib
     nul = None
