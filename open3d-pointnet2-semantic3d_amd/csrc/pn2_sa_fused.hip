@@ -23,6 +23,7 @@
 // Weights (<= 3 layers, widths <= 128) stay resident in LDS for the whole
 // persistent workgroup.
 #include "pn2_common.h"
+#include <atomic>
 #include <type_traits>
 #include <utility>
 
@@ -50,6 +51,7 @@ struct SaFusedParams {
     const float* bias[3];
     float* out;
     int prio;  // 1: stagger the two waves of a SIMD (see the kernel)
+    int blk;   // PACK: centres per classification block (<= 64), see the kernel
     int schedule;  // FP chain: 0 = lockstep kernel, 1 = software-pipelined kernel, -1 = the default (pipelined where it applies)
 #ifdef PN2_TUNING_HOOKS
     long long* stats;  // tuning builds: cycle stamps of the first workgroups (tools/chain_stage_ab.py)
@@ -249,6 +251,42 @@ __device__ __forceinline__ void pool_store_k(const f32x16 (&acc)[NT], const floa
     }
 }
 
+// pooled epilogue of a PACKED tile (K = 32, see sa_fused_kernel's PACK): the tile holds 32 >> sshift slots of 1 << sshift rows,
+// slot q = rows [q << sshift, (q + 1) << sshift) = accumulator registers [q << (sshift - 1), (q + 1) << (sshift - 1)) of both
+// half-waves, and belongs to centre gq[q].  One maximum per slot, the same half-wave exchange, bias and ReLU as pool_store;
+// slots >= nvalid repeat slot 0's rows and store nothing.  A maximum does not depend on the order it is taken in, nor on how
+// often a value occurs: same bits as pool_store over the centre's 32 rows when the dropped rows are copies of row 0.
+template <int NT>
+__device__ __forceinline__ void pool_store_packed(const f32x16 (&acc)[NT], const float* __restrict__ sbias, float* __restrict__ out,
+                                                  int wout, int sshift, int nvalid, const int (&gq)[4], int half, int l31) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const float bv = sbias[nt * 32 + l31];
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            v[q] = fmaxf(fmaxf(acc[nt][4 * q], acc[nt][4 * q + 1]), fmaxf(acc[nt][4 * q + 2], acc[nt][4 * q + 3]));
+        if (sshift == 3) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float u = fmaxf(v[q], __shfl_xor(v[q], 32));
+                if (half == 0 && q < nvalid) out[(size_t)gq[q] * wout + nt * 32 + l31] = fmaxf(u + bv, 0.f);
+            }
+        } else if (sshift == 4) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                float u = fmaxf(v[2 * q], v[2 * q + 1]);
+                u = fmaxf(u, __shfl_xor(u, 32));
+                if (half == 0 && q < nvalid) out[(size_t)gq[q] * wout + nt * 32 + l31] = fmaxf(u + bv, 0.f);
+            }
+        } else {
+            float u = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+            u = fmaxf(u, __shfl_xor(u, 32));
+            if (half == 0) out[(size_t)gq[0] * wout + nt * 32 + l31] = fmaxf(u + bv, 0.f);
+        }
+    }
+}
+
 // last-layer epilogue without pooling: relu(acc + bias) for all 32 rows of the tile
 template <int NT>
 __device__ __forceinline__ void rows_store(const f32x16 (&acc)[NT], const float* __restrict__ sbias,
@@ -312,9 +350,18 @@ __device__ __forceinline__ void rows_store_pk(const f32x16 (&acc)[NT], const flo
 //                gathered rows of Z are blended STRAIGHT INTO the accumulator layout of layer 1 (register r of tile nt
 //                <-> channel 32 nt + (r & 3) + 8 (r >> 2) + 4 half: four consecutive channels per 16-byte load), only the
 //                c1 skip-link channels still go through the MFMA.  Same gather traffic, (c2 / 2) * NT1 fewer MFMAs per tile.
-template <int L, int NT1, int NT2, int NT3, bool VEC8, bool DENSE, bool POOL, int NW, bool INTERP = false, bool PREZ = false>
+// PACK (gather mode with pooling, K = 32): the ball query pads a short row with copies of its first hit, a padded row's MLP output
+//                is a copy too and the max does not count copies, so only the LIVE prefix of a centre's index row needs the matrix
+//                pipe.  A centre's class is the smallest s in {8, 16, 32} with idx[j] == idx[0] for all j >= s (read from idx
+//                itself: any index table is handled, one without padding classifies as 32 and runs as without PACK).  The
+//                workgroup takes blocks of p.blk consecutive centres, classifies them, and packs four class-8 or two class-16
+//                centres into one 32-row tile; the tile list lives in LDS, wave w runs tiles w, w + NW, ...  Every row keeps its
+//                own MFMA row: which slot it sits in and which rows share its tile do not enter its value (bit-identical output).
+template <int L, int NT1, int NT2, int NT3, bool VEC8, bool DENSE, bool POOL, int NW, bool INTERP = false, bool PREZ = false,
+          bool PACK = false>
 __global__ void __launch_bounds__(NW * 64, (NW >= 8 ? NW / 4 : 2))  // NW <= 8: 2 waves/SIMD (<= 256 VGPR+AGPR per lane)
 sa_fused_kernel(SaFusedParams p) {
+    static_assert(!PACK || (POOL && !DENSE && !INTERP), "PACK: the pooled gather mode only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -338,7 +385,7 @@ sa_fused_kernel(SaFusedParams p) {
     // 128 -> 128 layer alone, 2 x 16 k for two waves together), so a SIMD needs both of its waves in the MFMA phase, and a
     // third wave per SIMD does not fit the register budget (12-wave workgroups: 128 vs 98 us).
 #ifdef PN2_TUNING_HOOKS
-    const bool stagger = NW == 8 && L >= 2 && p.prio != 0;
+    const bool stagger = NW == 8 && L >= 2 && p.prio != 0 && !PACK;
 #else
     constexpr bool stagger = false;  // the experiment is compiled out of the shipped library
 #endif
@@ -351,6 +398,10 @@ sa_fused_kernel(SaFusedParams p) {
     float* sb3 = sb2 + (L >= 2 ? W2 : 0);
     int* stagger_flag = reinterpret_cast<int*>(sb3 + (L >= 3 ? W3 : 0));  // NW ints behind the biases (launch_chain sizes them in)
     if (stagger && tid < NW) stagger_flag[tid] = 0;
+    // PACK: class of each centre of the block (64 ints), then the centres of each tile (64 x 4 ints), behind the flags
+    int* s_cls = stagger_flag + 16;
+    int* s_desc = s_cls + 64;
+    (void)s_cls; (void)s_desc;
     // Weight staging, 8 independent global loads in flight per thread (the permutation index maths is
     // cheap; what must be hidden is the L2 latency -- a workgroup may own only a handful of tiles).
     // 16-byte version: index_of(e4) returns the global FLOAT index of 4 consecutive columns (or -1).
@@ -421,9 +472,62 @@ sa_fused_kernel(SaFusedParams p) {
         g_hi = (xcd + 1) * per;
         g_step = (gridDim.x >> 3) * NW;
     }
+    // PACK: blocks of p.blk centres inside the XCD's range instead of single tiles; pk_* are wave-uniform
+    int pk_b = 0, pk_nb = 0, pk_bstep = 1, pk_lo = 0, pk_hi = 0;
+    if constexpr (PACK) {
+        pk_lo = 0; pk_hi = p.groups; pk_b = blockIdx.x; pk_bstep = gridDim.x;
+        if ((gridDim.x & 7u) == 0u && (p.groups & 7) == 0) {
+            const int per = p.groups >> 3, xcd = blockIdx.x & 7;
+            pk_lo = xcd * per; pk_hi = pk_lo + per; pk_b = blockIdx.x >> 3; pk_bstep = gridDim.x >> 3;
+        }
+        pk_nb = (pk_hi - pk_lo + p.blk - 1) / p.blk;
+    }
+    for (bool pk_first = true;; pk_b += pk_bstep, pk_first = false) {  // !PACK: one pass
+    int pk_base = 0, pk_n32 = 0, pk_t16 = 0, pk_n16 = 0, pk_n8 = 0;
+    if constexpr (PACK) {
+        if (pk_b >= pk_nb) break;
+        if (!pk_first) __syncthreads();  // the previous block's tile list is still being read
+        pk_base = pk_lo + pk_b * p.blk;
+        const int cnt = min(p.blk, pk_hi - pk_base);
+        // classify: a half-wave reads one centre's 32 indices (128 bytes); live slots = 1 + the last position that differs from
+        // position 0 (NOT the number of distinct values: equal entries need not be contiguous)
+        for (int c0 = 2 * wave; c0 < cnt; c0 += 2 * NW) {
+            const int cl = c0 + half;
+            const int v = p.idx[(size_t)(pk_base + (cl < cnt ? cl : c0)) * 32 + l31];
+            const int first = __shfl(v, lane & 32);
+            const unsigned long long diff = __ballot(v != first);
+            const unsigned mine = (unsigned)(diff >> (lane & 32));
+            const int live = 32 - __clz(mine | 1u);  // highest differing position + 1 (>= 1)
+            if (l31 == 0 && cl < cnt) s_cls[cl] = live <= 8 ? 8 : (live <= 16 ? 16 : 32);
+        }
+        __syncthreads();
+        const int cls = lane < cnt ? s_cls[lane] : 0;
+        const unsigned long long m32 = __ballot(cls == 32), m16 = __ballot(cls == 16), m8 = __ballot(cls == 8);
+        const int n16 = __popcll(m16), n8 = __popcll(m8);
+        // an odd class-16 centre shares its tile with the last class-8 centre when that saves the class-8 tile it would open
+        const int promote = ((n16 & 1) && (n8 & 3) == 1) ? 1 : 0;
+        pk_n32 = __popcll(m32); pk_n16 = n16 + promote; pk_n8 = n8 - promote;
+        pk_t16 = (pk_n16 + 1) >> 1;
+        if (wave == 0 && lane < cnt) {
+            const unsigned long long below = (1ull << lane) - 1ull;
+            int tile, slot;
+            if (cls == 32) { tile = __popcll(m32 & below); slot = 0; }
+            else {
+                int c = cls, r = __popcll((cls == 16 ? m16 : m8) & below);
+                if (promote && c == 8 && r == n8 - 1) { c = 16; r = n16; }
+                if (c == 16) { tile = pk_n32 + (r >> 1); slot = r & 1; }
+                else { tile = pk_n32 + pk_t16 + (r >> 2); slot = r & 3; }
+            }
+            s_desc[tile * 4 + slot] = pk_base + lane;
+        }
+        __syncthreads();
+        g_lo = wave; g_hi = pk_n32 + pk_t16 + ((pk_n8 + 3) >> 2); g_step = NW;
+    }
     for (int g = g_lo; g < g_hi; g += g_step, ++tile_no) {
         PN2_CHAIN_STAMP(2);
         size_t prow;  // row of the feature matrix feeding this lane
+        int pk_sshift = 5, pk_nvalid = 1, pk_gq[4] = {0, 0, 0, 0};  // PACK: log2(rows per slot), filled slots, their centres
+        (void)pk_sshift; (void)pk_nvalid; (void)pk_gq;
         f32x16 a1[NT1];
         zero_acc<NT1>(a1);
         constexpr bool LAST1 = (L == 1);
@@ -435,9 +539,22 @@ sa_fused_kernel(SaFusedParams p) {
         } else {
             // tile g = rows [32g, 32g+32) of the flat (b*m*K) neighbour list; K = 32: one centre per tile,
             // K = 16: two centres per tile, K = 64, 128, ...: a centre spans several tiles (max merged at the end)
-            const int grp = (g * 32 + l31) >> p.kshift;
+            int grp, ii;
+            if constexpr (PACK) {
+                // tile g of the block: 32-row slots first, then 16, then 8; the last tile of a class may be short
+                if (g < pk_n32) { pk_sshift = 5; pk_nvalid = 1; }
+                else if (g < pk_n32 + pk_t16) { pk_sshift = 4; pk_nvalid = min(2, pk_n16 - 2 * (g - pk_n32)); }
+                else { pk_sshift = 3; pk_nvalid = min(4, pk_n8 - 4 * (g - pk_n32 - pk_t16)); }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) pk_gq[q] = __builtin_amdgcn_readfirstlane(s_desc[g * 4 + (q < pk_nvalid ? q : 0)]);
+                const int q = l31 >> pk_sshift;
+                grp = q == 1 ? pk_gq[1] : (q == 2 ? pk_gq[2] : (q == 3 ? pk_gq[3] : pk_gq[0]));
+                ii = p.idx[(size_t)grp * 32 + (l31 & ((1 << pk_sshift) - 1))];
+            } else {
+                grp = (g * 32 + l31) >> p.kshift;
+                ii = p.idx[(size_t)g * 32 + l31];
+            }
             const int bi = grp / p.m;
-            const int ii = p.idx[(size_t)g * 32 + l31];
             prow = (size_t)bi * p.n + ii;
             const float cxv = p.new_xyz[(size_t)grp * 3 + 0];
             const float cyv = p.new_xyz[(size_t)grp * 3 + 1];
@@ -572,7 +689,8 @@ sa_fused_kernel(SaFusedParams p) {
         }
         if constexpr (L == 1) {
             if constexpr (POOL) {
-                if (DENSE || p.kshift == 5) pool_store<NT1>(a1, sb1, orow, half, l31);
+                if constexpr (PACK) pool_store_packed<NT1>(a1, sb1, p.out, WOUT, pk_sshift, pk_nvalid, pk_gq, half, l31);
+                else if (DENSE || p.kshift == 5) pool_store<NT1>(a1, sb1, orow, half, l31);
                 else pool_store_k<NT1>(a1, sb1, p.out, WOUT, g, p.kshift, half, l31);
             }
             else rows_store<NT1>(a1, sb1, p.out, WOUT, g * 32, p.rows, half, l31);
@@ -586,7 +704,8 @@ sa_fused_kernel(SaFusedParams p) {
                 __hip_atomic_store(&stagger_flag[wave], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             if constexpr (L == 2) {
                 if constexpr (POOL) {
-                if (DENSE || p.kshift == 5) pool_store<NT2>(a2, sb2, orow, half, l31);
+                if constexpr (PACK) pool_store_packed<NT2>(a2, sb2, p.out, WOUT, pk_sshift, pk_nvalid, pk_gq, half, l31);
+                else if (DENSE || p.kshift == 5) pool_store<NT2>(a2, sb2, orow, half, l31);
                 else pool_store_k<NT2>(a2, sb2, p.out, WOUT, g, p.kshift, half, l31);
             }
                 else rows_store<NT2>(a2, sb2, p.out, WOUT, g * 32, p.rows, half, l31);
@@ -599,13 +718,16 @@ sa_fused_kernel(SaFusedParams p) {
                 if (stagger && tile_no == 0 && wave < NW / 2 && lane == 0)
                     __hip_atomic_store(&stagger_flag[wave], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 if constexpr (POOL) {
-                if (DENSE || p.kshift == 5) pool_store<NT3>(a3, sb3, orow, half, l31);
+                if constexpr (PACK) pool_store_packed<NT3>(a3, sb3, p.out, WOUT, pk_sshift, pk_nvalid, pk_gq, half, l31);
+                else if (DENSE || p.kshift == 5) pool_store<NT3>(a3, sb3, orow, half, l31);
                 else pool_store_k<NT3>(a3, sb3, p.out, WOUT, g, p.kshift, half, l31);
             }
                 else rows_store<NT3>(a3, sb3, p.out, WOUT, g * 32, p.rows, half, l31);
             }
         }
         PN2_CHAIN_STAMP(6);
+    }
+    if constexpr (!PACK) break;
     }
     // a wave of the first half without a (complete) first tile must not leave its partner waiting
     if (stagger && wave < NW / 2 && lane == 0)
@@ -915,9 +1037,31 @@ PN2_TUNABLE(int, g_chain_grid, 256)  // tuning hook (pn2_debug_set(6, v)): persi
 PN2_TUNABLE(long long*, g_chain_trace, nullptr)  // tuning hook: (8 x 1024) counters + (8 x 1024 x 16 x 2) stamps, see SaFusedParams::trace
 PN2_TUNABLE(int, g_chain_tag, 0)     // tuning hook (pn2_debug_set(16, v)): graph tag of the launches captured from now on
 
+// Row packing of the pooled K = 32 gather kernels (sa_fused_kernel's PACK): process-wide, on by default.  The choice is read when
+// a launch is issued, so a captured graph keeps the one it was captured with.
+std::atomic<int> g_sa_row_packing{1};
+constexpr size_t kPackLdsBytes = (64 + 64 * 4) * sizeof(int);  // classes + tile list of one block
+
+template <int L, int NT1, int NT2, int NT3, bool VEC8, bool DENSE, bool POOL, int NW, bool INTERP, bool PREZ>
+auto chain_kernel(bool pack) -> void (*)(SaFusedParams) {
+    if constexpr (POOL && !DENSE && !INTERP) {
+        if (pack) return sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, NW, INTERP, PREZ, true>;
+    }
+    return sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, NW, INTERP, PREZ, false>;
+}
+
+// PACK: centres per block = the share of one workgroup of its XCD's range (the kernel's own split), at most 64 (one ballot)
+inline int pack_block(int groups, int grid) {
+    int per = groups, nsl = grid;
+    if ((grid & 7) == 0 && (groups & 7) == 0) { per = groups >> 3; nsl = grid >> 3; }
+    const int blk = (per + nsl - 1) / nsl;
+    return blk < 1 ? 1 : (blk > 64 ? 64 : blk);
+}
+
 template <int L, int NT1, int NT2, int NT3, bool VEC8, bool DENSE, bool POOL, bool INTERP = false, bool PREZ = false>
 int launch_chain(const SaFusedParams& p_in, hipStream_t st) {
     SaFusedParams p = p_in;
+    const bool pack = POOL && !DENSE && !INTERP && p.kshift == 5 && g_sa_row_packing.load(std::memory_order_relaxed) != 0;
     p.prio = g_chain_prio;
     if (!p.ldx) p.ldx = 3;
     if (!p.ldp) p.ldp = p.c;
@@ -1000,30 +1144,32 @@ int launch_chain(const SaFusedParams& p_in, hipStream_t st) {
     if (bytes > 78 * 1024 && p.groups >= 2048 && g_chain_nw != 4) {  // g_chain_nw == 4 (tuning): one wave per SIMD
         // only one workgroup fits per CU: give it 8 waves (2 per SIMD) sharing the LDS weights.
         // (With fewer than 2048 tiles, 4-wave workgroups spread the tiles over twice as many CUs.)
-        auto kern = sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 8, INTERP, PREZ>;
-        static bool attr_set = false;  // per instantiation; benign race (idempotent call)
-        if (!attr_set) {
+        auto kern = chain_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 8, INTERP, PREZ>(pack);
+        static bool attr_set[2] = {false, false};  // per instantiation; benign race (idempotent call)
+        if (!attr_set[pack]) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return (int)e;
-            attr_set = true;
+            attr_set[pack] = true;
         }
         int grid = g_chain_grid;
         const int need8 = (p.groups + 7) / 8;
         if (grid > need8) grid = need8;
-        kern<<<grid, 512, bytes, st>>>(p);
+        p.blk = pack_block(p.groups, grid);
+        kern<<<grid, 512, bytes + (pack ? kPackLdsBytes : 0), st>>>(p);
     } else {
-        auto kern = sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 4, INTERP, PREZ>;
-        static bool attr_set = false;
-        if (!attr_set) {
+        auto kern = chain_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 4, INTERP, PREZ>(pack);
+        static bool attr_set[2] = {false, false};
+        if (!attr_set[pack]) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return (int)e;
-            attr_set = true;
+            attr_set[pack] = true;
         }
         int grid = bytes > 78 * 1024 ? g_chain_grid : g_chain_grid * 2;  // 4-wave workgroups: as many as LDS lets co-reside per CU
         if (grid > need4) grid = need4;
-        kern<<<grid, 256, bytes, st>>>(p);
+        p.blk = pack_block(p.groups, grid);
+        kern<<<grid, 256, bytes + (pack ? kPackLdsBytes : 0), st>>>(p);
     }
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
@@ -1043,6 +1189,13 @@ extern "C" int pn2_debug_set_fused(int what, int value) {
     return PN2_EINVAL;
 }
 #endif  // PN2_TUNING_HOOKS
+
+// Row packing of the pooled K = 32 set-abstraction kernels on (non-zero, the default) or off: same bits either way (the A/B and
+// parity switch).  Takes effect for launches issued after the call.
+extern "C" int pn2_set_sa_row_packing(int on) {
+    g_sa_row_packing.store(on != 0, std::memory_order_relaxed);
+    return PN2_OK;
+}
 
 static int sa_fused_impl(int b, int n, int m, int nsample, int c, const float* xyz,
                          const float* new_xyz, const float* points, const int* idx,

@@ -100,6 +100,7 @@ def _sa_fused_inference(xyz, new_xyz, points, idx, mlp, bn, conv_scope_fmt, pool
         bs.append(b2)
         cin = cout
     L = len(mlp)
+    _sync_sa_row_packing(xyz)
     widths, bptrs = int_array(mlp), ptr_table(bs)
     oshape = (b, m, mlp[-1]) if pool else (b, m, nsample, mlp[-1])
     out = torch.empty(oshape, dtype=torch.float32, device=xyz.device)
@@ -264,6 +265,21 @@ USE_FUSED_SA = True
 
 
 USE_HOISTED_SA = True  # A/B: feature part of the first SA layer computed on the source points (linearity)
+# A/B and parity switch: the pooled K = 32 SA kernels skip the rows the ball query padded (csrc/pn2_sa_fused.hip, PACK).  Same
+# bits either way.  The library's switch is process-wide and on by default: it is told only when this flag differs from what it
+# was last told.  A captured graph keeps the choice it was captured with.
+USE_SA_ROW_PACKING = True
+_sa_row_packing_told = True
+
+
+def _sync_sa_row_packing(where):
+    global _sa_row_packing_told
+    want = bool(USE_SA_ROW_PACKING)
+    if want != _sa_row_packing_told:
+        launch("pn2_set_sa_row_packing", where, int(want), stream=False)
+        _sa_row_packing_told = want
+
+
 USE_HOISTED_FP = True  # A/B: first FP layer's product with the interpolated channels computed on the known points (linearity)
 def sa_geometry(xyz, npoint, radius, nsample):
     """The feature-independent half of an SA layer: FPS -> gather -> ball query.
