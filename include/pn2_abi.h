@@ -465,10 +465,15 @@ int pn2_bn_relu_backward_stats(long long rows, int c, const float *dz, const flo
 /* model.get_loss  model.py:152-161: weighted sparse softmax cross-entropy, reduction SUM_BY_NONZERO_WEIGHTS.
  * logits (rows,num_class) f32, labels (rows) int32 (label64 = 0) or int64 (label64 = 1), weights (rows) f32 ->
  * *loss (device f32) = sum_r w_r*ce_r / max(1, #{w_r != 0}).  lse (rows) f32 and acc (2 doubles, zeroed by the callee)
- * carry the forward's results to the backward.  num_class <= 64. */
+ * carry the forward's results to the backward.  num_class <= 64.
+ * A row whose label lies outside [0, num_class) behaves as a row of weight 0: it adds nothing to the sum, is not counted
+ * in #{w_r != 0}, and gets a zero gradient row from the backward (its lse is still written).  An int64 label is compared at
+ * 64 bits: 2^32 + 3 is out of range although its low word is a class.  pn2_confusion_update sets the same rows aside.
+ * PN2_EINVAL: rows <= 0 or num_class <= 0; PN2_EUNSUP: num_class > 64; PN2_ENULL: a NULL pointer other than gout. */
 int pn2_weighted_ce_forward(int rows, int num_class, const float *logits, const void *labels, int label64,
                             const float *weights, float *lse, double *acc, float *loss, void *stream);
-/* d loss / d logits = gout * w_r / nz * (softmax_r - onehot_r); gout: device scalar (upstream gradient) or NULL (= 1). */
+/* d loss / d logits = gout * w_r / nz * (softmax_r - onehot_r), a row of zeros where the label is out of range;
+ * gout: device scalar (upstream gradient) or NULL (= 1). */
 int pn2_weighted_ce_backward(int rows, int num_class, const float *logits, const void *labels, int label64,
                              const float *weights, const float *lse, const double *acc, const float *gout,
                              float *dlogits, void *stream);
@@ -488,7 +493,8 @@ int pn2_confusion_update(int rows, int num_class, const float *logits, const voi
 
 /* tf_util.dropout  util/tf_util.py:646-665 (tf.nn.dropout): y = x / keep_prob where kept, else 0; mask (n bytes) for the
  * backward.  state: device int64[2] = {seed, step}; the draw is a pure function of (seed, step, element index), so a
- * captured graph can be replayed while the caller advances `step` in device memory. */
+ * captured graph can be replayed while the caller advances `step` in device memory.  keep_prob = 1 keeps every element
+ * whatever it draws.  PN2_EINVAL: n <= 0, or keep_prob not in (0, 1] (NaN included). */
 int pn2_dropout(long long n, const float *x, float keep_prob, const long long *state, float *y,
                 unsigned char *mask, void *stream);
 int pn2_dropout_grad(long long n, const float *dy, const unsigned char *mask, float keep_prob, float *dx,

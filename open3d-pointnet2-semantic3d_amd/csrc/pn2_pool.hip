@@ -51,9 +51,8 @@ group_pool_kernel(long long rows, int k, int c, int mode, const float* __restric
 }
 
 // gradient w.r.t. x only (grouped_xyz comes from index ops: no gradient, like the reference's NoGradient ops).
-// max: the gradient goes to the FIRST neighbour that attains the maximum (tf.reduce_max splits ties evenly in TF; the
-// model's own max pooling lives in the batch-norm kernels with TF's even split -- this entry point serves the
-// inference-style poolings of the API and documents the difference).
+// max: neighbours that attain the maximum share its gradient evenly, g / #ties each, as tf.reduce_max's gradient does (the
+// model's own max pooling lives in the batch-norm kernels with the same even split).
 template <int V>
 __global__ void __launch_bounds__(256)
 group_pool_grad_kernel(long long rows, int k, int c, int mode, const float* __restrict__ x, const float* __restrict__ gxyz,

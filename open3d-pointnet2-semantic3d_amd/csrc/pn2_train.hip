@@ -10,6 +10,12 @@ namespace {
 
 constexpr int kCeMaxClasses = 64;
 
+// A label outside [0, C) -- compared at the label's own width, so an int64 whose low word happens to be a class is still
+// outside -- makes its row behave as weight 0 in the forward AND the backward: no loss, no count, zero gradient
+// (pn2_confusion_update sets the same rows aside).
+template <typename LabelT>
+__device__ __forceinline__ bool ce_label_valid(LabelT lab, int C) { return lab >= 0 && lab < (LabelT)C; }
+
 // one thread per point: logits row (C floats) -> lse, w * (lse - logit[label]); block partials -> two fp64 atomics
 template <typename LabelT>
 __global__ void __launch_bounds__(256)
@@ -26,11 +32,13 @@ ce_forward_kernel(int rows, int C, const float* __restrict__ logits, const Label
         for (int c = 0; c < C; ++c) se += expf(z[c] - mx);
         const float lse = mx + logf(se);
         lse_out[r] = lse;
-        const int lab = (int)labels[r];
-        const float wr = w[r];
-        const float ce = lse - z[lab >= 0 && lab < C ? lab : 0];
-        loss = (double)(wr * ce);
-        nz = wr != 0.f ? 1.0 : 0.0;
+        const LabelT lab = labels[r];
+        if (ce_label_valid(lab, C)) {
+            const float wr = w[r];
+            const float ce = lse - z[(int)lab];
+            loss = (double)(wr * ce);
+            nz = wr != 0.f ? 1.0 : 0.0;
+        }
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) { loss += __shfl_xor(loss, o); nz += __shfl_xor(nz, o); }
@@ -58,7 +66,8 @@ ce_backward_kernel(long long total, int C, const float* __restrict__ logits, con
         const long long r = e / C;
         const int c = (int)(e - r * C);
         const float p = expf(logits[e] - lse[r]);
-        dlogits[e] = scale * w[r] * (p - ((int)labels[r] == c ? 1.f : 0.f));
+        const LabelT lab = labels[r];
+        dlogits[e] = ce_label_valid(lab, C) ? scale * w[r] * (p - (lab == (LabelT)c ? 1.f : 0.f)) : 0.f;
     }
 }
 
@@ -78,7 +87,8 @@ dropout_kernel(long long n, const float* __restrict__ x, float keep, const long 
                float* __restrict__ y, unsigned char* __restrict__ mask) {
     const unsigned long long seed = (unsigned long long)state[0], step = (unsigned long long)state[1];
     const float inv = 1.0f / keep;
-    const unsigned thr = keep >= 1.f ? 0xFFFFFFFFu : (unsigned)((double)keep * 4294967296.0);
+    const bool all = keep >= 1.f;  // keep_prob = 1 keeps every element, a draw of 0xFFFFFFFF included
+    const unsigned thr = all ? 0xFFFFFFFFu : (unsigned)((double)keep * 4294967296.0);
     const long long nv = n / VEC;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < nv; e += (long long)gridDim.x * 256) {
         if constexpr (VEC == 4) {
@@ -88,14 +98,14 @@ dropout_kernel(long long n, const float* __restrict__ x, float keep, const long 
             unsigned mw = 0;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const bool k = mix_u32(seed, step, (unsigned long long)(e * 4 + u)) < thr;
+                const bool k = all || mix_u32(seed, step, (unsigned long long)(e * 4 + u)) < thr;
                 mw |= (k ? 1u : 0u) << (8 * u);
                 out[u] = k ? in[u] * inv : 0.f;
             }
             reinterpret_cast<unsigned*>(mask)[e] = mw;
             reinterpret_cast<float4*>(y)[e] = make_float4(out[0], out[1], out[2], out[3]);
         } else {
-            const bool k = mix_u32(seed, step, (unsigned long long)e) < thr;
+            const bool k = all || mix_u32(seed, step, (unsigned long long)e) < thr;
             mask[e] = k ? 1 : 0;
             y[e] = k ? x[e] * inv : 0.f;
         }
@@ -204,7 +214,8 @@ multi_copy_kernel(MultiCopyArgs a) {
 
 // model.get_loss (reference model.py:152-161): logits (rows,C) f32, labels (rows) int32 (label64 = 0) or int64 (label64 = 1),
 // weights (rows) f32 -> *loss = sum_r w_r * ce_r / max(1, #{w_r != 0}).  lse (rows) and acc (2 doubles) are kept for the
-// backward; acc is zeroed here.  No host synchronisation.
+// backward; acc is zeroed here.  A row whose label is outside [0, num_class) counts as weight 0 (its lse is still written).
+// No host synchronisation.
 extern "C" int pn2_weighted_ce_forward(int rows, int num_class, const float* logits, const void* labels, int label64,
                                        const float* weights, float* lse, double* acc, float* loss, void* stream) {
     if (rows <= 0 || num_class <= 0) return PN2_EINVAL;
@@ -221,7 +232,8 @@ extern "C" int pn2_weighted_ce_forward(int rows, int num_class, const float* log
     return PN2_OK;
 }
 
-// d loss / d logits = gout * w_r / nz * (softmax_r - onehot_r); gout (device scalar) may be NULL (= 1).
+// d loss / d logits = gout * w_r / nz * (softmax_r - onehot_r), 0 for a row with an out-of-range label; gout (device scalar)
+// may be NULL (= 1).
 extern "C" int pn2_weighted_ce_backward(int rows, int num_class, const float* logits, const void* labels, int label64,
                                         const float* weights, const float* lse, const double* acc, const float* gout,
                                         float* dlogits, void* stream) {

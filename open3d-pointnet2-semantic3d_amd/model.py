@@ -241,7 +241,11 @@ class _WeightedCE(torch.autograd.Function):
 def get_loss(pred, label, smpw, end_points=None):
     """Weighted sparse softmax cross-entropy, tf.losses reduction SUM_BY_NONZERO_WEIGHTS
     (model.py:152-161): sum(w * ce) / count(w != 0), on pn2_weighted_ce_forward / _backward (one pass each, no host
-    synchronisation).  `end_points` is accepted and unused, as in the reference."""
+    synchronisation).  `end_points` is accepted and unused, as in the reference.
+
+    A point whose label lies outside [0, num_class) counts as a point of weight 0: it adds no loss, is left out of
+    count(w != 0) and gets zero gradient, in the forward and the backward alike (util.metric's confusion matrix sets the same
+    points aside).  Labels are compared at their own width: the int64 label 2**32 + 3 is out of range."""
     from ._lib import require_cuda
     require_cuda(pred, label, smpw)
     if label.dtype not in (torch.int32, torch.int64):

@@ -250,6 +250,19 @@ def test_dropout_statistics_scaling_and_replay(pn2, cuda):
     assert abs(float((y3 != 0).float().mean()) - 0.9) < 2e-3
 
 
+def adam_ref_step(p, m, v, g, lr_t, b1, b2, eps, grad_scale):
+    """One tf.train.AdamOptimizer step in float64 on float64 state (p, m, v) with the float32 gradient g -> (p, m, v).
+    The kernel (like TensorFlow's fp32 kernel) holds beta1, beta2, lr_t, epsilon and grad_scale as float32 and forms 1 - beta in
+    float32; epsilon sits OUTSIDE the bias correction."""
+    f = np.float32
+    ge = np.asarray(g, np.float32).astype(np.float64) * float(f(grad_scale))
+    b1f, b2f, c1, c2, lrf = float(f(b1)), float(f(b2)), float(f(1) - f(b1)), float(f(1) - f(b2)), float(f(lr_t))
+    m = b1f * m + c1 * ge
+    v = b2f * v + c2 * ge * ge
+    p = p - lrf * m / (np.sqrt(v) + float(f(eps)))
+    return p, m, v
+
+
 def test_adam_step_matches_tf_formula(pn2, cuda):
     import torch
     L = pn2._lib
@@ -264,13 +277,7 @@ def test_adam_step_matches_tf_formula(pn2, cuda):
         lr_t = pn2.train.adam_lr_t(lr, t, b1, b2)
         hyper = T(np.array([lr_t, b1, b2, eps, 0.5], np.float32), cuda)   # grad_scale 0.5 = 1/world for two ranks
         L.check(L.lib.pn2_adam_step(n, L.ptr(tp), L.ptr(T(g, cuda)), L.ptr(tm), L.ptr(tv), L.ptr(hyper), L.stream_ptr()), "adam")
-        ge = g.astype(np.float64) * 0.5
-        # the kernel (like TensorFlow's fp32 kernel) holds beta1, beta2 and lr_t as float32 and forms 1 - beta in float32
-        f = np.float32
-        b1f, b2f, c1, c2, lrf = float(f(b1)), float(f(b2)), float(f(1) - f(b1)), float(f(1) - f(b2)), float(f(lr_t))
-        mr = b1f * mr + c1 * ge
-        vr = b2f * vr + c2 * ge * ge
-        pr = pr - lrf * mr / (np.sqrt(vr) + float(f(eps)))   # tf.train.AdamOptimizer: epsilon OUTSIDE the bias correction
+        pr, mr, vr = adam_ref_step(pr, mr, vr, g, lr_t, b1, b2, eps, 0.5)
         np.testing.assert_allclose(tp.cpu().numpy(), pr, rtol=2e-6, atol=2e-7)
         np.testing.assert_allclose(tm.cpu().numpy(), mr, rtol=2e-6, atol=1e-9)
         np.testing.assert_allclose(tv.cpu().numpy(), vr, rtol=2e-6, atol=1e-12)
