@@ -7,7 +7,12 @@ synthetic scenes -- one to train on, one to validate on:
                 reset_eval_metrics -> V eval_step batches (captured inference forward + loss + counting) -> eval_metrics
 
 It also prints what the metrics cost per training step (the captured step replayed with and without them).
-usage: python examples/train_eval_synthetic.py [epochs] [steps_per_epoch] [val_batches] [scene_points]"""
+usage: python examples/train_eval_synthetic.py [epochs] [steps_per_epoch] [val_batches] [scene_points]
+                                               [--optimizer {adam,momentum}] [--save PATH] [--resume PATH]
+--optimizer: the reference's semantic.json "optimizer" (train.py:380-388).  --save: the trainer's state (variables, moving
+averages, optimizer slots, step count) after the last epoch; --resume: load such a file before the first step -- the run then
+continues where the saved one stopped (same learning-rate staircase, batch-norm decay, dropout stream)."""
+import argparse
 import os
 import sys
 import time
@@ -43,14 +48,20 @@ def log(title, m):
 
 
 def main():
-    epochs = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-    val_batches = int(sys.argv[3]) if len(sys.argv) > 3 else 4
-    n_scene = int(sys.argv[4]) if len(sys.argv) > 4 else 1000000
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("epochs", type=int, nargs="?", default=3)
+    ap.add_argument("steps_per_epoch", type=int, nargs="?", default=20)
+    ap.add_argument("val_batches", type=int, nargs="?", default=4)
+    ap.add_argument("scene_points", type=int, nargs="?", default=1000000)
+    ap.add_argument("--optimizer", choices=["adam", "momentum"], default="adam")
+    ap.add_argument("--save", metavar="PATH", help="write the trainer's state here after the last epoch")
+    ap.add_argument("--resume", metavar="PATH", help="load a saved state before the first step")
+    args = ap.parse_args()
+    epochs, steps, val_batches, n_scene = args.epochs, args.steps_per_epoch, args.val_batches, args.scene_points
     dev = torch.device("cuda:0")
     train_fd, train_w = make_scene(0, n_scene, dev)
     val_fd, val_w = make_scene(1, n_scene, dev)
-    hp = dict(pn2.model.SEMANTIC_HYPERPARAMS)
+    hp = dict(pn2.model.SEMANTIC_HYPERPARAMS, optimizer=args.optimizer)
     B, N = hp["batch_size"], hp["num_point"]
 
     def batch(fd, w):
@@ -61,6 +72,9 @@ def main():
     # validation loss is 0 under SUM_BY_NONZERO_WEIGHTS; here the training weights are used so that the loss says something.)
     val = [batch(val_fd, val_w) for _ in range(val_batches)]
     tr = pn2.train.Trainer(hp, 9, store=pn2.util.tf_util.VariableStore(device=dev, seed=0), device=dev, track_metrics=True)
+    if args.resume:
+        tr.load(args.resume)  # applied when the first batch (the validation below) creates the variables
+        print("resuming from %s" % args.resume)
 
     def validate(title):
         tr.reset_eval_metrics()
@@ -82,6 +96,9 @@ def main():
         last = validate("---- epoch %03d validation ----" % epoch)
     train_fd.check_last()
     val_fd.check_last()
+    if args.save:
+        tr.save(args.save)
+        print("saved the trainer's state after step %d to %s" % (tr.step_count, args.save))
     print("validation accuracy: %.4f at initialisation -> %.4f after %d steps" % (init["accuracy"], last["accuracy"],
                                                                                   epochs * steps))
 

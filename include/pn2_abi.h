@@ -510,6 +510,11 @@ int pn2_relu_grad(long long n, const float *z, const float *dz, float *dx, void 
 int pn2_adam_step(long long n, float *params, const float *grads, float *m, float *v, const float *hyper,
                   void *stream);
 
+/* tf.train.MomentumOptimizer(lr, momentum).apply_gradients, use_nesterov = False (train.py:380-383), one launch over flat
+ * fp32 buffers of n elements:  g' = grads[i] * grad_scale;  accum[i] = momentum * accum[i] + g';  params[i] -= lr * accum[i]
+ * hyper: DEVICE float[3] = {lr, momentum, grad_scale}  (lr first: it is the per-step slot a captured step rewrites) */
+int pn2_momentum_step(long long n, float *params, const float *grads, float *accum, const float *hyper, void *stream);
+
 /* sample_and_group's tail for layers too wide for the fused kernel (util/pointnet_util.py:39-54: group_point(xyz) -
  * tile(new_xyz), group_point(points), concat [xyz | points]) in one pass: out (b,m,nsample,3+c) with
  * out[..., :3] = xyz[idx] - new_xyz and out[..., 3:] = points[idx] (c may be 0, then points may be NULL). */

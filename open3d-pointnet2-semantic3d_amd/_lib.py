@@ -142,6 +142,7 @@ SIGNATURES = {
     "pn2_dropout_grad": [ctypes.c_longlong, c_void_p, c_void_p, c_float, c_void_p, c_void_p],
     "pn2_relu_grad": [ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p],
     "pn2_adam_step": [ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "pn2_momentum_step": [ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "pn2_scene_extract_z_box": [c_int, c_void_p, c_int, c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int,
                                 c_void_p, c_void_p, c_void_p],
     "pn2_scene_sample": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double,
@@ -243,12 +244,12 @@ def _load():
 _raw = _load()
 
 
-# entry points that mutate caller state beyond their outputs (moving averages): never launched twice by the dup hook
+# entry points that mutate caller state beyond their outputs (moving averages, optimizer slots): never launched twice by the dup hook
 _STATEFUL = frozenset({"pn2_bn_relu_forward", "pn2_bn_relu_forward_ws0", "pn2_bn_relu_forward_stats", "pn2_linear_bn_stats",
                        "pn2_bn_relu_forward_pool", "pn2_bn_relu_forward_deferred", "pn2_linear_bn_stats_xf", "pn2_linear_wgrad_gx",
                        "pn2_linear_wgrad_accumulate_xf", "pn2_bn_grad_constants", "pn2_linear_dgrad_gx", "pn2_linear_dgrad_fin",
                        "pn2_linear_bn_stats_fin", "pn2_bn_relu_forward_mode", "pn2_sa_first_layer_bn", "pn2_sa_hoist_rows_bn", "pn2_fp_hoist_rows_bn", "pn2_linear_bwd_fused", "pn2_linear_dgrad_bn_grad_stats",
-                       "pn2_adam_step", "pn2_linear_wgrad_accumulate"})
+                       "pn2_adam_step", "pn2_momentum_step", "pn2_linear_wgrad_accumulate"})
 
 
 class _LibProxy:

@@ -1,7 +1,8 @@
 // pn2_train.hip -- the training step's non-GEMM tail on the device:
 //   * weighted sparse softmax cross-entropy, reduction SUM_BY_NONZERO_WEIGHTS (reference model.py:152-161), forward + backward;
 //   * dropout (util/tf_util.py:646-665 -> tf.nn.dropout: keep with probability keep_prob, scale by 1/keep_prob);
-//   * Adam exactly as tf.train.AdamOptimizer applies it (reference train.py:381-388), ONE launch over the flat parameter buffer.
+//   * Adam exactly as tf.train.AdamOptimizer applies it (reference train.py:381-388), ONE launch over the flat parameter buffer;
+//   * momentum as tf.train.MomentumOptimizer applies it (reference train.py:380-383), likewise.
 // Step-dependent scalars (learning rate with bias correction, dropout step counter, upstream loss gradient) are read from
 // DEVICE memory, so a captured hipGraph of the whole step can be replayed while they change.
 #include "pn2_common.h"
@@ -164,6 +165,41 @@ adam_kernel(long long n, float* __restrict__ p, const float* __restrict__ g, flo
     }
 }
 
+// tf.train.MomentumOptimizer (python/training/momentum.py, use_nesterov = False): accum <- momentum accum + g; p <- p - lr accum.
+// ONE set of expressions for both paths of momentum_kernel: an element's result does not depend on the path it took.
+__device__ __forceinline__ void momentum_update(float& p, float g, float& a, float lr, float mom, float gs) {
+    const float gi = g * gs;  // gs = 1/world after a summing all-reduce
+    const float ai = mom * a + gi;
+    a = ai;
+    p -= lr * ai;
+}
+
+// Pure streaming: 12 bytes read, 8 written per element.  The first nv4 groups of four go as 16-byte lanes (the entry point passes
+// nv4 = n / 4 when p, g and a are all 16-byte aligned, 0 otherwise), the elements from 4 * nv4 on one by one.
+__global__ void __launch_bounds__(256)
+momentum_kernel(long long n, long long nv4, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ a,
+                const float* __restrict__ hyper /* [lr, momentum, grad_scale] */) {
+    const float lr = hyper[0], mom = hyper[1], gs = hyper[2];
+    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+    for (long long e = tid; e < nv4; e += stride) {
+        float4 pv = reinterpret_cast<const float4*>(p)[e];
+        float4 av = reinterpret_cast<const float4*>(a)[e];
+        const float4 gv = reinterpret_cast<const float4*>(g)[e];
+        momentum_update(pv.x, gv.x, av.x, lr, mom, gs);
+        momentum_update(pv.y, gv.y, av.y, lr, mom, gs);
+        momentum_update(pv.z, gv.z, av.z, lr, mom, gs);
+        momentum_update(pv.w, gv.w, av.w, lr, mom, gs);
+        reinterpret_cast<float4*>(a)[e] = av;
+        reinterpret_cast<float4*>(p)[e] = pv;
+    }
+    for (long long i = nv4 * 4 + tid; i < n; i += stride) {
+        float pi = p[i], ai = a[i];
+        momentum_update(pi, g[i], ai, lr, mom, gs);
+        a[i] = ai;
+        p[i] = pi;
+    }
+}
+
 inline int grid_1d(long long n) {
     long long g = (n + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 256 * 16 ? 256 * 16 : g));
@@ -293,6 +329,18 @@ extern "C" int pn2_adam_step(long long n, float* params, const float* grads, flo
     if (n <= 0) return PN2_EINVAL;
     if (!params || !grads || !m || !v || !hyper) return PN2_ENULL;
     adam_kernel<<<grid_1d(n), 256, 0, static_cast<hipStream_t>(stream)>>>(n, params, grads, m, v, hyper);
+    PN2_RETURN_IF_LAUNCH_FAILED();
+    return PN2_OK;
+}
+
+// One tf.train.MomentumOptimizer step (use_nesterov = False, train.py:380-383) over flat fp32 buffers of n elements
+// (parameters, gradients, the accumulator slot).  hyper: device float[3] = {lr, momentum, grad_scale}.
+extern "C" int pn2_momentum_step(long long n, float* params, const float* grads, float* accum, const float* hyper, void* stream) {
+    if (n <= 0) return PN2_EINVAL;
+    if (!params || !grads || !accum || !hyper) return PN2_ENULL;
+    const bool aligned = (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)accum) % 16) == 0;
+    const long long nv4 = aligned ? n / 4 : 0;  // the n % 4 elements behind the vectors (< one block) take the scalar loop
+    momentum_kernel<<<grid_1d(nv4 > 0 ? nv4 : n), 256, 0, static_cast<hipStream_t>(stream)>>>(n, nv4, params, grads, accum, hyper);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

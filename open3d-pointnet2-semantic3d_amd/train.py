@@ -4,8 +4,10 @@ Restates what train.py of the reference does per batch (train.py:80-119 schedule
 minimize, model.py:152-161 loss) on the MI355X layer API: forward with batch-statistic BatchNorm
 (HIP index/gather kernels + differentiable torch layers), weighted sparse softmax cross-entropy,
 backward through the HIP gradient kernels (group_point_grad, gather_point_grad,
-three_interpolate_grad, pn2_linear_dgrad / _wgrad), a two-bucket RCCL all-reduce overlapped with backward, Adam.
+three_interpolate_grad, pn2_linear_dgrad / _wgrad), a two-bucket RCCL all-reduce overlapped with backward, Adam or momentum.
 """
+from collections import OrderedDict
+
 import torch
 
 from . import dist as pdist
@@ -32,10 +34,16 @@ def adam_lr_t(lr, t, beta1=0.9, beta2=0.999):
 class Trainer:
     """One process per GPU.  Everything between the input batch and the updated weights runs on the HIP library:
     forward GEMMs (pn2_linear), batch-norm kernels, weighted CE (pn2_weighted_ce_*), dropout (pn2_dropout), data and
-    weight gradients (pn2_linear_dgrad / _wgrad), index-op gradients, and ONE Adam launch over flat parameter / moment
-    buffers (pn2_adam_step).  torch supplies memory, streams, the autograd tape and torch.distributed.
+    weight gradients (pn2_linear_dgrad / _wgrad), index-op gradients, and ONE optimizer launch over flat parameter / slot
+    buffers.  torch supplies memory, streams, the autograd tape and torch.distributed.
 
-    Step-dependent scalars live in device memory (learning rate with Adam's bias correction, dropout step), so after
+    The optimizer is the reference's choice (semantic.json "optimizer", train.py:380-388): "adam" (the default) is
+    tf.train.AdamOptimizer -- pn2_adam_step over flat_p and the slots flat_m, flat_v, device scalars [lr_t, beta1, beta2, eps,
+    1/world]; "momentum" is tf.train.MomentumOptimizer(lr, momentum=hp["momentum"]) -- pn2_momentum_step over flat_p and the
+    one slot flat_accum, device scalars [lr, momentum, 1/world], the plain scheduled rate with no bias correction.  `slots`
+    maps the slot names ("m", "v" / "accum") to their flat buffers.
+
+    Step-dependent scalars live in device memory (the optimizer's learning rate, dropout step), so after
     `warmup_eager` ordinary steps the step is captured and replayed: on one GPU as ONE hipGraph; with several ranks as three
     (forward + head/FP backward | SA backward | Adam) with the two buckets' all-reduces between them, the first one
     asynchronous so that it travels while the second graph replays -- no collective inside a captured region.  Eager steps
@@ -45,7 +53,12 @@ class Trainer:
     also counts the argmax of its logits against the labels into `train_confusion` (util.metric.ConfusionMatrix on the device)
     and adds its loss to a device [sum, count] -- one pn2_confusion_update launch right after the loss, inside whichever graphs
     the step is captured into; `train_metrics()` reads them (the one synchronisation), `reset_metrics()` starts an epoch.
-    `eval_step` is the validation forward (inference mode) + loss + the same counting into `eval_confusion`."""
+    `eval_step` is the validation forward (inference mode) + loss + the same counting into `eval_confusion`.
+
+    Stopping and continuing (what the reference's tf.train.Saver checkpoint holds): `state_dict()` / `save(path)` give the
+    variables, the moving averages, the optimizer slots by variable name and the step count -- which drives the learning-rate
+    staircase, the batch-norm decay, Adam's bias correction and the dropout stream; `load_state_dict(state)` / `load(path)` put
+    them into a fresh trainer (applied when its first batch creates the variables) or, in place, into a live one."""
 
     BETA1, BETA2, EPS = 0.9, 0.999, 1e-8  # tf.train.AdamOptimizer defaults (train.py:381-384)
 
@@ -54,9 +67,11 @@ class Trainer:
         self.hp = dict(hyperparams)
         # schedule / optimizer keys of the reference's semantic.json (train.py:80-119, 380-386); its defaults when absent
         opt = str(self.hp.get("optimizer", "adam")).lower()
-        if opt != "adam":
-            raise ValueError("optimizer %r: only 'adam' (the reference's semantic.json setting, train.py:385-386) is built; "
-                             "the 'momentum' branch of train.py:380-383 is not" % (opt,))
+        if opt not in ("adam", "momentum"):
+            raise ValueError("optimizer %r: 'adam' (the reference's semantic.json setting, train.py:385-386) and 'momentum' "
+                             "(train.py:380-383) are built" % (opt,))
+        self.optimizer = opt
+        self.momentum = float(self.hp.get("momentum", 0.9))
         self.sched = dict(base_lr=float(self.hp.get("learning_rate", 1e-3)), decay_step=int(self.hp.get("decay_step", 200000)),
                           lr_decay_rate=float(self.hp.get("learning_rate_decay_rate", 0.7)),
                           bn_init=float(self.hp.get("bn_init_decay", 0.5)), bn_rate=float(self.hp.get("bn_decay_decay_rate", 0.5)),
@@ -64,7 +79,11 @@ class Trainer:
         self.num_class = num_class
         self.store = store or tf_util.set_default_store(tf_util.VariableStore(device=device, seed=0))
         self.step_count = 0
+        self._steps_run = 0  # steps THIS object has run (= step_count unless a state was loaded): what warmup_eager counts, so
+                             # that a resumed trainer also warms up eagerly before it captures
         self.bucket = None
+        self.flat_p, self.flat_m, self.flat_v, self.flat_accum, self.slots = None, None, None, None, None
+        self._var_slices, self._pending_state = None, None
         self.capture, self.warmup_eager = bool(capture), int(warmup_eager)
         self._graph, self._graph_decay, self._static, self._stream = None, None, None, None
         self._static_geo, self._geo, self._geo_tag, self._geo_event, self._geo_stream = None, None, None, None, None
@@ -116,14 +135,22 @@ class Trainer:
         n = sum(p.numel() for p in params)
         self.flat_p = torch.empty(n, dtype=torch.float32, device=dev)
         off = 0
+        self._var_slices = OrderedDict()  # variable name -> (offset, numel, shape) in flat_p and in every slot buffer
         with torch.no_grad():
-            for p in params:
+            for name, p in zip(names, params):
                 v = self.flat_p[off:off + p.numel()].view_as(p)
                 v.copy_(p)
                 p.data = v
+                self._var_slices[name] = (off, p.numel(), tuple(p.shape))
                 off += p.numel()
-        self.flat_m = torch.zeros_like(self.flat_p)
-        self.flat_v = torch.zeros_like(self.flat_p)
+        # the optimizer's slots, flat like the parameters: Adam's two moments, or momentum's one accumulator
+        if self.optimizer == "adam":
+            self.flat_m = torch.zeros_like(self.flat_p)
+            self.flat_v = torch.zeros_like(self.flat_p)
+            self.slots = OrderedDict([("m", self.flat_m), ("v", self.flat_v)])
+        else:
+            self.flat_accum = torch.zeros_like(self.flat_p)
+            self.slots = OrderedDict([("accum", self.flat_accum)])
         # backward reaches the head and the FP layers first: they are the early bucket (created after layer1..layer4)
         split = next((i for i, k in enumerate(names) if not k.startswith("layer")), len(names))
         self.bucket = pdist.OverlappedGradAllReduce(params, split)
@@ -136,7 +163,9 @@ class Trainer:
         # pn2_adam_step's device-side scalars: [lr_t, beta1, beta2, eps, grad_scale].  Only lr_t changes per step; it is
         # written with a fill whose value travels BY VALUE in the launch (no host buffer a run-ahead host could rewrite
         # before an asynchronous copy has read it: with sync=False the host is several steps ahead of the device).
-        self.hyper = torch.tensor([0.0, self.BETA1, self.BETA2, self.EPS, 1.0 / self.bucket.world()], dtype=torch.float32).to(dev)
+        # pn2_momentum_step's: [lr, momentum, grad_scale], the per-step slot first as well.
+        scalars = [self.BETA1, self.BETA2, self.EPS] if self.optimizer == "adam" else [self.momentum]
+        self.hyper = torch.tensor([0.0] + scalars + [1.0 / self.bucket.world()], dtype=torch.float32).to(dev)
         self._lr_slot = self.hyper[0:1]
         self._world0 = self.bucket.world()  # frozen into grad_scale above: a process group created later would mis-scale
         self._stream = torch.cuda.Stream(device=dev) if dev.type == "cuda" else None
@@ -145,6 +174,11 @@ class Trainer:
             # fixed device buffers: a captured step adds into these addresses on every replay (reset zeroes them in place)
             self.train_confusion = metric.ConfusionMatrix(self.num_class, device=dev)
             self._train_loss_acc = torch.zeros(2, dtype=torch.float64, device=dev)
+        if self._pending_state is not None:
+            # a state loaded before the variables existed: in place of the initial moments and moving averages
+            state, self._pending_state = self._pending_state, None
+            self._check_state(state)
+            self._apply_state(state)
 
     def _learning_rate(self, step, batch_size):
         c = self.sched
@@ -153,6 +187,12 @@ class Trainer:
     def _bn_decay(self, step, batch_size):
         c = self.sched
         return bn_decay(step, batch_size, c["bn_init"], c["decay_step"], c["bn_rate"], c["bn_clip"])
+
+    def _optimizer_lr(self, step, batch_size):
+        """what the lr slot (hyper[0]) holds for 0-based step `step`: Adam's bias-corrected rate of time step `step` + 1, or, for
+        momentum, the plain scheduled rate"""
+        lr = self._learning_rate(step, batch_size)
+        return adam_lr_t(lr, step + 1, self.BETA1, self.BETA2) if self.optimizer == "adam" else lr
 
     # ---- one step ------------------------------------------------------------------------------------------------
     def _forward_backward(self, pc, labels, smpw, decay, geometry=None):
@@ -222,8 +262,13 @@ class Trainer:
         return self.bucket.pack_late_and_bind()
 
     def _adam(self, flat_g):
-        launch("pn2_adam_step", self.flat_p, self.flat_p.numel(), ptr(self.flat_p), ptr(flat_g), ptr(self.flat_m), ptr(self.flat_v),
-               ptr(self.hyper))
+        """the optimizer's apply step (the name is the Adam-only trainer's): ONE launch of the selected entry point"""
+        if self.optimizer == "adam":
+            launch("pn2_adam_step", self.flat_p, self.flat_p.numel(), ptr(self.flat_p), ptr(flat_g), ptr(self.flat_m), ptr(self.flat_v),
+                   ptr(self.hyper))
+        else:
+            launch("pn2_momentum_step", self.flat_p, self.flat_p.numel(), ptr(self.flat_p), ptr(flat_g), ptr(self.flat_accum),
+                   ptr(self.hyper))
 
     def _step_body(self, pc, labels, smpw, decay, geometry=None):
         loss, flat_g = self._forward_backward(pc, labels, smpw, decay, geometry)
@@ -273,7 +318,7 @@ class Trainer:
                 dsts = stg["inputs"] + stg["geo"]
                 if len(srcs) == len(dsts):
                     nxt = self.step_count + 1  # the step this batch is for (0-based), its Adam time step is nxt + 1
-                    lr_t = adam_lr_t(self._learning_rate(nxt, next_pc.shape[0]), nxt + 1, self.BETA1, self.BETA2)
+                    lr_t = self._optimizer_lr(nxt, next_pc.shape[0])
                     fills = [(stg["lr"], lr_t)] + [(t, nxt) for t in stg["steps"]]
                     tf_util.multi_copy_(dsts, srcs, fills=fills)
                     self._staged_tag = (self._tag(next_pc), self._tag(next_labels), self._tag(next_smpw), nxt)
@@ -304,11 +349,9 @@ class Trainer:
         if world != self._world0 and not self.bucket.skip_collectives:
             raise RuntimeError("the process group changed after the trainer's first step (world %d -> %d): the gradient scale "
                                "1/world is part of the optimizer state; build a new Trainer" % (self._world0, world))
-        t = self.step_count + 1
-        lr = self._learning_rate(self.step_count, b)
         decay = self._bn_decay(self.step_count, b)
-        lr_t = adam_lr_t(lr, t, self.BETA1, self.BETA2)
-        use_graph = self.capture and pc.is_cuda and self.step_count >= self.warmup_eager
+        lr_t = self._optimizer_lr(self.step_count, b)  # the eager fill and the fills= between graphs below write this value
+        use_graph = self.capture and pc.is_cuda and self._steps_run >= self.warmup_eager
         split = use_graph and (world > 1 if self.split_capture is None else bool(self.split_capture))
         caller = torch.cuda.current_stream()
         if not use_graph:
@@ -344,6 +387,7 @@ class Trainer:
                         loss = float(loss)
                     caller.wait_stream(self._stream)
                     self.step_count += 1
+                    self._steps_run += 1
                     self.store.train_epoch += 1
                     return float(loss) if sync else loss
                 geo = self._geometry_for(pc, self._stream)  # eager (or eagerly prefetched: prefetch_geometry)
@@ -393,6 +437,7 @@ class Trainer:
                     loss = float(loss)
             caller.wait_stream(self._stream)
         self.step_count += 1
+        self._steps_run += 1
         # A replayed graph updates parameters and moving averages through raw pointers: neither a tensor version counter
         # nor the training-mode layer calls (which only run while capturing) tell the inference-weight cache
         # (VariableStore.folded) that they changed.  Every step does.
@@ -449,6 +494,93 @@ class Trainer:
                 tf_util.multi_copy_(dsts, srcs)
             self._copy_graph, self._staging = gc, stg
         # the capture itself executed nothing: the replay that follows is this step
+
+    # ---- stop and continue -----------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """Everything a stopped run continues from (the content of the reference's tf.train.Saver checkpoint), as CPU tensors and
+        Python scalars:
+          "variables":     store.state_dict() -- parameters and moving averages by variable name;
+          "optimizer":     {"name": "adam" | "momentum", "slots": {"<var>/m", "<var>/v" | "<var>/accum": tensor}} -- TF's
+                           <var>/Adam, <var>/Adam_1 | <var>/Momentum; by variable, so a file does not depend on the flat layout;
+          "step_count":    the number of steps taken;
+          "dropout_seeds": {site: seed word} of every dropout site, so that a store with another seed refuses the state instead
+                           of drawing other masks.
+        The world size (grad_scale) is not part of it.  One synchronisation."""
+        if self.bucket is None:
+            raise RuntimeError("this trainer has no variables yet: they are created by its first batch (train_step / eval_step)")
+
+        def read():
+            variables = {k: v.cpu() for k, v in self.store.state_dict().items()}
+            slots = {}
+            for var, (off, n, shape) in self._var_slices.items():
+                for slot, flat in self.slots.items():
+                    slots["%s/%s" % (var, slot)] = flat[off:off + n].view(shape).cpu()
+            seeds = {str(k): int(t[0]) for k, t in self.store._dropout.items()}
+            return {"variables": variables, "optimizer": {"name": self.optimizer, "slots": slots},
+                    "step_count": int(self.step_count), "dropout_seeds": seeds}
+        return self._on_trainer_stream(read)
+
+    def _check_state(self, state):
+        """ValueError unless `state` fits this trainer: same optimizer, same variables and slots with the same shapes, same
+        dropout seeds.  Called before anything is written."""
+        name = state["optimizer"]["name"]
+        if name != self.optimizer:
+            raise ValueError("the state was saved by optimizer %r, this trainer runs %r" % (name, self.optimizer))
+        have = OrderedDict((k, tuple(v.shape)) for k, v in list(self.store.params.items()) + list(self.store.buffers.items()))
+        for what, want, got in (("variables", have, state["variables"]),
+                                ("optimizer slots", {"%s/%s" % (var, slot): shape for var, (_, _, shape) in self._var_slices.items()
+                                                     for slot in self.slots}, state["optimizer"]["slots"])):
+            if set(want) != set(got):
+                diff = sorted(set(want) ^ set(got))
+                raise ValueError("the state's %s differ from this trainer's: %s%s" % (what, ", ".join(diff[:4]),
+                                                                                     " ..." if len(diff) > 4 else ""))
+            for k, shape in want.items():
+                if tuple(got[k].shape) != shape:
+                    raise ValueError("%s: the state holds shape %s, this trainer %s" % (k, tuple(got[k].shape), shape))
+        seeds = {str(k): int(t[0]) for k, t in self.store._dropout.items()}
+        if {str(k): int(v) for k, v in state["dropout_seeds"].items()} != seeds:
+            raise ValueError("the state's dropout seeds differ from this store's (a VariableStore built with another seed): "
+                             "the continued run would draw other masks")
+
+    def _apply_state(self, state):
+        """copy a checked state into the EXISTING buffers (captured graphs hold their addresses) and set the step count"""
+        dev = self.flat_p.device
+
+        def write():
+            with torch.no_grad():
+                for k, v in state["variables"].items():
+                    self.store.params.get(k, self.store.buffers.get(k)).copy_(v.to(dev))
+                for var, (off, n, shape) in self._var_slices.items():
+                    for slot, flat in self.slots.items():
+                        flat[off:off + n].view(shape).copy_(state["optimizer"]["slots"]["%s/%s" % (var, slot)].to(dev))
+        self._on_trainer_stream(write)
+        self.step_count = int(state["step_count"])
+        self.store.train_epoch += 1  # parameters and moving averages changed under the folded inference weights
+        # a prefetched or staged next batch carries the learning rate and dropout step of the old step count
+        self._geo, self._geo_tag, self._staged_tag = None, None, None
+
+    def load_state_dict(self, state):
+        """Continue from `state` (a state_dict()).  On a trainer that has stepped, everything is copied in place -- no buffer moves,
+        the captured graphs stay valid; the next train_step recaptures by itself only if the batch-norm decay of the new step
+        differs.  On a fresh trainer the state is kept and applied when the first batch has created the variables, in place of
+        their initial moments and moving averages (that call then raises what this one would have).  ValueError, with nothing
+        loaded: another optimizer, other variable names or shapes, other dropout seeds.  The world size may differ."""
+        name = state["optimizer"]["name"]
+        if name != self.optimizer:
+            raise ValueError("the state was saved by optimizer %r, this trainer runs %r" % (name, self.optimizer))
+        if self.bucket is None:
+            self._pending_state = state
+            return
+        self._check_state(state)
+        self._apply_state(state)
+
+    def save(self, path):
+        """torch.save of state_dict(): tensors, strings, ints and floats only"""
+        torch.save(self.state_dict(), path)
+
+    def load(self, path):
+        """load_state_dict of a file written by save()"""
+        self.load_state_dict(torch.load(path, weights_only=True, map_location="cpu"))
 
     # ---- metrics and validation ----------------------------------------------------------------------------------------------
     def _on_trainer_stream(self, fn):
