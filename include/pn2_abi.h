@@ -244,6 +244,17 @@ int pn2_scatter_plan_build(int b, int nent, int div, int nsrc, const int *idx, c
 int pn2_scatter_plan_apply(int b, int nent, int div, int c, int nsrc, const float *rows_in, int in_stride,
                            const void *plan, size_t plan_bytes, float *out, void *stream);
 
+/* pn2_scatter_plan_apply for nplans (<= 4) plans of one batch over the SAME nsrc source points in ONE launch (the scales of a
+ * multi-scale SA module): plan i gathers rows_in[i] (rows in_stride[i] >= c[i] floats apart) into columns [ocol[i], ocol[i] + c[i])
+ * of the shared out (b,nsrc,out_stride).  Every element of those column blocks is written (no zero fill needed), in the plan's
+ * summation order: each block holds the bits pn2_scatter_plan_apply writes for that plan alone; columns outside every block are
+ * left alone.  nent / div / c / ocol / rows_in / in_stride / plan / plan_bytes: host arrays read at call time.  c[i] % 4 == 0,
+ * c[i] <= 1024; ocol[i] % 4 == 0, blocks ascending and disjoint; out_stride % 4 == 0, out 16-byte aligned (PN2_EUNSUP /
+ * PN2_EINVAL otherwise, as pn2_scatter_plan_apply). */
+int pn2_scatter_plan_apply_multi(int nplans, int b, int nsrc, int out_stride, const int *nent, const int *div, const int *c,
+                                 const int *ocol, const float *const *rows_in, const int *in_stride, const void *const *plan,
+                                 const size_t *plan_bytes, float *out, void *stream);
+
 /* n (<= 48) independent device-to-device copies in ONE launch: dst[i][0..bytes[i]) = src[i][0..bytes[i]); the three arrays
  * are host arrays read at call time; regions must not overlap.  Training-step plumbing: a batch's geometry tensors (mixed
  * int32 / float32 / byte buffers) into the static buffers the captured step reads. */
@@ -791,6 +802,23 @@ int pn2_fp_hoist_rows_bn(int b, int n, int m, int c1, int cout, const float *dis
                          const float *z, const float *w1, float *y, void *bn_workspace, size_t workspace_bytes, int finish,
                          const float *gamma, const float *beta, const float *bias, float eps, float decay, float *running_mean,
                          float *running_var, float *save_mean, float *save_invstd, float *scale, float *shift, void *stream);
+/* pn2_sa_hoist_rows_bn for nscales (<= 4) scales of one batch in ONE launch -- the first layers of pointnet_sa_module_msg
+ * (pointnet_util.py:219-282) in training, whose scales all gather from the same cloud:
+ *   y[s] (b,m,nsample[s],cout[s]) = z[b, idx[s], zcol[s] : zcol[s] + cout[s]] + (group_point(xyz, idx[s]) - new_xyz) . w_xyz[s]
+ * z (b,n,z_stride) = points . [Wf_0 | Wf_1 | ...] is ONE product of the caller (pn2_linear), read in place by column block;
+ * gxyz[s] (b,m,nsample[s],3), optional (null table or null entry): the centred coordinates.  The batch statistics of y[s] go to
+ * bn_workspace[s] (ZEROED, workspace_bytes[s] >= pn2_bn_workspace_bytes(cout[s])); finish[s] = 0 / 1 / 2 and the tables gamma ..
+ * shift as the arguments of pn2_sa_hoist_rows_bn (a null table = a table of nulls), eps / decay shared.  Every per-scale argument
+ * is a host array read at call time (as pn2_multi_copy's), so the call may be captured.  y[s] and gxyz[s] are the bits of
+ * pn2_sa_hoist_rows on a dense copy of the scale's columns.  cout[s] % 4 == 0, <= 1024 (PN2_EUNSUP); zcol[s] % 4 == 0,
+ * z_stride % 4 == 0, z / y[s] / w_xyz[s] 16-byte aligned (PN2_EINVAL). */
+int pn2_sa_hoist_rows_multi_bn(int nscales, int b, int n, int m, int z_stride, const float *xyz, const float *new_xyz, const float *z,
+                               const int *nsample, const int *cout, const int *zcol, const int *const *idx,
+                               const float *const *w_xyz, float *const *y, float *const *gxyz, void *const *bn_workspace,
+                               const size_t *workspace_bytes, const int *finish, const float *const *gamma,
+                               const float *const *beta, const float *const *bias, float eps, float decay,
+                               float *const *running_mean, float *const *running_var, float *const *save_mean,
+                               float *const *save_invstd, float *const *scale, float *const *shift, void *stream);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,8 @@ struct HoistParams {
     int m;         // SA: centres per batch element
     const int* idx;        // SA (b, m, nsample), FP (b, n, 3)
     const float* dist;     // FP (b, n, 3) squared distances of three_nn
-    const float* z;        // (b, nsrc, cout)
+    const float* z;        // (b, nsrc, cout); multi-scale: columns [zcol, zcol + cout) of (b, nsrc, 4 * zld), z points at column zcol
+    int zld;               // float4s between two rows of z
     const float* xyz;      // SA (b, nsrc, 3)
     const float* new_xyz;  // SA (b, m, 3)
     const float* points1;  // FP (b, n, ca)
@@ -47,20 +48,25 @@ struct HoistParams {
     Pn2BnFinish fin;
 };
 
-template <bool SA, int CA, bool STATS = false>
-__global__ void __launch_bounds__(256)
-hoist_rows_kernel(HoistParams p) {
-    int bx = blockIdx.x, bi = blockIdx.y;
-    {   // XCD-aware block remap (speed only), as in fp_interp_concat_rows_kernel
-        const unsigned nwg = gridDim.x * gridDim.y;
-        if ((nwg & 7u) == 0u) {
-            const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
-            const unsigned swz = (lin & 7u) * (nwg >> 3) + (lin >> 3);
-            bx = (int)(swz % gridDim.x);
-            bi = (int)(swz / gridDim.x);
-        }
+// XCD-aware block remap (speed only), as in fp_interp_concat_rows_kernel
+__device__ __forceinline__ void hoist_block_remap(int& bx, int& bi) {
+    bx = blockIdx.x; bi = blockIdx.y;
+    const unsigned nwg = gridDim.x * gridDim.y;
+    if ((nwg & 7u) == 0u) {
+        const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
+        const unsigned swz = (lin & 7u) * (nwg >> 3) + (lin >> 3);
+        bx = (int)(swz % gridDim.x);
+        bi = (int)(swz / gridDim.x);
     }
+}
+
+// What one workgroup does: workgroup bx of the gx that share batch element bi; lin / nwg = its index among / the number of the
+// workgroups that feed p.stats_ws (the ticket of pn2_bn_finish).  Shared by the one-scale kernel and the multi-scale one, so that
+// both write the same bits.
+template <bool SA, int CA, bool STATS>
+__device__ __forceinline__ void hoist_rows_body(const HoistParams& p, int bx, int bi, int gx, unsigned lin, unsigned nwg) {
     const int cv = p.cout >> 2;                 // float4 columns
+    const int zld = p.zld;                      // float4s between two rows of z (cv, or more: z is a column block of a wider product)
     const int rp = 256 / cv;                    // rows per pass of the block (cv <= 256)
     const int rr = (int)threadIdx.x / cv, cc = (int)threadIdx.x - rr * cv;
     const bool active = rr < rp;
@@ -68,13 +74,13 @@ hoist_rows_kernel(HoistParams p) {
     double part[2][4];
 #pragma unroll
     for (int v = 0; v < 4; ++v) part[0][v] = part[1][v] = 0.0;
-    const f32x4* __restrict__ z = reinterpret_cast<const f32x4*>(p.z + (size_t)bi * p.nsrc * p.cout);
+    const f32x4* __restrict__ z = reinterpret_cast<const f32x4*>(p.z) + (size_t)bi * p.nsrc * zld;
     f32x4* __restrict__ y = reinterpret_cast<f32x4*>(p.y + (size_t)bi * p.rows * p.cout);
     f32x4 wa[CA > 0 ? CA : 1];
 #pragma unroll
     for (int a = 0; a < CA; ++a) wa[a] = *reinterpret_cast<const f32x4*>(p.wa + (size_t)a * p.cout + cc * 4);
     constexpr int U = 4;  // rows in flight per thread
-    for (int r0 = bx * rp * U + rr; active && r0 < p.rows; r0 += gridDim.x * rp * U) {
+    for (int r0 = bx * rp * U + rr; active && r0 < p.rows; r0 += gx * rp * U) {
         f32x4 acc[U];
         float av[U][CA > 0 ? CA : 1];
         int rows_[U];
@@ -94,7 +100,7 @@ hoist_rows_kernel(HoistParams p) {
             for (int u = 0; u < U; ++u) {
                 const int rc = rows_[u] < p.rows ? rows_[u] : p.rows - 1;
                 const int j = rc / p.nsample;
-                acc[u] = z[(size_t)src[u] * cv + cc];
+                acc[u] = z[(size_t)src[u] * zld + cc];
 #pragma unroll
                 for (int a = 0; a < 3; ++a) av[u][a] = xyz[(size_t)src[u] * 3 + a] - nx[(size_t)j * 3 + a];
             }
@@ -129,7 +135,7 @@ hoist_rows_kernel(HoistParams p) {
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const f32x4 a = z[(size_t)i1[u] * cv + cc], b = z[(size_t)i2[u] * cv + cc], c = z[(size_t)i3[u] * cv + cc];
+                const f32x4 a = z[(size_t)i1[u] * zld + cc], b = z[(size_t)i2[u] * zld + cc], c = z[(size_t)i3[u] * zld + cc];
                 acc[u] = (a * w1[u] + b * w2[u]) + c * w3[u];
                 if (CA == 0 && p.accumulate) acc[u] += y[(size_t)(rows_[u] < p.rows ? rows_[u] : p.rows - 1) * cv + cc];
             }
@@ -178,7 +184,6 @@ hoist_rows_kernel(HoistParams p) {
             __syncthreads();
             sz = h;
         }
-        const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y, nwg = gridDim.x * gridDim.y;
         double* __restrict__ slot = p.stats_ws + kPn2BnHead + (size_t)2 * p.cout * (1 + lin % (unsigned)p.nslots);
         if (active && rr == 0) {
 #pragma unroll
@@ -190,17 +195,52 @@ hoist_rows_kernel(HoistParams p) {
     }
 }
 
-template <bool SA, int CA>
-int launch_hoist(int b, const HoistParams& p, hipStream_t st) {
-    const int cv = p.cout / 4, rp = 256 / cv;
-    long long blocks = ((long long)p.rows + rp * 4 - 1) / (rp * 4);
+template <bool SA, int CA, bool STATS = false>
+__global__ void __launch_bounds__(256)
+hoist_rows_kernel(HoistParams p) {
+    int bx, bi;
+    hoist_block_remap(bx, bi);
+    hoist_rows_body<SA, CA, STATS>(p, bx, bi, (int)gridDim.x, blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y);
+}
+
+// Up to kHoistMaxScales SA scales of one batch (pointnet_sa_module_msg: every scale gathers from the same cloud) in ONE launch:
+// the workgroups [start[s], start[s + 1]) of the x axis work on scale s, each scale with its own workspace, ticket and workgroup
+// count.  z is the shared product points @ [Wf_0 | Wf_1 | ...], read in place by column block (HoistParams::z / zld).
+constexpr int kHoistMaxScales = 4;
+struct HoistMultiParams {
+    HoistParams s[kHoistMaxScales];
+    int start[kHoistMaxScales + 1];
+};
+
+__global__ void __launch_bounds__(256)
+hoist_rows_multi_kernel(HoistMultiParams mp) {
+    int bx, bi;
+    hoist_block_remap(bx, bi);
+    int si = 0;
+#pragma unroll
+    for (int k = 1; k < kHoistMaxScales; ++k) si += bx >= mp.start[k] ? 1 : 0;   // start[k] = the grid width past the last scale
+    const int gx = mp.start[si + 1] - mp.start[si];
+    bx -= mp.start[si];
+    hoist_rows_body<true, 3, true>(mp.s[si], bx, bi, gx, (unsigned)(bx + gx * bi), (unsigned)gx * gridDim.y);
+}
+
+// workgroups per batch element for `rows` output rows of cv float4 columns
+static int hoist_blocks(int b, int rows, int cv, bool stats) {
+    const int rp = 256 / cv;
+    long long blocks = ((long long)rows + rp * 4 - 1) / (rp * 4);
     // ~8 workgroups per CU over the batch; with the statistics epilogue every workgroup ends in 2 * cout fp64 atomics and a ticket:
     // PN2_HOIST_STAT_WGS of them (tools/hoist_stats_ab.py)
-    const int total = p.stats_ws ? PN2_HOIST_STAT_WGS : 2048;
+    const int total = stats ? PN2_HOIST_STAT_WGS : 2048;
     const long long cap = total / (b < 1 ? 1 : b) < 8 ? 8 : total / b;
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     if ((blocks * b) % 8 != 0 && blocks > 8) blocks -= blocks % 8;     // keeps the XCD remap active
+    return (int)blocks;
+}
+
+template <bool SA, int CA>
+int launch_hoist(int b, const HoistParams& p, hipStream_t st) {
+    const int blocks = hoist_blocks(b, p.rows, p.cout / 4, p.stats_ws != nullptr);
     if (p.stats_ws) hoist_rows_kernel<SA, CA, true><<<dim3((unsigned)blocks, b), 256, 0, st>>>(p);
     else hoist_rows_kernel<SA, CA><<<dim3((unsigned)blocks, b), 256, 0, st>>>(p);
     PN2_RETURN_IF_LAUNCH_FAILED();
@@ -243,7 +283,7 @@ static int sa_hoist_impl(int b, int n, int m, int nsample, int cout, const float
     if ((long long)m * nsample > 0x7fffffffLL || b > 65535) return PN2_ERANGE;
     HoistParams p = {};
     p.rows = m * nsample; p.nsrc = n; p.cout = cout; p.ca = 3; p.nsample = nsample; p.m = m;
-    p.idx = idx; p.z = z; p.xyz = xyz; p.new_xyz = new_xyz; p.wa = w_xyz; p.y = y; p.gxyz = gxyz;
+    p.idx = idx; p.z = z; p.zld = cout / 4; p.xyz = xyz; p.new_xyz = new_xyz; p.wa = w_xyz; p.y = y; p.gxyz = gxyz;
     if (st_args) { p.stats_ws = st_args->stats_ws; p.nslots = st_args->nslots; p.fin = st_args->fin; }
     return launch_hoist<true, 3>(b, p, static_cast<hipStream_t>(stream));
 }
@@ -269,6 +309,53 @@ extern "C" int pn2_sa_hoist_rows_bn(int b, int n, int m, int nsample, int cout, 
     return sa_hoist_impl(b, n, m, nsample, cout, xyz, new_xyz, idx, z, w_xyz, y, gxyz, stream, &sp);
 }
 
+// pn2_sa_hoist_rows_bn for nscales <= 4 scales of one batch in ONE launch (the first layers of pointnet_sa_module_msg in training):
+// scale s gathers columns [zcol[s], zcol[s] + cout[s]) of the shared z (b, n, z_stride) = points @ [Wf_0 | Wf_1 | ...] in place.
+// The per-scale arguments are host arrays read here, at call time (as pn2_multi_copy's): the call is capturable.  A null table of
+// optional pointers (gxyz, gamma .. shift) stands for a table of nulls.  Same float expressions -- the same device function -- as
+// the one-scale kernel: y and gxyz are its bits.
+extern "C" int pn2_sa_hoist_rows_multi_bn(int nscales, int b, int n, int m, int z_stride, const float* xyz, const float* new_xyz,
+                                          const float* z, const int* nsample, const int* cout, const int* zcol, const int* const* idx,
+                                          const float* const* w_xyz, float* const* y, float* const* gxyz, void* const* bn_workspace,
+                                          const size_t* workspace_bytes, const int* finish, const float* const* gamma,
+                                          const float* const* beta, const float* const* bias, float eps, float decay,
+                                          float* const* running_mean, float* const* running_var, float* const* save_mean,
+                                          float* const* save_invstd, float* const* scale, float* const* shift, void* stream) {
+    if (nscales <= 0 || nscales > kHoistMaxScales || b <= 0 || n <= 0 || m <= 0 || z_stride <= 0) return PN2_EINVAL;
+    if (!nsample || !cout || !zcol || !idx || !w_xyz || !y || !bn_workspace || !workspace_bytes || !finish) return PN2_ENULL;
+    for (int s = 0; s < nscales; ++s) {
+        if (nsample[s] <= 0 || cout[s] <= 0 || zcol[s] < 0) return PN2_EINVAL;
+        if (cout[s] % 4 != 0 || cout[s] > 1024) return PN2_EUNSUP;
+        if (zcol[s] % 4 != 0 || (long long)zcol[s] + cout[s] > z_stride) return PN2_EINVAL;
+        if ((long long)m * nsample[s] > 0x7fffffffLL) return PN2_ERANGE;
+    }
+    if (!xyz || !new_xyz || !z) return PN2_ENULL;
+    if (z_stride % 4 != 0 || ((uintptr_t)z % 16) != 0) return PN2_EINVAL;
+    if (b > 65535) return PN2_ERANGE;
+    HoistMultiParams mp = {};
+    long long total = 0;
+    for (int s = 0; s < nscales; ++s) {
+        if (!idx[s] || !w_xyz[s] || !y[s]) return PN2_ENULL;
+        if ((((uintptr_t)y[s] | (uintptr_t)w_xyz[s]) % 16) != 0) return PN2_EINVAL;
+        HoistParams& p = mp.s[s];
+        const int rc = hoist_stats_args(p, (long long)b * m * nsample[s], cout[s], bn_workspace[s], workspace_bytes[s], finish[s],
+                                        gamma ? gamma[s] : nullptr, beta ? beta[s] : nullptr, bias ? bias[s] : nullptr, eps, decay,
+                                        running_mean ? running_mean[s] : nullptr, running_var ? running_var[s] : nullptr,
+                                        save_mean ? save_mean[s] : nullptr, save_invstd ? save_invstd[s] : nullptr,
+                                        scale ? scale[s] : nullptr, shift ? shift[s] : nullptr);
+        if (rc != PN2_OK) return rc;
+        p.rows = m * nsample[s]; p.nsrc = n; p.cout = cout[s]; p.ca = 3; p.nsample = nsample[s]; p.m = m;
+        p.idx = idx[s]; p.z = z + zcol[s]; p.zld = z_stride / 4; p.xyz = xyz; p.new_xyz = new_xyz; p.wa = w_xyz[s]; p.y = y[s];
+        p.gxyz = gxyz ? gxyz[s] : nullptr;
+        mp.start[s] = (int)total;
+        total += hoist_blocks(b, p.rows, p.cout / 4, true);
+    }
+    for (int s = nscales; s <= kHoistMaxScales; ++s) mp.start[s] = (int)total;
+    hoist_rows_multi_kernel<<<dim3((unsigned)total, b), 256, 0, static_cast<hipStream_t>(stream)>>>(mp);
+    PN2_RETURN_IF_LAUNCH_FAILED();
+    return PN2_OK;
+}
+
 // FP: y (b, n, cout) = three_interpolate(z, idx, w(dist)) + points1 (b, n, c1) @ w1 (c1, cout) with z (b, m, cout) =
 // points2 @ W[:c2] computed by the caller; the weights are formed from three_nn's squared distances as in
 // pn2_fp_interp_concat.  1 <= c1 <= 8: the product with points1 is formed here (the level-0 module: colours).
@@ -284,7 +371,7 @@ static int fp_hoist_impl(int b, int n, int m, int c1, int cout, const float* dis
     if ((long long)n * 3 > 0x7fffffffLL || b > 65535) return PN2_ERANGE;
     HoistParams p = {};
     p.rows = n; p.nsrc = m; p.cout = cout; p.ca = c1;
-    p.idx = idx; p.dist = dist; p.z = z; p.points1 = points1; p.wa = w1; p.y = y;
+    p.idx = idx; p.dist = dist; p.z = z; p.zld = cout / 4; p.points1 = points1; p.wa = w1; p.y = y;
     p.accumulate = c1 == 0;
     if (st_args) { p.stats_ws = st_args->stats_ws; p.nslots = st_args->nslots; p.fin = st_args->fin; }
     hipStream_t st = static_cast<hipStream_t>(stream);

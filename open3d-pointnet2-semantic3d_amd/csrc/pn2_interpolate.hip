@@ -163,16 +163,17 @@ ti_csr_fill_kernel(int n3, int m, int div, const int* __restrict__ idx_all, cons
 // Input rows are `stride` floats apart (>= c: the caller may hand over a column slice of a wider gradient in place);
 // ALIGNED = every row starts on a 16-byte boundary, else the 16-byte loads are issued as 4-byte-aligned ones.
 typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
+// (the body of the gather: workgroup bx of batch element bi; the result row s goes to grad_points_all + (bi * m + s) * ostride --
+//  ostride = c, or more: a column block of a wider tensor.  Shared by the one-plan kernel and the multi-plan one: the same bits.)
 template <bool ALIGNED>
-__global__ void __launch_bounds__(256)
-ti_csr_gather_kernel(int n, int n3, int c, int stride, int m, const float* __restrict__ grad_out_all, const int* __restrict__ off_all,
-                     const int* __restrict__ ent_q_all, const float* __restrict__ ent_w_all,
-                     float* __restrict__ grad_points_all) {
+__device__ __forceinline__ void ti_csr_gather_body(int bx, int bi, int n, int n3, int c, int stride, int m,
+                                                   const float* __restrict__ grad_out_all, const int* __restrict__ off_all,
+                                                   const int* __restrict__ ent_q_all, const float* __restrict__ ent_w_all,
+                                                   float* __restrict__ grad_points_all, int ostride) {
     const int cv = c >> 2;
     const int spb = 256 / cv;  // sources per block (host guarantees cv <= 256)
     const int slot = (int)threadIdx.x / cv, col = (int)threadIdx.x - slot * cv;
-    const int bi = blockIdx.y;
-    const int s = blockIdx.x * spb + slot;
+    const int s = bx * spb + slot;
     if (slot >= spb || s >= m) return;
     const float* __restrict__ gbase = grad_out_all + (size_t)bi * n * stride + 4 * col;
     auto row4 = [&](int q) -> f32x4 {
@@ -203,7 +204,16 @@ ti_csr_gather_kernel(int n, int n3, int c, int stride, int m, const float* __res
         acc.x = __builtin_fmaf(g.x, w, acc.x); acc.y = __builtin_fmaf(g.y, w, acc.y);
         acc.z = __builtin_fmaf(g.z, w, acc.z); acc.w = __builtin_fmaf(g.w, w, acc.w);
     }
-    reinterpret_cast<f32x4*>(grad_points_all + ((size_t)bi * m + s) * c)[col] = acc;
+    reinterpret_cast<f32x4*>(grad_points_all + ((size_t)bi * m + s) * ostride)[col] = acc;
+}
+
+template <bool ALIGNED>
+__global__ void __launch_bounds__(256)
+ti_csr_gather_kernel(int n, int n3, int c, int stride, int m, const float* __restrict__ grad_out_all, const int* __restrict__ off_all,
+                     const int* __restrict__ ent_q_all, const float* __restrict__ ent_w_all,
+                     float* __restrict__ grad_points_all) {
+    ti_csr_gather_body<ALIGNED>((int)blockIdx.x, (int)blockIdx.y, n, n3, c, stride, m, grad_out_all, off_all, ent_q_all, ent_w_all,
+                                grad_points_all, c);
 }
 
 // Fused FP front end: inverse-distance weights (pointnet_util.py:300-303) +
@@ -760,6 +770,81 @@ extern "C" int pn2_scatter_plan_apply(int b, int nent, int div, int c, int nsrc,
     const bool aligned = ((uintptr_t)rows_in % 16) == 0 && in_stride % 4 == 0;
     if (aligned) ti_csr_gather_kernel<true><<<gg, 256, 0, st>>>(nent / div, nent, c, in_stride, nsrc, rows_in, off, ent_q, ent_w, out);
     else ti_csr_gather_kernel<false><<<gg, 256, 0, st>>>(nent / div, nent, c, in_stride, nsrc, rows_in, off, ent_q, ent_w, out);
+    PN2_RETURN_IF_LAUNCH_FAILED();
+    return PN2_OK;
+}
+
+// ---- several plans applied in one launch ----------------------------------------------------------------------------------
+// The scales of a multi-scale SA module gather from ONE source cloud: their gradients are column blocks of one (b, nsrc, out_stride)
+// tensor (the operand of ONE data-gradient GEMM over the concatenated weights).  The workgroups [start[i], start[i + 1]) of the x
+// axis apply plan i; every element of a block is written, in the plan's order: the bits of pn2_scatter_plan_apply.
+constexpr int kMaxApplyPlans = 4;
+struct ApplyDesc {
+    int n, n3, c, stride, aligned;
+    const float* rows_in;
+    const int* off;
+    const int* eq;
+    const float* ew;
+    float* out;   // the shared output + this plan's first column
+};
+struct ApplyBatch {
+    ApplyDesc d[kMaxApplyPlans];
+    int start[kMaxApplyPlans + 1];
+    int nsrc, ostride;
+};
+
+__global__ void __launch_bounds__(256)
+ti_csr_gather_multi_kernel(ApplyBatch ab) {
+    const int bx0 = blockIdx.x;
+    int pi = 0;
+#pragma unroll
+    for (int k = 1; k < kMaxApplyPlans; ++k) pi += bx0 >= ab.start[k] ? 1 : 0;   // start[k] = the grid width past the last plan
+    const ApplyDesc& d = ab.d[pi];
+    const int bx = bx0 - ab.start[pi];
+    if (d.aligned) ti_csr_gather_body<true>(bx, (int)blockIdx.y, d.n, d.n3, d.c, d.stride, ab.nsrc, d.rows_in, d.off, d.eq, d.ew, d.out, ab.ostride);
+    else ti_csr_gather_body<false>(bx, (int)blockIdx.y, d.n, d.n3, d.c, d.stride, ab.nsrc, d.rows_in, d.off, d.eq, d.ew, d.out, ab.ostride);
+}
+
+// pn2_scatter_plan_apply for nplans <= 4 plans of one batch over the same nsrc source points in ONE launch: plan i gathers
+// rows_in[i] (rows in_stride[i] floats apart, c[i] columns) into columns [ocol[i], ocol[i] + c[i]) of out (b, nsrc, out_stride).
+// Blocks ascending and disjoint; columns of out outside every block are left alone.  Host arrays read at call time.
+extern "C" int pn2_scatter_plan_apply_multi(int nplans, int b, int nsrc, int out_stride, const int* nent, const int* div, const int* c,
+                                            const int* ocol, const float* const* rows_in, const int* in_stride,
+                                            const void* const* plan, const size_t* plan_bytes, float* out, void* stream) {
+    if (nplans <= 0 || nplans > kMaxApplyPlans || b <= 0 || nsrc <= 0 || out_stride <= 0) return PN2_EINVAL;
+    if (!nent || !div || !c || !ocol || !rows_in || !in_stride || !plan || !plan_bytes) return PN2_ENULL;
+    int end = 0;
+    for (int i = 0; i < nplans; ++i) {
+        if (nent[i] <= 0 || div[i] <= 0 || nent[i] % div[i] != 0 || c[i] <= 0 || in_stride[i] < c[i]) return PN2_EINVAL;
+        if (c[i] % 4 != 0 || c[i] > 1024) return PN2_EUNSUP;
+        if (ocol[i] % 4 != 0 || ocol[i] < end || (long long)ocol[i] + c[i] > out_stride) return PN2_EINVAL;
+        end = ocol[i] + c[i];
+    }
+    if (!out) return PN2_ENULL;
+    if (out_stride % 4 != 0 || ((uintptr_t)out % 16) != 0) return PN2_EUNSUP;
+    if (b > 65535) return PN2_ERANGE;
+    ApplyBatch ab{};
+    ab.nsrc = nsrc; ab.ostride = out_stride;
+    long long total = 0;
+    for (int i = 0; i < nplans; ++i) {
+        if (!rows_in[i] || !plan[i]) return PN2_ENULL;
+        if (((uintptr_t)rows_in[i] % 4) != 0) return PN2_EUNSUP;
+        if (plan_bytes[i] < pn2_scatter_plan_bytes(b, nent[i], nsrc) || ((uintptr_t)plan[i] % 4) != 0) return PN2_EINVAL;
+        ApplyDesc& d = ab.d[i];
+        d.n = nent[i] / div[i]; d.n3 = nent[i]; d.c = c[i]; d.stride = in_stride[i];
+        d.aligned = ((uintptr_t)rows_in[i] % 16) == 0 && in_stride[i] % 4 == 0;
+        d.rows_in = rows_in[i];
+        d.off = static_cast<const int*>(plan[i]) + (size_t)b * nsrc;
+        d.eq = d.off + (size_t)b * nsrc;
+        d.ew = reinterpret_cast<const float*>(d.eq + (size_t)b * nent[i]);
+        d.out = out + ocol[i];
+        const int spb = 256 / (c[i] / 4);
+        ab.start[i] = (int)total;
+        total += (nsrc + spb - 1) / spb;
+    }
+    for (int i = nplans; i <= kMaxApplyPlans; ++i) ab.start[i] = (int)total;
+    if (total > 0x7fffffffLL) return PN2_ERANGE;
+    ti_csr_gather_multi_kernel<<<dim3((unsigned)total, b), 256, 0, static_cast<hipStream_t>(stream)>>>(ab);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

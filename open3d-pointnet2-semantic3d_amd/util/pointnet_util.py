@@ -527,24 +527,78 @@ def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_al
         return new_xyz, new_points, idx
 
 
+def msg_geometry(xyz, npoint, radius_list, nsample_list, plans=True):
+    """The feature-independent half of pointnet_sa_module_msg -- one FPS (with its tie record tagged on new_xyz), one ball query
+    for all radii (query_ball_point_multi) and, plans=True, the scatter plans of every scale's grouping gradient in one
+    scatter_plans call -- for pointnet_sa_module_msg(..., geometry=...): what model.compute_geometry does per SSG level.  Depends
+    on coordinates only, so it can run on a side stream ahead of the step.
+    -> (new_xyz (B,npoint,3), [idx_s (B,npoint,nsample_s)], [plan_s or None])"""
+    require_cuda(xyz)
+    xyz = xyz.contiguous()
+    fps_idx, fps_tie, _ = farthest_point_sample_with_ties(npoint, xyz)
+    new_xyz = tag_fps_output(gather_point(xyz, fps_idx), fps_tie)
+    idxs = [q[0] for q in query_ball_point_multi(radius_list, nsample_list, xyz, new_xyz)]
+    built = scatter_plans([(idx, xyz.shape[1], None, None) for idx in idxs]) if plans else [None] * len(idxs)
+    return new_xyz, idxs, built
+
+
 def pointnet_sa_module_msg(xyz, points, npoint, radius_list, nsample_list, mlp_list, is_training, bn_decay, scope,
-                           bn=True, use_xyz=True, use_nchw=False, new_xyz=None):
+                           bn=True, use_xyz=True, use_nchw=False, new_xyz=None, geometry=None):
     """Multi-scale grouping SA module (:219-282): one FPS, per scale ball query +
     group + MLP + max; NOTE the concat order here is [features, xyz] (:259), unlike
     sample_and_group.  -> new_xyz, new_points (B,npoint,sum mlp[k][-1]).
     new_xyz (extension): the npoint samples of this very cloud, drawn ahead (runtime.StaggeredPipeline runs a batch's sampling as
-    a graph of its own); everything else is done here."""
+    a graph of its own); everything else is done here.
+    geometry (extension) = msg_geometry(xyz, npoint, radius_list, nsample_list): samples, ball queries and scatter plans computed
+    ahead; nothing geometric runs here.  In training, with bn and use_xyz, float32 points of >= 16 channels, at most 4 scales,
+    every mlp_list[s][0] % 4 == 0 and the plans given, the first layers of all scales run hoisted on the source points
+    (tf_util._TrainHoistedMsgBnRelu: one GEMM, one gather launch, one scatter and one pair of gradient GEMMs for all scales) and
+    the max over K rides in each scale's last batch-norm kernel.  Anything else -- more than 4 scales included: they are NOT
+    split into chunks -- uses the given new_xyz / idx on the path below."""
     require_cuda(xyz, points)
     with tf_util.variable_scope(scope):
         xyz = xyz.contiguous()
+        queries = None
+        if geometry is not None:
+            if new_xyz is not None:
+                raise ValueError("pass the samples either as new_xyz or inside geometry, not both")
+            new_xyz, g_idx = geometry[0], geometry[1]
+            g_plans = geometry[2] if len(geometry) > 2 and geometry[2] is not None else [None] * len(g_idx)
+            if len(g_idx) != len(radius_list) or len(g_plans) != len(g_idx):
+                raise ValueError("geometry: one idx (and one plan or None) per scale expected")
+            for idx, nsample in zip(g_idx, nsample_list):
+                if tuple(idx.shape) != (xyz.shape[0], int(npoint), int(nsample)):
+                    raise ValueError("geometry: idx of shape (batch_size, npoint, nsample) expected per scale")
+            queries = [(idx, None) for idx in g_idx]
         if new_xyz is None:
             fps_idx, fps_tie, _ = farthest_point_sample_with_ties(npoint, xyz)  # (:36-37; the tie record rides on new_xyz, see
             new_xyz = tag_fps_output(gather_point(xyz, fps_idx), fps_tie)         #  tf_sampling.USE_NESTED_FPS)
         elif tuple(new_xyz.shape) != (xyz.shape[0], int(npoint), 3):
             raise ValueError("new_xyz: (batch_size, npoint, 3) samples of xyz expected")
         outs = []
+        if (geometry is not None and bool(is_training) and tf_util.USE_HOISTED_MSG_TRAIN and bn and use_xyz and points is not None
+                and points.dtype == torch.float32 and points.shape[2] >= 16 and len(mlp_list) <= tf_util.MSG_HOIST_MAX_SCALES
+                and all(len(mlp) > 0 and mlp[0] % 4 == 0 and _plan_usable(pl, mlp[0]) for mlp, pl in zip(mlp_list, g_plans))
+                and all(k <= 1024 for k in nsample_list)):
+            # ---- training, geometry + plans computed ahead: all scales' first layers hoisted together ----
+            rows = [g_idx[i].numel() for i in range(len(mlp_list))]
+            defer = lambda i, j: (j + 1 < len(mlp_list[i])  # noqa: E731
+                                  and tf_util.can_defer_bn(rows[i], mlp_list[i][j], mlp_list[i][j + 1]))
+            firsts = tf_util.conv2d_hoisted_first_msg(
+                points, xyz, new_xyz, g_idx, g_plans, [mlp[0] for mlp in mlp_list], ["conv%d_0" % i for i in range(len(mlp_list))],
+                bn_decay, pools=[nsample_list[i] if len(mlp) == 1 else 0 for i, mlp in enumerate(mlp_list)],
+                defer_bn=[defer(i, 0) for i in range(len(mlp_list))])
+            for i, mlp in enumerate(mlp_list):
+                grouped_points = firsts[i]
+                for j in range(1, len(mlp)):
+                    grouped_points = tf_util.conv2d(grouped_points, mlp[j], [1, 1], padding="VALID", stride=[1, 1], bn=True,
+                                                    is_training=is_training, scope="conv%d_%d" % (i, j), bn_decay=bn_decay,
+                                                    pool=nsample_list[i] if j == len(mlp) - 1 else 0, defer_bn=defer(i, j))
+                outs.append(grouped_points.squeeze(2))
+            return new_xyz, torch.cat(outs, dim=-1)
         # one scan of xyz for all radii (the reference re-scans once per radius, :245-250)
-        queries = query_ball_point_multi(radius_list, nsample_list, xyz, new_xyz)
+        if queries is None:
+            queries = query_ball_point_multi(radius_list, nsample_list, xyz, new_xyz)
         for i, (radius, nsample) in enumerate(zip(radius_list, nsample_list)):
             idx = queries[i][0]
             if (not is_training) and USE_FUSED_SA and (use_xyz or points is None):

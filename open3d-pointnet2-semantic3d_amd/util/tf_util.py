@@ -1264,6 +1264,141 @@ def conv2d_hoisted_first(kind, src, geo, plan, cin, num_output_channels, scope, 
     return z.reshape(src.shape[0], geo[2].shape[1], 1, cout)
 
 
+USE_HOISTED_MSG_TRAIN = True  # pointnet_sa_module_msg(geometry=...) in training: all scales' first layers hoisted together (A/B, tests)
+MSG_HOIST_MAX_SCALES = 4      # scales one pn2_sa_hoist_rows_multi_bn / pn2_scatter_plan_apply_multi launch takes
+_MSG_PER = 8                  # tensors per scale in _TrainHoistedMsgBnRelu's argument list
+
+
+class _TrainHoistedMsgBnRelu(torch.autograd.Function):
+    """The first layers of ALL scales of pointnet_sa_module_msg (pointnet_util.py:219-282), training path, hoisted together: every
+    scale gathers from the same source cloud, so the feature halves of their first 1x1 convs are ONE GEMM of the n source rows
+    against the column-concatenated weights,
+        z = points @ [Wf_0 | Wf_1 | ...],     y_s = z[idx_s, its columns] + (group_point(xyz, idx_s) - new_xyz) @ Wx_s
+    (one pn2_linear, one pn2_sa_hoist_rows_multi_bn that also takes every scale's batch statistics), then per scale batch norm +
+    ReLU (+ max over K, or deferred) as in _TrainHoistedBnRelu.  The variables keep the reference's [features | xyz] row order
+    (:259): Wf_s = w_s[:C], Wx_s = w_s[C:].  Backward: dy_s from the batch-norm kernels; ONE pn2_scatter_plan_apply_multi into the
+    shared dz (b, n, sum cout); d(points) = dz @ Wf_all^T -- the GEMM's reduction adds the scales' contributions --; ONE weight
+    gradient points^T dz whose column blocks are the feature rows of the variables' gradients; dWx_s = gxyz_s^T dy_s.
+    Arguments after `defers`: per scale (w (C + 3, cout), b, gamma, beta, running_mean, running_var, idx, plan).
+    -> one tensor per scale: (b * m * K_s, cout_s), or (b * m, cout_s) behind the fused max (pools[s] = K_s > 1)."""
+
+    @staticmethod
+    def forward(ctx, src, xyz, new_xyz, decay, pools, defers, *per):
+        nsc = len(pools)
+        bsz, nsrc, c = src.shape
+        src2d = src.reshape(-1, c)
+        ws_, bs_, gammas, betas, rms, rvs, idxs, plans = (per[k::_MSG_PER] for k in range(_MSG_PER))
+        m = idxs[0].shape[1]
+        ks = [int(i.shape[2]) for i in idxs]
+        couts = [int(w.shape[1]) for w in ws_]
+        cols = [sum(couts[:s]) for s in range(nsc)]
+        wf_all = torch.cat([w[:c] for w in ws_], dim=1) if nsc > 1 else ws_[0][:c].contiguous()
+        z = hip_matmul(src2d, wf_all)  # (b * nsrc, sum cout)
+        needs = any(ctx.needs_input_grad)
+        defers = [bool(d) and not pools[s] and needs for s, d in enumerate(defers)]  # as _TrainDenseBnRelu
+        fin = bool(USE_BN_FINISH_IN_PRODUCER)
+        finish = [(2 if d else 1) if fin else 0 for d in defers]
+        ys = [torch.empty((bsz * m * k, co), dtype=torch.float32, device=src.device) for k, co in zip(ks, couts)]
+        gx = [torch.empty((bsz * m * k, 3), dtype=torch.float32, device=src.device) for k in ks]
+        wss = [_bn_zeroed_scratch(co, src.device) for co in couts]
+        consts = [_bn_consts_out(co, src.device) if f == 2 else (None, None, None, None) for co, f in zip(couts, finish)]
+        wxs = [w[c:] for w in ws_]
+        launch("pn2_sa_hoist_rows_multi_bn", src, nsc, bsz, nsrc, m, z.shape[1], ptr(xyz), ptr(new_xyz), ptr(z), int_array(ks),
+               int_array(couts), int_array(cols), ptr_table(idxs), ptr_table(wxs), ptr_table(ys), ptr_table(gx), ptr_table(wss),
+               u64_array([nbytes(w_) for w_ in wss]), int_array(finish), ptr_table(gammas), ptr_table(betas), ptr_table(bs_),
+               BN_EPSILON, float(decay), ptr_table(rms), ptr_table(rvs), *(ptr_table([cs[k] for cs in consts]) for k in range(4)))
+        outs, saved, links = [], [src2d, wf_all], []
+        for s in range(nsc):
+            y, pool = ys[s], int(pools[s])
+            if defers[s]:
+                if finish[s] == 2:
+                    save_mean, save_invstd, sc, sh = consts[s]
+                else:
+                    save_mean, save_invstd, sc, sh = _bn_train_forward_deferred(y, bs_[s], gammas[s], betas[s], rms[s], rvs[s], decay,
+                                                                                wss[s])
+                saved += [ws_[s], y, gammas[s], betas[s], save_mean, save_invstd, gx[s], plans[s]]
+                lk = _bn_register_producer(y, y, gammas[s], betas[s], save_mean, save_invstd, True, False, sc, sh)
+                if lk is None:
+                    raise RuntimeError("deferred batch norm needs the producer links (USE_DGRAD_BN_STATS)")
+                outs.append(y)
+            else:
+                zact, ties, save_mean, save_invstd = _bn_train_forward(y, bs_[s], gammas[s], betas[s], rms[s], rvs[s], decay, True,
+                                                                       pool, wss[s], folded=fin)
+                saved += [ws_[s], y, gammas[s], betas[s], save_mean, save_invstd, gx[s], plans[s]]
+                if pool > 1:
+                    saved += [zact, ties]
+                lk = _bn_register_producer(zact, y, gammas[s], betas[s], save_mean, save_invstd, True, pool > 1)
+                outs.append(zact)
+            links.append(lk)
+        ctx.save_for_backward(*saved)
+        ctx.links, ctx.pools, ctx.dims, ctx.cols = links, [int(p) for p in pools], (bsz, nsrc, m, c), cols
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *dzs):
+        saved = ctx.saved_tensors
+        src2d, wf_all = saved[:2]
+        bsz, nsrc, m, c = ctx.dims
+        nsc, pos = len(ctx.pools), 2
+        ws_, dys, gxs, plans, out_grads = [], [], [], [], []
+        for s in range(nsc):
+            w, y, gamma, beta, save_mean, save_invstd, a, plan = saved[pos:pos + 8]
+            pos += 8
+            zmax, ties = None, None
+            if ctx.pools[s] > 1:
+                zmax, ties = saved[pos:pos + 2]
+                pos += 2
+            dy, dgamma, dbeta = _bn_train_backward(dzs[s], y, gamma, beta, save_mean, save_invstd, True, ctx.pools[s], zmax, ties,
+                                                   ctx.links[s])
+            ws_.append(w); dys.append(dy); gxs.append(a); plans.append(plan)
+            out_grads.append([None, None, dgamma, dbeta, None, None, None, None])
+        couts = [int(w.shape[1]) for w in ws_]
+        total = wf_all.shape[1]
+        dzall = torch.empty((bsz, nsrc, total), dtype=torch.float32, device=src2d.device)
+        launch("pn2_scatter_plan_apply_multi", dzall, nsc, bsz, nsrc, total, int_array([dy.shape[0] // bsz for dy in dys]),
+               int_array([1] * nsc), int_array(couts), int_array(ctx.cols), ptr_table(dys), int_array(couts), ptr_table(plans),
+               u64_array([p.numel() for p in plans]), ptr(dzall))
+        dz2d = dzall.view(-1, total)
+        dsrc = hip_linear_dgrad(dz2d, wf_all).view(bsz, nsrc, c) if ctx.needs_input_grad[0] else None
+        if any(ctx.needs_input_grad[6 + _MSG_PER * s] for s in range(nsc)):
+            dwf = torch.empty((c, total), dtype=torch.float32, device=src2d.device)
+            launch("pn2_linear_wgrad", dz2d, src2d.shape[0], c, total, ptr(src2d), ptr(dz2d), ptr(dwf))
+            for s in range(nsc):
+                dw = _wgrad_out(ws_[s])
+                dw[:c].copy_(dwf[:, ctx.cols[s]:ctx.cols[s] + couts[s]])  # the column block -> the feature rows of the variable's gradient
+                _hip_wgrad_into(gxs[s], dys[s], dw[c:])
+                out_grads[s][0] = dw
+        return (dsrc, None, None, None, None, None) + tuple(g for og in out_grads for g in og)
+
+
+def conv2d_hoisted_first_msg(points, xyz, new_xyz, idxs, plans, num_output_channels, scopes, bn_decay=None, pools=None,
+                             defer_bn=None):
+    """conv2d(concat[group_point(points, idx_s) | grouped_xyz_s - new_xyz], ..., bn=True, is_training=True, relu) for every scale
+    s of pointnet_sa_module_msg at once, without building the grouped tensors: _TrainHoistedMsgBnRelu.  Same variables (names,
+    shapes, [features | xyz] row order, initialisation) as tf_util.conv2d under scopes[s]; pools[s] = nsample for a one-layer
+    scale (the max over K is fused), else 0; defer_bn[s]: hand the un-normalised output to the scale's next conv2d.
+    -> [(b, m, nsample_s or 1, cout_s)]"""
+    nsc = len(idxs)
+    if not 1 <= nsc <= MSG_HOIST_MAX_SCALES:
+        raise ValueError("conv2d_hoisted_first_msg takes 1..%d scales" % MSG_HOIST_MAX_SCALES)
+    cin = points.shape[2] + 3
+    decay = 0.9 if bn_decay is None else float(bn_decay)
+    pools = [int(p) if p and p > 1 else 0 for p in (pools or [0] * nsc)]
+    defers = [bool(d) and not pools[s] and torch.is_grad_enabled() for s, d in enumerate(defer_bn or [False] * nsc)]
+    per = []
+    for s in range(nsc):
+        cout = int(num_output_channels[s])
+        with variable_scope(scopes[s]):
+            st, w, b, bnv = _dense_variables(cin, cout, True, (1, 1, cin, cout))
+            st.train_epoch += 1
+            beta, gamma, mean, var = bnv
+        per += [w.reshape(cin, cout), b, gamma, beta, mean, var, idxs[s].contiguous(), plans[s]]
+    outs = _TrainHoistedMsgBnRelu.apply(points.contiguous(), xyz.detach().contiguous(), new_xyz.detach().contiguous(), decay,
+                                        tuple(pools), tuple(defers), *per)
+    b, m = points.shape[0], idxs[0].shape[1]
+    return [o.reshape(b, m, 1 if pools[s] else idxs[s].shape[2], int(num_output_channels[s])) for s, o in enumerate(outs)]
+
+
 def _train_layer(inputs, w2d, b, bnv, bn_decay, relu, pool=0, defer=False):
     """One dense layer of the training path, entirely on the HIP library: inputs (..., cin) -> (..., cout); pool > 1 also
     takes the max over groups of `pool` consecutive entries of the second-to-last axis (..., W, cin) -> (..., W/pool, cout).
