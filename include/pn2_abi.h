@@ -16,9 +16,13 @@
  *
  * Conventions: all tensors dense row-major contiguous DEVICE memory; float =
  * IEEE fp32; indices int32.  The caller owns every buffer (outputs and scratch);
- * the library never allocates, never synchronises, keeps no pointers and has no mutable global state (the kernel-
- * selection knobs of the A/B scripts exist only in a -DPN2_TUNING_HOOKS build, csrc/pn2_common.h).
- * Re-entrant; safe from several host threads on different streams.
+ * the library never allocates, never synchronises and keeps no pointers.  Its only mutable global state besides the
+ * documented switch pn2_set_sa_row_packing: per kernel that needs more than 64 KiB of dynamic LDS, an atomic set of the
+ * devices on which that kernel's LDS limit has been raised (pn2_allow_lds, csrc/pn2_common.h).  Raising the limit is
+ * idempotent and the set is safe from several host threads and several devices.  (The kernel-selection knobs of the A/B
+ * scripts exist only in a -DPN2_TUNING_HOOKS build.)
+ * Re-entrant; safe from several host threads on different streams, and on any device of the process: an entry point runs
+ * on the caller's current device, which must be the device of its buffers and its stream.
  */
 #ifndef PN2_ABI_H_
 #define PN2_ABI_H_

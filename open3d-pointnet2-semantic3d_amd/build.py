@@ -82,7 +82,8 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
 
 if __name__ == "__main__":
     # --tuning: compile the kernel-selection knobs of the A/B scripts (tools/) as process-global variables behind
-    # pn2_debug_set (csrc/pn2_common.h PN2_TUNABLE).  Experiments only: the shipped library has no mutable global state.
+    # pn2_debug_set (csrc/pn2_common.h PN2_TUNABLE).  Experiments only: the shipped library's only mutable global state is the
+    # per-kernel atomic set of devices whose LDS limit has been raised (include/pn2_abi.h).
     tuning = "--tuning" in sys.argv
     print(build(force="--force" in sys.argv or tuning, verbose="--verbose" in sys.argv,
                 extra_flags=["-DPN2_TUNING_HOOKS"] if tuning else ()))

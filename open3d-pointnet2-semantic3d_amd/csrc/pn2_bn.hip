@@ -89,9 +89,9 @@ __device__ __forceinline__ void bn_block_sums(const BnMap<VEC>& mp, int c, int n
     pn2_bn_finish(fin, gridDim.x, blockIdx.x);  // the last workgroup folds the copies (and derives the constants)
 }
 
-// final[col] = sum over the slot copies.  A launch of its own rather than a "last block folds" epilogue: that variant
-// needs a ticket counter and device-scope fences in every reduction block and measured the same step time (8.2-8.7 ms
-// for 128-512 blocks) -- the kernel boundary gives the ordering for free.
+// final[col] = sum over the slot copies, as a launch of its own.  The fallback only: the producers of the sums fold them
+// themselves -- their last workgroup does, pn2_bn_finish in pn2_common.h -- and this kernel runs where the producer did not
+// finish (mode 2: the GEMM that added the sums ran without a finish).  The kernel boundary gives it the ordering for free.
 // (Eight threads per column with all their copies in flight at once measured the same 4.9 us per launch: the duration of
 // this kernel is a fixed cost, not its eight dependent L2 round trips.)
 __global__ void __launch_bounds__(kBnThreads)

@@ -6,12 +6,14 @@
 #include <stdint.h>
 
 #include "../../include/pn2_abi.h"
+#include "pn2_device_set.h"
 
 #define PN2_WAVE 64
 
 // Kernel-selection knobs used by the A/B scripts under tools/.  In the shipped library they are compile-time constants:
-// the library keeps NO mutable global state (include/pn2_abi.h).  A tuning build (`build.py --tuning`,
-// -DPN2_TUNING_HOOKS) turns them into process-global variables behind pn2_debug_set(what, value) -- experiments only.
+// the library keeps no mutable global state beyond what include/pn2_abi.h names (pn2_allow_lds below, the row-packing switch).
+// A tuning build (`build.py --tuning`, -DPN2_TUNING_HOOKS) turns them into process-global variables behind
+// pn2_debug_set(what, value) -- experiments only.
 #ifdef PN2_TUNING_HOOKS
 #define PN2_TUNABLE(type, name, value) type name = value;
 #else
@@ -23,6 +25,27 @@
         hipError_t e__ = hipGetLastError();           \
         if (e__ != hipSuccess) return (int)e__;       \
     } while (0)
+
+// ---- dynamic LDS beyond the default limit -------------------------------------------------------------------------------------
+constexpr int kPn2CuLdsBytes = 160 * 1024;         // LDS of one CU: the most a workgroup can ask for
+constexpr int kPn2DefaultDynLdsBytes = 64 * 1024;  // what a launch may ask for without hipFuncAttributeMaxDynamicSharedMemorySize
+
+// Allow kernel Kern `bytes` of dynamic LDS on the CURRENT device: call in front of every launch that may ask for more than
+// kPn2DefaultDynLdsBytes, in the branch that chose Kern.  The attribute belongs to (kernel, device), and so does the state: one
+// atomic set of devices per kernel, marked only after the attribute call succeeded (a failed call is made again by the next
+// launch), so nothing is called for a pair already seen.  Returns 0 or (int)hipError_t.  Safe from several host threads.
+template <auto Kern>
+int pn2_allow_lds(int bytes) {
+    static Pn2DeviceSet raised;
+    int dev = -1;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (int)e;
+    if (raised.done(dev)) return 0;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return (int)e;
+    raised.mark(dev);
+    return 0;
+}
 
 // Training-mode batch-norm workspace (pn2_bn.hip; pn2_linear_bn_stats in pn2_linear.hip writes into it), in doubles:
 //   head[kPn2BnHead] | final[2][c] | slot[nslots][2][c], nslots <= kPn2BnSlots chosen per call
@@ -107,8 +130,9 @@ __device__ __forceinline__ void pn2_bn_finish(const Pn2BnFinish& f, unsigned nwg
     __syncthreads();
     if (!s_last) return;
     const int c = f.c;
-    // fold: one thread per COLUMN of the 2c sums, 16 copies in flight per thread (a device-scope load is a ~1 us round trip: the
-    // chain of batches is this tail's duration), added in slot order like bn_fold_kernel; the two sums of a channel then meet in LDS
+    // fold: one thread per COLUMN of the 2c sums, kPn2FoldDepth (64) copies in flight per thread (a device-scope load is a ~1 us
+    // round trip: the chain of batches is this tail's duration; fewer than kPn2FoldDepth copies are loaded one after another),
+    // added in slot order like bn_fold_kernel; the two sums of a channel then meet in LDS
     for (int col = threadIdx.x; col < 2 * c; col += blockDim.x) {
         double t = 0.0;
         const double* sl = f.ws + kPn2BnHead + (size_t)2 * c + col;

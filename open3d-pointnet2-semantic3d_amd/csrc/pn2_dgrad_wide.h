@@ -184,13 +184,7 @@ int launch_dgrad_wide_one(int rows, const float* w, float* dx, const Pn2GradOnLo
     int blocks = (ntiles + 7) / 8;
     if (blocks > 256) blocks = 256;  // one workgroup of eight waves per CU
     constexpr size_t lds = sizeof(float) * ((size_t)16 * CO * 256 + 6 * 128 + 8 * 32 * (PN2_DGW_KS + 4));
-    static bool attr_set = false;  // per instantiation; benign race (idempotent call)
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dgrad_wide_kernel<CO, GX>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = pn2_allow_lds<dgrad_wide_kernel<CO, GX>>((int)lds)) return e;
     dgrad_wide_kernel<CO, GX><<<blocks, 512, lds, st>>>(rows, w, dx, gx, gepi, fin ? *fin : Pn2BnFinish{});
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;

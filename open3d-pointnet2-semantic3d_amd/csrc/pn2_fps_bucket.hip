@@ -709,30 +709,25 @@ extern "C" int pn2_fps_large(int b, int n, int m, const float* inp, void* worksp
         }
     }
     fb_gather_kernel<<<dim3((L.npad + 255) / 256, b), 256, 0, st>>>(n, L.npad, inp, vals_out, sorted, td);
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void* ks[6] = {reinterpret_cast<const void*>(fps_bucket_kernel<PN2_ARITH_STRICT>), reinterpret_cast<const void*>(fps_bucket_kernel<PN2_ARITH_FMA>),
-                             reinterpret_cast<const void*>(fps_bucket_kernel<PN2_ARITH_FMA_ALT>), reinterpret_cast<const void*>(fps_bucket_lazy_kernel<PN2_ARITH_STRICT>),
-                             reinterpret_cast<const void*>(fps_bucket_lazy_kernel<PN2_ARITH_FMA>), reinterpret_cast<const void*>(fps_bucket_lazy_kernel<PN2_ARITH_FMA_ALT>)};
-        for (int i = 0; i < 6; ++i) {
-            hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)(i < 3 ? kFbLds : kFlLds));
-            if (e != hipSuccess) return (int)e;
-        }
-        attr_set = true;
-    }
+#define PN2_FB(KERN_, LDS_, ...)                                 \
+    do {                                                         \
+        if (int e = pn2_allow_lds<KERN_>((int)(LDS_))) return e; \
+        KERN_<<<b, kFbThreads, LDS_, st>>>(__VA_ARGS__);         \
+    } while (0)
     if (g_fb_variant == 1) {  // tuning builds: the one-pick-per-round kernel (2.5 us per pick at n = 65536)
         switch (arith_mode) {
-            case PN2_ARITH_STRICT: fps_bucket_kernel<PN2_ARITH_STRICT><<<b, kFbThreads, kFbLds, st>>>(n, L.npad, m, inp, sorted, td, out, new_xyz); break;
-            case PN2_ARITH_FMA: fps_bucket_kernel<PN2_ARITH_FMA><<<b, kFbThreads, kFbLds, st>>>(n, L.npad, m, inp, sorted, td, out, new_xyz); break;
-            default: fps_bucket_kernel<PN2_ARITH_FMA_ALT><<<b, kFbThreads, kFbLds, st>>>(n, L.npad, m, inp, sorted, td, out, new_xyz); break;
+            case PN2_ARITH_STRICT: PN2_FB(fps_bucket_kernel<PN2_ARITH_STRICT>, kFbLds, n, L.npad, m, inp, sorted, td, out, new_xyz); break;
+            case PN2_ARITH_FMA: PN2_FB(fps_bucket_kernel<PN2_ARITH_FMA>, kFbLds, n, L.npad, m, inp, sorted, td, out, new_xyz); break;
+            default: PN2_FB(fps_bucket_kernel<PN2_ARITH_FMA_ALT>, kFbLds, n, L.npad, m, inp, sorted, td, out, new_xyz); break;
         }
     } else {
         switch (arith_mode) {
-            case PN2_ARITH_STRICT: fps_bucket_lazy_kernel<PN2_ARITH_STRICT><<<b, kFbThreads, kFlLds, st>>>(n, L.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
-            case PN2_ARITH_FMA: fps_bucket_lazy_kernel<PN2_ARITH_FMA><<<b, kFbThreads, kFlLds, st>>>(n, L.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
-            default: fps_bucket_lazy_kernel<PN2_ARITH_FMA_ALT><<<b, kFbThreads, kFlLds, st>>>(n, L.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
+            case PN2_ARITH_STRICT: PN2_FB(fps_bucket_lazy_kernel<PN2_ARITH_STRICT>, kFlLds, n, L.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
+            case PN2_ARITH_FMA: PN2_FB(fps_bucket_lazy_kernel<PN2_ARITH_FMA>, kFlLds, n, L.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
+            default: PN2_FB(fps_bucket_lazy_kernel<PN2_ARITH_FMA_ALT>, kFlLds, n, L.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
         }
     }
+#undef PN2_FB
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

@@ -292,18 +292,13 @@ int launch_fwd_wide_in(int rows, const float* x, const Pn2LoadTransform* xf, con
     int blocks = (ntiles + 7) / 8;
     if (blocks > 256) blocks = 256;  // one workgroup of eight waves per CU
     constexpr size_t lds = sizeof(float) * ((size_t)16 * CO * 256 + 8 * 32 * (64 + 4));
-    static bool attr_set = false;  // per instantiation; benign race (idempotent call)
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fwd_wide_in_kernel<CO, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(fwd_wide_in_kernel<CO, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
+    if (xf) {
+        if (int e = pn2_allow_lds<fwd_wide_in_kernel<CO, true>>((int)lds)) return e;
+        fwd_wide_in_kernel<CO, true><<<blocks, 512, lds, st>>>(rows, x, *xf, w, y, stats, f);
+    } else {
+        if (int e = pn2_allow_lds<fwd_wide_in_kernel<CO, false>>((int)lds)) return e;
+        fwd_wide_in_kernel<CO, false><<<blocks, 512, lds, st>>>(rows, x, Pn2LoadTransform{}, w, y, stats, f);
     }
-    if (xf) fwd_wide_in_kernel<CO, true><<<blocks, 512, lds, st>>>(rows, x, *xf, w, y, stats, f);
-    else fwd_wide_in_kernel<CO, false><<<blocks, 512, lds, st>>>(rows, x, Pn2LoadTransform{}, w, y, stats, f);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }
@@ -324,20 +319,17 @@ int launch_fwd_narrow_one(int rows, const float* x, const Pn2LoadTransform* xf, 
     int blocks = (ntiles + 3) / 4;
     if (blocks > 1024) blocks = 1024;  // ~4 workgroups per CU: several tiles per wave, one pair of atomics per column and wave
     constexpr size_t lds = sizeof(float) * ((size_t)(CI * 4) * CO * 256 + 4 * 32 * (32 * CI + 4));
-    if constexpr (lds > 64 * 1024) {
-        static bool attr_set = false;  // per instantiation; benign race (idempotent call)
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fwd_narrow_kernel<CI, CO, true>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(fwd_narrow_kernel<CI, CO, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-            attr_set = true;
+    if (xf) {
+        if constexpr (lds > kPn2DefaultDynLdsBytes) {
+            if (int e = pn2_allow_lds<fwd_narrow_kernel<CI, CO, true>>((int)lds)) return e;
         }
+        fwd_narrow_kernel<CI, CO, true><<<blocks, 256, lds, st>>>(rows, x, *xf, w, y, stats, f);
+    } else {
+        if constexpr (lds > kPn2DefaultDynLdsBytes) {
+            if (int e = pn2_allow_lds<fwd_narrow_kernel<CI, CO, false>>((int)lds)) return e;
+        }
+        fwd_narrow_kernel<CI, CO, false><<<blocks, 256, lds, st>>>(rows, x, Pn2LoadTransform{}, w, y, stats, f);
     }
-    if (xf) fwd_narrow_kernel<CI, CO, true><<<blocks, 256, lds, st>>>(rows, x, *xf, w, y, stats, f);
-    else fwd_narrow_kernel<CI, CO, false><<<blocks, 256, lds, st>>>(rows, x, Pn2LoadTransform{}, w, y, stats, f);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

@@ -276,14 +276,8 @@ int launch_ball_query_lane(int b, int n, int m, float thr, int nsample, const fl
     seg = (seg + 3) & ~3;
     const size_t lds = ((size_t)64 * nsample + kBq2Waves * 64 + 128) * sizeof(int) + (size_t)kBq2Waves * nsample * 64 * sizeof(unsigned short);
     if (seg > 65535) return PN2_ERANGE;
-    auto kern = ball_query_lane_kernel<MODE>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    constexpr auto kern = ball_query_lane_kernel<MODE>;
+    if (int e = pn2_allow_lds<kern>(kPn2CuLdsBytes)) return e;
     dim3 grid((m + 63) / 64, b);
     kern<<<grid, kBq2Threads, lds, st>>>(n, m, thr, nsample, seg, xyz1, xyz2, idx, cnt);
     PN2_RETURN_IF_LAUNCH_FAILED();
@@ -439,14 +433,8 @@ int launch_ball_query_multi(int b, const BqmParams& p, hipStream_t st) {
     for (int r = 0; r < R; ++r)
         lds += ((size_t)64 * p.ns[r] + kBqmWaves * 64 + 128) * sizeof(int) + (size_t)kBqmWaves * p.ns[r] * 64 * sizeof(unsigned short);
     if (lds > 150 * 1024) return PN2_EUNSUP;
-    auto kern = ball_query_multi_kernel<MODE, R>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    constexpr auto kern = ball_query_multi_kernel<MODE, R>;
+    if (int e = pn2_allow_lds<kern>(kPn2CuLdsBytes)) return e;
     dim3 grid((p.m + 63) / 64, b);
     kern<<<grid, kBqmThreads, lds, st>>>(p);
     PN2_RETURN_IF_LAUNCH_FAILED();
@@ -813,19 +801,14 @@ int launch_ball_query_grid(int b, int n, int m, float radius, float thr, int nsa
                            const float* xyz2, int* idx, int* cnt, hipStream_t st, unsigned char* bins = nullptr, int ld1 = 3) {
     const int np = (n + 63) & ~63;
     const size_t lds = bqg_lds_bytes(np);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ball_query_grid_kernel<MODE, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(ball_query_grid_kernel<MODE, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
     dim3 grid((m + kBqgWaves * kBqgQPW - 1) / (kBqgWaves * kBqgQPW), b);
-    if (bins) ball_query_grid_kernel<MODE, true><<<grid, kBqgThreads, lds, st>>>(n, m, radius, thr, nsample, xyz1, xyz2, idx, cnt, bins, bqg_ws_stride(n), ld1);
-    else ball_query_grid_kernel<MODE, false><<<grid, kBqgThreads, lds, st>>>(n, m, radius, thr, nsample, xyz1, xyz2, idx, cnt, nullptr, 0, ld1);
+    if (!bins) {  // <MODE, false> named first: the order of first use is the order of the kernels in the code object
+        if (int e = pn2_allow_lds<ball_query_grid_kernel<MODE, false>>(kPn2CuLdsBytes)) return e;
+        ball_query_grid_kernel<MODE, false><<<grid, kBqgThreads, lds, st>>>(n, m, radius, thr, nsample, xyz1, xyz2, idx, cnt, nullptr, 0, ld1);
+    } else {
+        if (int e = pn2_allow_lds<ball_query_grid_kernel<MODE, true>>(kPn2CuLdsBytes)) return e;
+        ball_query_grid_kernel<MODE, true><<<grid, kBqgThreads, lds, st>>>(n, m, radius, thr, nsample, xyz1, xyz2, idx, cnt, bins, bqg_ws_stride(n), ld1);
+    }
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }
@@ -839,7 +822,7 @@ int launch_ball_query_q(int b, int n, int m, float thr, int nsample, const float
                         const float* xyz2, int* idx, int* cnt, hipStream_t st) {
     dim3 grid((m + kBqWaves * QPW - 1) / (kBqWaves * QPW), b);
     const size_t lds = (size_t)kBqWaves * QPW * nsample * sizeof(int);
-    if (lds > 64 * 1024) return PN2_ERANGE;
+    if (lds > kPn2DefaultDynLdsBytes) return PN2_ERANGE;
     ball_query_kernel<MODE, QPW><<<grid, kBqThreads, lds, st>>>(n, m, thr, nsample, xyz1, xyz2, idx, cnt);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
@@ -1064,12 +1047,7 @@ extern "C" int pn2_ball_query_bin_ld(int b, int n, float radius, const float* xy
     if (b > 65535 || (long long)n * ld1 > 0x7fffffffLL) return PN2_ERANGE;
     const size_t stride = bqg_ws_stride(n);
     if (workspace_bytes < stride * (size_t)b || ((uintptr_t)workspace & 255) != 0) return PN2_EINVAL;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ball_query_bin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = pn2_allow_lds<ball_query_bin_kernel>(kPn2CuLdsBytes)) return e;
     ball_query_bin_kernel<<<b, kBqgThreads, bqg_lds_bytes((n + 63) & ~63), static_cast<hipStream_t>(stream)>>>(
         n, radius, xyz1, ld1, static_cast<unsigned char*>(workspace), stride);
     PN2_RETURN_IF_LAUNCH_FAILED();
@@ -1173,13 +1151,7 @@ extern "C" int pn2_selection_sort(int b, int n, int m, int k, const float* dist,
     if (!dist || !outi || !out) return PN2_ENULL;
     const size_t lds = (size_t)n * 8;
     if (lds > 150 * 1024 || m > 65535 * 32 || b > 65535) return PN2_ERANGE;  // row must fit LDS (n <= 19200)
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(selection_sort_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (int e = pn2_allow_lds<selection_sort_kernel>(kPn2CuLdsBytes)) return e;
     dim3 grid(m, b);
     selection_sort_kernel<<<grid, 64, lds, static_cast<hipStream_t>(stream)>>>(n, m, k, dist, outi, out);
     PN2_RETURN_IF_LAUNCH_FAILED();

@@ -733,13 +733,7 @@ extern "C" int pn2_scatter_plan_build_multi(int nplans, int b, const int* nent, 
     for (int i = 0; i < nplans; ++i) max_src = nsrc[i] > max_src ? nsrc[i] : max_src;
     if (max_src <= kPlanLdsMaxSrc) {  // one launch, LDS atomics, no memset (cnt / off / eq / ew are all written)
         const size_t lds = sizeof(int) * 2 * (size_t)max_src;
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(ti_csr_build_lds_kernel),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, sizeof(int) * 2 * kPlanLdsMaxSrc);
-            if (ea != hipSuccess) return (int)ea;
-            attr_set = true;
-        }
+        if (int e = pn2_allow_lds<ti_csr_build_lds_kernel>(sizeof(int) * 2 * kPlanLdsMaxSrc)) return e;
         ti_csr_build_lds_kernel<<<dim3(b, nplans), kPlanLdsThreads, lds, st>>>(pb);
         PN2_RETURN_IF_LAUNCH_FAILED();
         return PN2_OK;

@@ -1317,13 +1317,7 @@ static int linear_wgrad_impl(int rows, int cin, int cout, const float* x, const 
         constexpr size_t lds8 = sizeof(float) * 4 * 2 * 4 * 16 * 64;  // 128 KB: beyond the default dynamic limit
 #define PN2_WG8(XF_, GX_, XFV_, GXV_)                                                                                              \
         do {                                                                                                                       \
-            static bool attr_set = false; /* per instantiation; benign race (idempotent call) */                                  \
-            if (!attr_set) {                                                                                                       \
-                hipError_t e8 = hipFuncSetAttribute(reinterpret_cast<const void*>(linear_wgrad_kernel<2, 4, XF_, GX_, 8>),         \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);                       \
-                if (e8 != hipSuccess) return (int)e8;                                                                              \
-                attr_set = true;                                                                                                   \
-            }                                                                                                                      \
+            if (int e8 = pn2_allow_lds<linear_wgrad_kernel<2, 4, XF_, GX_, 8>>((int)lds8)) return e8;                             \
             linear_wgrad_kernel<2, 4, XF_, GX_, 8><<<grid8, 512, lds8, st>>>(rows, cin, cout, chunk, x, dy, dw, XFV_, GXV_);       \
         } while (0)
         const Pn2LoadTransform xv = xf ? *xf : Pn2LoadTransform{};

@@ -421,6 +421,14 @@ mlp_wide_kernel(WideParams p) {
     }
 }
 
+template <int MODE>
+int launch_mlp_wide_mode(const WideParams& p, size_t lds, hipStream_t st) {
+    if (int e = pn2_allow_lds<mlp_wide_kernel<MODE>>(kPn2CuLdsBytes)) return e;
+    mlp_wide_kernel<MODE><<<(p.rows + 31) / 32, 256, lds, st>>>(p);
+    PN2_RETURN_IF_LAUNCH_FAILED();
+    return PN2_OK;
+}
+
 int launch_mlp_wide(WideParams& p, int mode, hipStream_t st) {
     // LDS: buffer 0 holds the layer-0 and layer-2 inputs, buffer 1 the layer-1 input
     const int k0 = (p.cin + 7) & ~7;
@@ -445,22 +453,10 @@ int launch_mlp_wide(WideParams& p, int mode, hipStream_t st) {
     p.scratch_alias = sliced && alias_ok;
     p.rowtab_off = p.scratch_off + (sliced && !alias_ok ? 2 * 64 * 64 : 0);
     const size_t lds = sizeof(float) * ((size_t)p.rowtab_off + (p.zpre && mode == kWideInterp ? 32 * 8 : 0));
-    if (lds > 160 * 1024) return PN2_EUNSUP;
-    const void* kern = mode == kWideGather ? reinterpret_cast<const void*>(mlp_wide_kernel<kWideGather>)
-                       : mode == kWideInterp ? reinterpret_cast<const void*>(mlp_wide_kernel<kWideInterp>)
-                                             : reinterpret_cast<const void*>(mlp_wide_kernel<kWidePlain>);
-    static bool attr_set[3] = {false, false, false};
-    if (!attr_set[mode]) {
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set[mode] = true;
-    }
-    const int tiles = (p.rows + 31) / 32;
-    if (mode == kWideGather) mlp_wide_kernel<kWideGather><<<tiles, 256, lds, st>>>(p);
-    else if (mode == kWideInterp) mlp_wide_kernel<kWideInterp><<<tiles, 256, lds, st>>>(p);
-    else mlp_wide_kernel<kWidePlain><<<tiles, 256, lds, st>>>(p);
-    PN2_RETURN_IF_LAUNCH_FAILED();
-    return PN2_OK;
+    if (lds > kPn2CuLdsBytes) return PN2_EUNSUP;
+    if (mode == kWideGather) return launch_mlp_wide_mode<kWideGather>(p, lds, st);
+    if (mode == kWideInterp) return launch_mlp_wide_mode<kWideInterp>(p, lds, st);
+    return launch_mlp_wide_mode<kWidePlain>(p, lds, st);
 }
 
 int check_layers(int nlayers, const int* widths, const float* const* w, const float* const* bias) {

@@ -1042,12 +1042,19 @@ PN2_TUNABLE(int, g_chain_tag, 0)     // tuning hook (pn2_debug_set(16, v)): grap
 std::atomic<int> g_sa_row_packing{1};
 constexpr size_t kPackLdsBytes = (64 + 64 * 4) * sizeof(int);  // classes + tile list of one block
 
+// the chain kernel with or without row packing, its LDS limit raised on the current device (err = pn2_allow_lds's result)
 template <int L, int NT1, int NT2, int NT3, bool VEC8, bool DENSE, bool POOL, int NW, bool INTERP, bool PREZ>
-auto chain_kernel(bool pack) -> void (*)(SaFusedParams) {
+auto chain_kernel(bool pack, int& err) -> void (*)(SaFusedParams) {
     if constexpr (POOL && !DENSE && !INTERP) {
-        if (pack) return sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, NW, INTERP, PREZ, true>;
+        if (pack) {
+            constexpr auto packed = sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, NW, INTERP, PREZ, true>;
+            err = pn2_allow_lds<packed>(kPn2CuLdsBytes);
+            return packed;
+        }
     }
-    return sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, NW, INTERP, PREZ, false>;
+    constexpr auto plain = sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, NW, INTERP, PREZ, false>;
+    err = pn2_allow_lds<plain>(kPn2CuLdsBytes);
+    return plain;
 }
 
 // PACK: centres per block = the share of one workgroup of its XCD's range (the kernel's own split), at most 64 (one ballot)
@@ -1081,14 +1088,8 @@ int launch_chain(const SaFusedParams& p_in, hipStream_t st) {
     const int need4 = (p.groups + 3) / 4;
     if constexpr (L == 1) {
         if (g_chain_nw == 16 && p.groups >= 4096) {  // one 16-wave workgroup per CU: 4 waves/SIMD share the MFMA pipe
-            auto kern = sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 16, INTERP, PREZ>;
-            static bool attr_set = false;
-            if (!attr_set) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return (int)e;
-                attr_set = true;
-            }
+            constexpr auto kern = sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 16, INTERP, PREZ>;
+            if (int e = pn2_allow_lds<kern>(kPn2CuLdsBytes)) return e;
             kern<<<g_chain_grid, 1024, bytes, st>>>(p);
             PN2_RETURN_IF_LAUNCH_FAILED();
             return PN2_OK;
@@ -1101,13 +1102,9 @@ int launch_chain(const SaFusedParams& p_in, hipStream_t st) {
         if (want_pipe && p.c1 <= 2 * kPipeSkipSteps && (p.groups >= 2048 || p.schedule == 1)) {
             const bool ns2 = p.c1 <= 4;
             auto kern = ns2 ? fp_chain_pipe_kernel<NT2, NT3, 2> : fp_chain_pipe_kernel<NT2, NT3, 4>;
-            static bool attr_set[2] = {false, false};
-            if (!attr_set[ns2]) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return (int)e;
-                attr_set[ns2] = true;
-            }
+            if (int e = ns2 ? pn2_allow_lds<fp_chain_pipe_kernel<NT2, NT3, 2>>(kPn2CuLdsBytes)
+                            : pn2_allow_lds<fp_chain_pipe_kernel<NT2, NT3, 4>>(kPn2CuLdsBytes))
+                return e;
             const size_t pbytes = ((size_t)(ns2 ? 2 : 4) * 2 * W1 + W1 + (size_t)W1 * W2 + W2 + (size_t)W2 * W3 + W3) * sizeof(float);
             int grid = g_chain_grid;
             if (grid > need4) grid = need4;
@@ -1125,14 +1122,8 @@ int launch_chain(const SaFusedParams& p_in, hipStream_t st) {
         // three waves per SIMD (168 registers, 12 B of scratch): 128-131 us against 101 for two -- measured twice, with and
         // without spills; not used
         if (nw12 && bytes > 78 * 1024 && p.groups >= 2048) {
-            auto kern = sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 12, INTERP, PREZ>;
-            static bool attr_set = false;
-            if (!attr_set) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return (int)e;
-                attr_set = true;
-            }
+            constexpr auto kern = sa_fused_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 12, INTERP, PREZ>;
+            if (int e = pn2_allow_lds<kern>(kPn2CuLdsBytes)) return e;
             int grid = g_chain_grid;
             const int need12 = (p.groups + 11) / 12;
             if (grid > need12) grid = need12;
@@ -1144,28 +1135,18 @@ int launch_chain(const SaFusedParams& p_in, hipStream_t st) {
     if (bytes > 78 * 1024 && p.groups >= 2048 && g_chain_nw != 4) {  // g_chain_nw == 4 (tuning): one wave per SIMD
         // only one workgroup fits per CU: give it 8 waves (2 per SIMD) sharing the LDS weights.
         // (With fewer than 2048 tiles, 4-wave workgroups spread the tiles over twice as many CUs.)
-        auto kern = chain_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 8, INTERP, PREZ>(pack);
-        static bool attr_set[2] = {false, false};  // per instantiation; benign race (idempotent call)
-        if (!attr_set[pack]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return (int)e;
-            attr_set[pack] = true;
-        }
+        int e = 0;
+        auto kern = chain_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 8, INTERP, PREZ>(pack, e);
+        if (e) return e;
         int grid = g_chain_grid;
         const int need8 = (p.groups + 7) / 8;
         if (grid > need8) grid = need8;
         p.blk = pack_block(p.groups, grid);
         kern<<<grid, 512, bytes + (pack ? kPackLdsBytes : 0), st>>>(p);
     } else {
-        auto kern = chain_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 4, INTERP, PREZ>(pack);
-        static bool attr_set[2] = {false, false};
-        if (!attr_set[pack]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return (int)e;
-            attr_set[pack] = true;
-        }
+        int e = 0;
+        auto kern = chain_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 4, INTERP, PREZ>(pack, e);
+        if (e) return e;
         int grid = bytes > 78 * 1024 ? g_chain_grid : g_chain_grid * 2;  // 4-wave workgroups: as many as LDS lets co-reside per CU
         if (grid > need4) grid = need4;
         p.blk = pack_block(p.groups, grid);

@@ -268,14 +268,8 @@ int launch_bf16(const SaBf16Params& p, hipStream_t st) {
     if (L >= 3) bytes += (size_t)(W2 / 16) * 2 * W3 * 16 + W3 * 4;
     if (bytes > 150 * 1024) return PN2_EUNSUP;
     constexpr int NW = 8;
-    auto kern = sa_fused_bf16_kernel<L, NT1, NT2, NT3, RT, NW>;
-    static bool attr_set = false;  // per instantiation; benign race (idempotent call)
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    constexpr auto kern = sa_fused_bf16_kernel<L, NT1, NT2, NT3, RT, NW>;
+    if (int e = pn2_allow_lds<kern>(kPn2CuLdsBytes)) return e;
     int grid = bytes > 78 * 1024 ? 256 : 512;
     const int need = (p.groups + NW - 1) / NW;
     if (grid > need) grid = need;

@@ -498,14 +498,13 @@ fps_lazy_kernel(int n, int m, const float* __restrict__ xyz_all, int ld, int* __
 template <int NT, int PPT, int MODE>
 int launch_fps_lazy(int b, int n, int m, const float* inp, int ld, int* out, float* nxyz, const int* tie_in, int* tie_out, hipStream_t st) {
     const size_t bytes = fps_lazy_bytes(n, m);
-    auto kern = tie_out ? fps_lazy_kernel<NT, PPT, MODE, true> : fps_lazy_kernel<NT, PPT, MODE, false>;
-    static bool attr_set[2] = {false, false};  // per instantiation; benign race (idempotent call)
-    if (!attr_set[tie_out != nullptr]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set[tie_out != nullptr] = true;
+    if (tie_out) {
+        if (int e = pn2_allow_lds<fps_lazy_kernel<NT, PPT, MODE, true>>(kPn2CuLdsBytes)) return e;
+        fps_lazy_kernel<NT, PPT, MODE, true><<<b, NT, bytes, st>>>(n, m, inp, ld, out, nxyz, g_fps_stats, tie_in, tie_out);
+    } else {
+        if (int e = pn2_allow_lds<fps_lazy_kernel<NT, PPT, MODE, false>>(kPn2CuLdsBytes)) return e;
+        fps_lazy_kernel<NT, PPT, MODE, false><<<b, NT, bytes, st>>>(n, m, inp, ld, out, nxyz, g_fps_stats, tie_in, tie_out);
     }
-    kern<<<b, NT, bytes, st>>>(n, m, inp, ld, out, nxyz, g_fps_stats, tie_in, tie_out);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }
@@ -558,16 +557,15 @@ int launch_fps_reg(int b, int n, int m, const float* inp, int ld, int* out, floa
     const size_t xyz_bytes = (size_t)n * sizeof(float4);
     // 160 KiB LDS per CU; keep the cloud (and the pick list) in LDS when they fit (n <= 8192 -> 128 KiB + 4m)
     const size_t pick_bytes = (size_t)m * sizeof(int);
-    if (slots_bytes + xyz_bytes + pick_bytes <= 158 * 1024) {
-        auto kern = tie_out ? fps_reg_kernel<NT, PPT, MODE, true, true> : fps_reg_kernel<NT, PPT, MODE, true, false>;
-        static int attr_bytes[2] = {0, 0};  // per instantiation; benign race (idempotent call)
-        if (attr_bytes[tie_out != nullptr] < (int)(slots_bytes + xyz_bytes + pick_bytes)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return (int)e;
-            attr_bytes[tie_out != nullptr] = 160 * 1024;
+    const size_t bytes = slots_bytes + xyz_bytes + pick_bytes;
+    if (bytes <= 158 * 1024) {
+        if (tie_out) {
+            if (int e = pn2_allow_lds<fps_reg_kernel<NT, PPT, MODE, true, true>>(kPn2CuLdsBytes)) return e;
+            fps_reg_kernel<NT, PPT, MODE, true, true><<<b, NT, bytes, st>>>(n, m, inp, ld, out, nxyz, tie_in, tie_out);
+        } else {
+            if (int e = pn2_allow_lds<fps_reg_kernel<NT, PPT, MODE, true, false>>(kPn2CuLdsBytes)) return e;
+            fps_reg_kernel<NT, PPT, MODE, true, false><<<b, NT, bytes, st>>>(n, m, inp, ld, out, nxyz, tie_in, tie_out);
         }
-        kern<<<b, NT, slots_bytes + xyz_bytes + pick_bytes, st>>>(n, m, inp, ld, out, nxyz, tie_in, tie_out);
     } else if constexpr (NT != 64) {
         auto kern = tie_out ? fps_reg_kernel<NT, PPT, MODE, false, true> : fps_reg_kernel<NT, PPT, MODE, false, false>;
         kern<<<b, NT, slots_bytes, st>>>(n, m, inp, ld, out, nxyz, tie_in, tie_out);
@@ -590,7 +588,7 @@ int dispatch_fps(int b, int n, int m, const float* inp, int ld, float* temp, int
     // (B = 16; profiles/r03_fps_lazy.txt).  At n <= 2048 its serial picking wave (~400 cycles per pick) costs what a whole
     // round of the one-pick kernels below costs (93 vs 84 us at n = 1024), so those keep the small levels.
     // g_fps_variant (tuning builds): 2 = one-pick kernels everywhere, 3 = lazy kernel from n > 512.
-    if (g_fps_variant != 2 && n > (g_fps_variant == 3 ? 512 : 2048) && n <= 8192 && fps_lazy_bytes(n, m) <= 160 * 1024) {
+    if (g_fps_variant != 2 && n > (g_fps_variant == 3 ? 512 : 2048) && n <= 8192 && fps_lazy_bytes(n, m) <= kPn2CuLdsBytes) {
         if (n <= 1024) return launch_fps_lazy<256, 4, MODE>(b, n, m, inp, ld, out, nxyz, tie_in, tie_out, st);
         if (n <= 2048) return launch_fps_lazy<512, 4, MODE>(b, n, m, inp, ld, out, nxyz, tie_in, tie_out, st);
         if (n <= 4096) return launch_fps_lazy<1024, 4, MODE>(b, n, m, inp, ld, out, nxyz, tie_in, tie_out, st);

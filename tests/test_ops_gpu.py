@@ -904,3 +904,124 @@ def test_fps_large_bucket_kernel_bit_exact(pn2, oracle, cuda, case, mode):
     assert np.array_equal(only_idx.cpu().numpy(), ref)
     assert np.array_equal(streamed.cpu().numpy(), ref)
     assert np.array_equal(new_xyz.cpu().numpy(), oracle.gather_point(xyz, ref))
+
+
+# ------------------------------------------------------------------ dynamic LDS beyond 64 KiB, on two devices ----------
+# Every launcher whose kernel asks for more than the default 64 KiB of dynamic LDS raises the limit per (kernel, device)
+# (pn2_allow_lds, csrc/pn2_common.h).  Each case is the smallest shape of its entry point whose request exceeds 65536 bytes, by
+# the launcher's own byte formula; inputs are built once on the host and must give the same bits on both devices.
+def _lds_selection_sort(pn2, torch, dev):
+    """pn2_selection_sort: n * 8 bytes of LDS; n = 8256 -> 66048"""
+    dist = torch.from_numpy(s_randn(1, 1, 1, 8256).reshape(1, 1, 8256)).abs().to(dev)
+    return pn2.tf_ops.tf_grouping.select_top_k(2, dist)
+
+
+def _lds_fps_lazy(pn2, torch, dev):
+    """lazy FPS kernel (2048 < n <= 8192): kLazyHead + 16 n + max(16384, 2 n, 4 m) = 2176 + 131072 + 16384 = 149632 at n = 8192"""
+    return (pn2.farthest_point_sample(8, torch.from_numpy(s_scene(2, 1, 8192)).to(dev)),)
+
+
+def _lds_ball_query_grid(pn2, torch, dev):
+    """LDS-grid ball query: bqg_lds_bytes(np) = 14 np + 37356 with np = n rounded up to 64: 65132 at np = 1984, 66028 at
+    np = 2048, so n = 1985 is the smallest cloud above the limit (kernel 3 named explicitly: by shape it starts at n = 4096)"""
+    xyz = s_scene(3, 1, 1985)
+    return pn2.query_ball_point(0.8, 16, torch.from_numpy(xyz).to(dev), torch.from_numpy(xyz[:, :64].copy()).to(dev), kernel=3)
+
+
+def _chain_layers(torch, dev, cin, seed):
+    rs = np.random.RandomState(seed)
+    ws = [torch.from_numpy(rs.uniform(-0.2, 0.2, (k, 128)).astype(np.float32)).to(dev) for k in (cin, 128)]
+    bs = [torch.from_numpy(rs.uniform(-0.1, 0.1, 128).astype(np.float32)).to(dev) for _ in ws]
+    return ws, bs
+
+
+def _lds_sa_chain(pn2, torch, dev):
+    """pn2_sa_mlp_max_fused, widths [128, 128], c = 0: (2 k-steps * 2 * 128 + 128 + 128 * 128 + 128) floats + 64 = 68672 bytes
+    whatever the number of groups (the narrower supported stacks stay below 64 KiB); 4 groups of 32 rows -> the 4-wave kernel"""
+    from pn2_amd._lib import int_array, launch, ptr, ptr_table
+    rs = np.random.RandomState(4)
+    xyz = torch.from_numpy(s_scene(4, 1, 64)).to(dev)
+    new_xyz = xyz[:, :4].contiguous()
+    idx = torch.from_numpy(rs.randint(0, 64, (1, 4, 32)).astype(np.int32)).to(dev)
+    ws, bs = _chain_layers(torch, dev, 3, 5)
+    out = torch.empty((1, 4, 128), dtype=torch.float32, device=dev)
+    launch("pn2_sa_mlp_max_fused", xyz, 1, 64, 4, 32, 0, ptr(xyz), ptr(new_xyz), None, ptr(idx), 2, int_array([128, 128]),
+           ptr_table(ws), ptr_table(bs), ptr(out))  # raises unless PN2_OK
+    return (out,)
+
+
+def _lds_fp_chain(pn2, torch, dev):
+    """pn2_fp_mlp_fused, widths [128, 128], c2 = 8, c1 = 0: (4 k-steps * 2 * 128 + 128 + 128 * 128 + 128) floats + 64 = 70720
+    bytes; one group of 32 rows"""
+    rs = np.random.RandomState(6)
+    dist = torch.from_numpy(rs.uniform(0.01, 1.0, (1, 32, 3)).astype(np.float32)).to(dev)
+    idx = torch.from_numpy(rs.randint(0, 4, (1, 32, 3)).astype(np.int32)).to(dev)
+    points2 = torch.from_numpy(s_randn(7, 1, 4, 8)).to(dev)
+    ws, bs = _chain_layers(torch, dev, 8, 8)
+    y = pn2.util.tf_util.hip_fp_mlp_fused(dist, idx, None, points2, ws, bs)
+    assert y is not None, "pn2_fp_mlp_fused refused [128, 128]"
+    return (y,)
+
+
+_STREAM_ROWS = 65536  # PN2_STREAM_MIN_ROWS (csrc/pn2_common.h): fewest rows the streaming training GEMMs take
+
+
+def _small_ints(torch, dev, seed, shape):
+    """integer values in [-2, 2]: every product and partial sum of the GEMMs below is exact in fp32, so the result does not
+    depend on the order of the atomics that close them"""
+    return torch.from_numpy(np.random.RandomState(seed).randint(-2, 3, shape).astype(np.float32)).to(dev)
+
+
+def _lds_fwd_wide_in(pn2, torch, dev):
+    """pn2_linear_bn_stats, 128 -> 128 at PN2_STREAM_MIN_ROWS rows (fwd_wide_in_kernel<4>): exactly
+    4 * (16 * 4 * 256 + 8 * 32 * 68) = 135168 bytes are requested and asked for"""
+    tfu = pn2.util.tf_util
+    x, w = _small_ints(torch, dev, 9, (_STREAM_ROWS, 128)), _small_ints(torch, dev, 10, (128, 128))
+    ws = torch.zeros(pn2._lib.lib.pn2_bn_workspace_bytes(128) // 8, dtype=torch.float64, device=dev)
+    y = tfu.hip_matmul_bn_stats(x, w, ws)
+    assert torch.equal(y, (x.double() @ w.double()).float())
+    return (y,)
+
+
+def _lds_wgrad_eight_waves(pn2, torch, dev):
+    """pn2_linear_wgrad, 64 x 128 tile at PN2_STREAM_MIN_ROWS rows (linear_wgrad_kernel<2, 4, ., ., 8>): exactly
+    4 * 4 * 2 * 4 * 16 * 64 = 131072 bytes"""
+    from pn2_amd._lib import launch, ptr
+    x, dy = _small_ints(torch, dev, 11, (_STREAM_ROWS, 64)), _small_ints(torch, dev, 12, (_STREAM_ROWS, 128))
+    dw = torch.empty((64, 128), dtype=torch.float32, device=dev)
+    launch("pn2_linear_wgrad", x, _STREAM_ROWS, 64, 128, ptr(x), ptr(dy), ptr(dw))
+    assert torch.equal(dw, (x.double().t() @ dy.double()).float())
+    return (dw,)
+
+
+_LDS_CASES = [_lds_selection_sort, _lds_fps_lazy, _lds_ball_query_grid, _lds_sa_chain, _lds_fp_chain, _lds_fwd_wide_in,
+              _lds_wgrad_eight_waves]
+_LDS_STEP_SECONDS = 60  # a step is milliseconds of GPU work; a hung one ends the process instead of the whole run's time limit
+
+
+def run_lds_case(case, pn2, dev):
+    """one entry point on one device, under its own time limit -> its outputs on the host.  A step that outlives
+    _LDS_STEP_SECONDS ends the WHOLE pytest process: faulthandler writes every thread's traceback to stderr and calls
+    _exit(1), so the tests after it do not run and no summary line is printed.  A run that stops here with a traceback and
+    status 1 is a hung launch in this step, not a fault of whatever started pytest; nothing else is started on the device."""
+    import faulthandler
+    import torch
+    faulthandler.dump_traceback_later(_LDS_STEP_SECONDS, exit=True)
+    try:
+        with torch.cuda.device(dev):
+            outs = [o.cpu() for o in case(pn2, torch, dev)]  # a wrapper raises Pn2Error unless its entry point returned PN2_OK
+            torch.cuda.synchronize()
+    finally:
+        faulthandler.cancel_dump_traceback_later()
+    return outs
+
+
+@pytest.mark.parametrize("case", _LDS_CASES, ids=lambda f: f.__name__[5:])
+def test_lds_limit_is_raised_on_every_device(pn2, cuda, case):
+    """In one process: the entry point on cuda:0, then on cuda:1, same inputs -> PN2_OK and the same bits on both.  With the
+    limit raised once per process (a function-local flag) the second device's launch fails with an invalid-value error."""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("one device visible")
+    first, second = (run_lds_case(case, pn2, torch.device("cuda", i)) for i in (0, 1))
+    assert len(first) == len(second) and all(torch.equal(a, b) for a, b in zip(first, second))
