@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PN2_ABI_VERSION 1
+#define PN2_ABI_VERSION 2
 
 /* error codes (negative); positive return values are hipError_t */
 #define PN2_OK 0
@@ -318,26 +318,24 @@ int pn2_bn_relu_backward(long long rows, int c, const float *dz, const float *y,
                          const float *beta, const float *save_mean, const float *save_invstd, int relu,
                          int pool, const float *zmax, const float *ties, void *workspace,
                          size_t workspace_bytes, float *dy, float *dgamma, float *dbeta, void *stream);
-/* The two calls above with a workspace the CALLER has already zero-filled: one fill of an arena holding the scratch of
- * every layer of a training step replaces one memset per call (88 per step for the semantic.json model). */
-int pn2_bn_relu_forward_ws0(long long rows, int c, const float *y, const float *gamma, const float *beta,
-                            const float *bias, float eps, float decay, int relu, int pool, float *running_mean,
-                            float *running_var, void *workspace, size_t workspace_bytes, float *save_mean,
-                            float *save_invstd, float *z, float *ties, void *stream);
-int pn2_bn_relu_backward_ws0(long long rows, int c, const float *dz, const float *y, const float *gamma,
-                             const float *beta, const float *save_mean, const float *save_invstd, int relu,
-                             int pool, const float *zmax, const float *ties, void *workspace,
-                             size_t workspace_bytes, float *dy, float *dgamma, float *dbeta, void *stream);
+/* The state of a batch-norm workspace when a call arrives = the `stats_mode` argument (an int) of pn2_bn_relu_forward_mode,
+ * pn2_bn_relu_forward_pool and pn2_bn_relu_backward_mode; any other value is PN2_EINVAL.  The two calls above are UNCLEARED.
+ *   UNCLEARED  contents irrelevant: the call zeroes the workspace itself.
+ *   ZEROED     the caller zeroed it: one fill of an arena holding the scratch of every layer of a training step replaces one
+ *              memset per call (88 per step for the semantic.json model).
+ *   SUMMED     zeroed by the caller, and a producer has added its sums (forward: y, y*y; backward, pool <= 1: g, g*xhat) to all
+ *              slot copies: the call folds them and skips its reduction pass.  Left by pn2_linear_bn_stats, pn2_linear_bn_stats_xf,
+ *              pn2_linear_dgrad_bn_grad_stats, pn2_linear_dgrad_gx with y_below, and the entry points below with finish 0.
+ *   FOLDED     the sums are there and the producer's last workgroup has folded them: only the normalisation pass is left.  Left
+ *              by pn2_linear_bn_stats_fin, pn2_sa_first_layer_bn, pn2_*_hoist_rows*_bn with finish 1 and by pn2_linear_dgrad_fin,
+ *              pn2_linear_bwd_fused with finish_below 1. */
+enum { PN2_BN_WS_UNCLEARED = 0, PN2_BN_WS_ZEROED = 1, PN2_BN_WS_SUMMED = 2, PN2_BN_WS_FOLDED = 3 };
 /* conv2d -> batch_norm of the training path (util/tf_util.py:186-204) without the statistics pass over y:
  * pn2_linear_bn_stats computes y (rows,cout) = x (rows,cin) . w (cin,cout) (no bias, no activation; cout % 32 == 0)
  * and adds the column sums of y and y*y to `bn_workspace` (pn2_bn_workspace_bytes(cout) bytes, ZEROED by the caller)
- * from the GEMM's accumulators; pn2_bn_relu_forward_stats is pn2_bn_relu_forward for such a (y, workspace) pair. */
+ * from the GEMM's accumulators, which leaves it PN2_BN_WS_SUMMED for pn2_bn_relu_forward_mode / _pool. */
 int pn2_linear_bn_stats(int rows, int cin, int cout, const float *x, const float *w, float *y,
                         void *bn_workspace, size_t workspace_bytes, void *stream);
-int pn2_bn_relu_forward_stats(long long rows, int c, const float *y, const float *gamma, const float *beta,
-                              const float *bias, float eps, float decay, int relu, int pool, float *running_mean,
-                              float *running_var, void *workspace, size_t workspace_bytes, float *save_mean,
-                              float *save_invstd, float *z, float *ties, void *stream);
 
 /* Fused set-abstraction MLP (pointnet_util.py:43-54 + :150-170, inference BN
  * folded): for every (b, j) group gathers nsample neighbours by idx, builds
@@ -464,18 +462,14 @@ int pn2_linear_dgrad(int rows, int cin, int cout, const float *dy, const float *
  * layer's input, consumed by nothing else): y_below (rows,cin) = that layer's pre-normalisation output, gamma / beta /
  * save_mean / save_invstd its parameters and saved batch moments, relu its activation flag.  While the accumulator tiles of
  * dx are at hand the kernel adds sum g and sum g*xhat per channel (g = dx * [ReLU mask], xhat = (y-mean)*invstd) to that
- * layer's ZEROED batch-norm workspace (pn2_bn_workspace_bytes(cin) bytes); pn2_bn_relu_backward_stats -- pn2_bn_relu_backward
- * for such a (dz, workspace) pair, pool <= 1 -- then skips its reduction pass over (dz, y).  Same results up to fp64
- * summation order.  PN2_EUNSUP for cout <= 16 (streaming kernel): use pn2_linear_dgrad + pn2_bn_relu_backward.
+ * layer's ZEROED batch-norm workspace (pn2_bn_workspace_bytes(cin) bytes), which leaves it PN2_BN_WS_SUMMED:
+ * pn2_bn_relu_backward_mode then skips its reduction pass over (dz, y).  Same results up to fp64 summation order.
+ * PN2_EUNSUP for cout <= 16 (streaming kernel): use pn2_linear_dgrad + pn2_bn_relu_backward.
  * (tf.gradients through tf_util.py:186-204: conv2d -> batch_norm -> relu.) */
 int pn2_linear_dgrad_bn_grad_stats(int rows, int cin, int cout, const float *dy, const float *w, float *dx,
                                    const float *y_below, const float *gamma, const float *beta, const float *save_mean,
                                    const float *save_invstd, int relu, void *bn_workspace, size_t workspace_bytes,
                                    void *stream);
-int pn2_bn_relu_backward_stats(long long rows, int c, const float *dz, const float *y, const float *gamma,
-                               const float *beta, const float *save_mean, const float *save_invstd, int relu,
-                               int pool, const float *zmax, const float *ties, void *workspace,
-                               size_t workspace_bytes, float *dy, float *dgamma, float *dbeta, void *stream);
 
 /* model.get_loss  model.py:152-161: weighted sparse softmax cross-entropy, reduction SUM_BY_NONZERO_WEIGHTS.
  * logits (rows,num_class) f32, labels (rows) int32 (label64 = 0) or int64 (label64 = 1), weights (rows) f32 ->
@@ -670,8 +664,8 @@ int pn2_group_pool_grad(long long rows, int k, int c, int mode, const float *x, 
                         float *dx, void *stream);
 
 /* conv2d -> batch_norm -> relu -> conv2d of the training path (tf_util.py:186-204 twice) without writing the normalised
- * activation of the lower layer: pn2_bn_relu_forward_deferred turns the statistics of y (stats_done = 1: left in the zeroed
- * workspace by pn2_linear_bn_stats; 0: taken here, workspace zeroed by the caller) into save_mean / save_invstd, the moving
+ * activation of the lower layer: pn2_bn_relu_forward_deferred turns the statistics of y (stats_done = 1: the
+ * workspace is PN2_BN_WS_SUMMED; 0: PN2_BN_WS_ZEROED, the statistics are taken here) into save_mean / save_invstd, the moving
  * averages and per-channel (scale, shift) with z = relu?(fma(y, scale, shift)); pn2_linear_bn_stats_xf (the upper layer's
  * forward GEMM + statistics) and pn2_linear_wgrad_accumulate_xf (its weight gradient) apply them to y while loading it.
  * Only valid when the lower activation has no other consumer.  _xf: cin % 4 == 0, rows > 2048, 16-byte aligned operands,
@@ -692,9 +686,9 @@ int pn2_linear_narrow(int rows, int cin, int cout, const float *x, const float *
 
 /* The batch-norm gradient of the training path (tf_util.py:555-581 through tf.gradients) applied ON LOAD by the two gradient
  * GEMMs of the layer, so that dy = the gradient leaving the batch norm (+ReLU [+ max over groups of 32 rows]) is never written
- * or re-read.  pn2_bn_grad_constants turns the two per-channel sums (stats_done = 1: left in the zeroed workspace by
- * pn2_linear_dgrad_bn_grad_stats / pn2_linear_dgrad_gx of the layer above; 0: taken here with one pass over (dz, y), workspace
- * zeroed by the caller) into dgamma, dbeta and coef (6, c) = sc, sh, mean, invstd, k1, k2 with
+ * or re-read.  pn2_bn_grad_constants turns the two per-channel sums (stats_done = 1: the workspace is
+ * PN2_BN_WS_SUMMED by the data gradient of the layer above; 0: PN2_BN_WS_ZEROED, the sums are taken here with one pass over
+ * (dz, y)) into dgamma, dbeta and coef (6, c) = sc, sh, mean, invstd, k1, k2 with
  * dy = sc * fma(-(y - mean) * invstd, k2, g - k1), g = dz * [relu mask] -- pn2_bn_relu_backward's expressions, so both forms
  * hand the GEMMs the same bits.  pn2_linear_dgrad_gx: dx (rows, cin) = dy (rows, cout) . W^T (pn2_linear_dgrad) with dy formed
  * from y (rows, cout), dz ((rows, cout); pool = 32: the (rows / 32, cout) gradient of the pooled maxima beside zmax / ties of
@@ -707,9 +701,9 @@ int pn2_bn_grad_constants(long long rows, int c, const float *dz, const float *y
                           const float *ties, const float *ysel, int stats_done, void *workspace, size_t workspace_bytes,
                           float *coef, float *dgamma, float *dbeta, void *stream);
 /* pn2_bn_relu_forward with pool > 1 that also keeps ysel (rows / pool, c) = the pre-normalisation value of the first row that
- * attains each pooled maximum (stats_mode 3: sums there and folded, see pn2_linear_bn_stats_fin).  With it (pn2_bn_grad_constants(..., ysel != NULL, stats_done = 0)) the backward reduction behind
+ * attains each pooled maximum.  With it (pn2_bn_grad_constants(..., ysel != NULL, stats_done = 0)) the backward reduction behind
  * the max pool reads the pooled tensors only -- the gradient is non-zero on the rows attaining the maximum, all of which carry
- * zmax -- instead of making a pass over y (rows, c).  stats_mode 0 / 1 / 2 = pn2_bn_relu_forward / _ws0 / _stats. */
+ * zmax -- instead of making a pass over y (rows, c).  pool > 1 and ysel are required; stats_mode: a PN2_BN_WS_* state. */
 int pn2_bn_relu_forward_pool(long long rows, int c, const float *y, const float *gamma, const float *beta, const float *bias,
                              float eps, float decay, int relu, int pool, float *running_mean, float *running_var,
                              void *workspace, size_t workspace_bytes, int stats_mode, float *save_mean, float *save_invstd,
@@ -726,16 +720,16 @@ int pn2_linear_wgrad_gx(int rows, int cin, int cout, const float *x, const float
  * the slot copies of the sums and derives per-channel constants (45 launches of ~5 us per training step, all on the critical
  * path).  The producers below take a two-level ticket per workgroup instead, and the workgroup that draws the last one does that
  * work inside the producing launch.
- *   pn2_linear_bn_stats_fin: pn2_linear_bn_stats (a_scale == NULL) / pn2_linear_bn_stats_xf + finish 1: fold (then
- *     pn2_bn_relu_forward_mode / pn2_bn_relu_forward_pool with stats_mode 3), or 2: fold + what pn2_bn_relu_forward_deferred
- *     publishes (save_mean, save_invstd, moving averages, scale / shift; scale == shift == NULL: not wanted).
+ *   pn2_linear_bn_stats_fin: pn2_linear_bn_stats (a_scale == NULL) / pn2_linear_bn_stats_xf + finish 1: fold (the
+ *     workspace is then PN2_BN_WS_FOLDED for pn2_bn_relu_forward_mode / pn2_bn_relu_forward_pool), or 2: fold + what
+ *     pn2_bn_relu_forward_deferred publishes (save_mean, save_invstd, moving averages, scale / shift; both NULL: not wanted).
  *   pn2_linear_dgrad_fin: pn2_linear_dgrad (dy given, y == NULL) / pn2_linear_dgrad_gx (dy == NULL) + the epilogue of
- *     pn2_linear_dgrad_bn_grad_stats for the layer below (y_below != NULL) + finish_below 0: none, 1: fold (then
- *     pn2_bn_relu_backward_mode with stats_mode 3), 3: fold + what pn2_bn_grad_constants publishes for the layer below.
+ *     pn2_linear_dgrad_bn_grad_stats for the layer below (y_below != NULL) + finish_below 0: none, 1: fold (the
+ *     workspace is then PN2_BN_WS_FOLDED for pn2_bn_relu_backward_mode), 3: fold + what pn2_bn_grad_constants publishes there.
  *   pn2_bn_relu_forward_mode / pn2_bn_relu_backward_mode: pn2_bn_relu_forward (pool = 0) / pn2_bn_relu_backward with the state
- *     of the workspace explicit: 0 zero it here, 1 caller zeroed it, 2 sums already there, 3 sums there and folded.
- * (pn2_bn_relu_forward_deferred with stats_done = 0, pn2_bn_relu_forward / _backward in modes 0 / 1 and pn2_bn_grad_constants
- * with stats_done = 0 finish inside their own reduction kernel; no signature changes.)  Reference: tf_util.py:186-204,555-581. */
+ *     of the workspace given as stats_mode (a PN2_BN_WS_* state; SUMMED and FOLDED need pool <= 1 in the backward).
+ * (pn2_bn_relu_forward_deferred and pn2_bn_grad_constants with stats_done = 0 and the UNCLEARED / ZEROED batch-norm calls
+ * finish inside their own reduction kernel; no signature changes.)  Reference: tf_util.py:186-204,555-581. */
 int pn2_linear_bn_stats_fin(int rows, int cin, int cout, const float *x, const float *w, float *y, void *bn_workspace,
                             size_t workspace_bytes, const float *a_scale, const float *a_shift, int a_relu, int finish,
                             const float *gamma, const float *beta, const float *bias, float eps, float decay,
@@ -794,7 +788,7 @@ int pn2_fp_hoist_rows(int b, int n, int m, int c1, int cout, const float *dist, 
 /* The same two with the batch statistics of y (tf_util.py:186-204: conv2d -> batch_norm_template) taken on the way out: every
  * workgroup adds its column sums of y and y^2 (fp64) to one of the slot copies of the ZEROED batch-norm workspace
  * (pn2_bn_workspace_bytes(cout)), so no statistics pass reads y again; finish = 0: the copies are left there
- * (pn2_bn_relu_forward_stats / _deferred with stats_done = 1 fold them), 1: the last workgroup folds them, 2: it also publishes what
+ * (PN2_BN_WS_SUMMED), 1: the last workgroup folds them (PN2_BN_WS_FOLDED), 2: it also publishes what
  * pn2_bn_relu_forward_deferred publishes (save_mean / save_invstd, the moving averages, scale / shift) -- the arguments of
  * pn2_linear_bn_stats_fin.  r06: the hoisted first layers of SA2-SA4 / FP4 in training are one launch less each. */
 int pn2_sa_hoist_rows_bn(int b, int n, int m, int nsample, int cout, const float *xyz, const float *new_xyz, const int *idx,

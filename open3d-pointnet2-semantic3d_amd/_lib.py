@@ -70,10 +70,6 @@ SIGNATURES = {
                                          ctypes.c_size_t, c_void_p],
     "pn2_sa_group_concat": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_void_p, c_void_p],
-    "pn2_bn_relu_forward_ws0": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int,
-                            c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_bn_relu_backward_ws0": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                             c_int, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
     "pn2_mlp_wide": [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "pn2_sa_mlp_wide": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                         c_void_p, c_int, c_void_p, c_void_p],
@@ -88,8 +84,6 @@ SIGNATURES = {
     "pn2_scatter_plan_apply_multi": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p],
     "pn2_linear_bn_stats": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p],
-    "pn2_bn_relu_forward_stats": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int,
-                              c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "pn2_linear_wgrad_accumulate": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "pn2_linear_dgrad": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "pn2_bn_relu_forward_deferred": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int,
@@ -109,8 +103,6 @@ SIGNATURES = {
                                    c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "pn2_linear_dgrad_bn_grad_stats": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p],
-    "pn2_bn_relu_backward_stats": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                   c_int, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
     "pn2_linear_bn_stats_fin": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p,
                                 c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p],
@@ -179,6 +171,8 @@ SIGNATURES = {
                            c_void_p, c_void_p, c_void_p],
 }
 PN2_EUNSUP = -4
+# state of a batch-norm workspace when a call arrives: PN2_BN_WS_* of include/pn2_abi.h (the stats_mode argument)
+BN_WS_UNCLEARED, BN_WS_ZEROED, BN_WS_SUMMED, BN_WS_FOLDED = range(4)
 # workspace-size queries (-> size_t): name -> number of int arguments
 _SIZE_QUERIES = {"pn2_fps_large_workspace_bytes": 2, "pn2_ball_query_bin_bytes": 1, "pn2_interpolate_label_workspace_bytes": 1,
                  "pn2_three_interpolate_grad_workspace_bytes": 3, "pn2_scatter_plan_bytes": 3,
@@ -241,7 +235,7 @@ def _load():
     lib.pn2_build_info.restype = ctypes.c_char_p
     lib.pn2_strerror.restype = ctypes.c_char_p
     lib.pn2_strerror.argtypes = [c_int]
-    if lib.pn2_abi_version() != 1:
+    if lib.pn2_abi_version() != 2:
         raise ImportError("libpn2_hip.so ABI version mismatch")
     return lib
 
@@ -250,7 +244,7 @@ _raw = _load()
 
 
 # entry points that mutate caller state beyond their outputs (moving averages, optimizer slots): never launched twice by the dup hook
-_STATEFUL = frozenset({"pn2_bn_relu_forward", "pn2_bn_relu_forward_ws0", "pn2_bn_relu_forward_stats", "pn2_linear_bn_stats",
+_STATEFUL = frozenset({"pn2_bn_relu_forward", "pn2_linear_bn_stats",
                        "pn2_bn_relu_forward_pool", "pn2_bn_relu_forward_deferred", "pn2_linear_bn_stats_xf", "pn2_linear_wgrad_gx",
                        "pn2_linear_wgrad_accumulate_xf", "pn2_bn_grad_constants", "pn2_linear_dgrad_gx", "pn2_linear_dgrad_fin",
                        "pn2_linear_bn_stats_fin", "pn2_bn_relu_forward_mode", "pn2_sa_first_layer_bn", "pn2_sa_hoist_rows_bn", "pn2_fp_hoist_rows_bn", "pn2_sa_hoist_rows_multi_bn", "pn2_linear_bwd_fused", "pn2_linear_dgrad_bn_grad_stats",

@@ -91,7 +91,7 @@ __device__ __forceinline__ void bn_block_sums(const BnMap<VEC>& mp, int c, int n
 
 // final[col] = sum over the slot copies, as a launch of its own.  The fallback only: the producers of the sums fold them
 // themselves -- their last workgroup does, pn2_bn_finish in pn2_common.h -- and this kernel runs where the producer did not
-// finish (mode 2: the GEMM that added the sums ran without a finish).  The kernel boundary gives it the ordering for free.
+// finish (PN2_BN_WS_SUMMED: the GEMM that added the sums ran without a finish).  The kernel boundary gives it the ordering for free.
 // (Eight threads per column with all their copies in flight at once measured the same 4.9 us per launch: the duration of
 // this kernel is a fixed cost, not its eight dependent L2 round trips.)
 __global__ void __launch_bounds__(kBnThreads)
@@ -632,15 +632,16 @@ extern "C" int pn2_debug_set_bn(int what, int value) {
 }
 #endif  // PN2_TUNING_HOOKS
 
+static bool bn_ws_state_known(int state) { return state >= PN2_BN_WS_UNCLEARED && state <= PN2_BN_WS_FOLDED; }
+
 extern "C" size_t pn2_bn_workspace_bytes(int c) { return c > 0 ? sizeof(double) * bn_ws_doubles(c, kBnSlots) : 0; }
 
 static int bn_relu_forward_impl(long long rows, int c, const float* y, const float* gamma, const float* beta,
                                 const float* bias, float eps, float decay, int relu, int pool, float* running_mean,
                                 float* running_var, void* workspace, size_t workspace_bytes, float* save_mean,
-                                float* save_invstd, float* z, float* ties, void* stream, int mode, float* ysel = nullptr) {
-    // mode 0: zero the workspace here; 1: the caller zeroed it; 2: the caller zeroed it AND pn2_linear_bn_stats has already
-    // added the column sums of y to all kBnSlots slot copies (no statistics pass); 3: ... and the GEMM's last workgroup has folded
-    // them too (pn2_linear_bn_stats_fin): only the normalisation is left
+                                float* save_invstd, float* z, float* ties, void* stream, int state, float* ysel = nullptr) {
+    // state: PN2_BN_WS_* (include/pn2_abi.h).  summed: a producer has left the sums in all kBnSlots copies, no reduction pass here
+    const bool summed = state >= PN2_BN_WS_SUMMED;
     if (!y || !gamma || !beta || !workspace || !save_mean || !save_invstd || !z) return PN2_ENULL;
     if ((running_mean == nullptr) != (running_var == nullptr)) return PN2_ENULL;
     if (pool > 1 && !ties) return PN2_ENULL;
@@ -648,15 +649,15 @@ static int bn_relu_forward_impl(long long rows, int c, const float* y, const flo
     BnPlan p;
     const int rc = bn_plan(rows, c, y, z, ties, p);
     if (rc != PN2_OK) return rc;
-    if (workspace_bytes < pn2_bn_workspace_bytes(c) || ((uintptr_t)workspace % 8) != 0) return PN2_EINVAL;
+    if (!pn2_bn_ws_fits(workspace, workspace_bytes, c)) return PN2_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* ws = static_cast<double*>(workspace);
     const double* acc = ws + kBnHead;
-    if (mode == 0) {
+    if (state == PN2_BN_WS_UNCLEARED) {
         hipError_t e = hipMemsetAsync(ws, 0, sizeof(double) * bn_ws_doubles(c, p.nslots), st);
         if (e != hipSuccess) return (int)e;
     }
-    if (mode >= 2) p.nslots = kBnSlots;
+    if (summed) p.nslots = kBnSlots;
     const int fold_blocks = (2 * c + kBnThreads - 1) / kBnThreads;
     const Pn2BnFinish fin = bn_finish_fold(rows, c, p.nslots, ws);  // the statistics kernel's last workgroup folds the copies
     long long pb = 1;  // pooled apply: one group per (thread row slot), grid-stride beyond 8 blocks per CU
@@ -667,8 +668,8 @@ static int bn_relu_forward_impl(long long rows, int c, const float* y, const flo
     }
 #define PN2_BN_FWD(V_)                                                                                                   \
     do {                                                                                                                 \
-        if (mode < 2) bn_stats_kernel<V_><<<p.stat_blocks, kBnThreads, 0, st>>>(rows, c, p.slab, p.nslots, y, ws, fin);   \
-        if (mode == 2) bn_fold_kernel<<<fold_blocks, kBnThreads, 0, st>>>(2 * c, p.nslots, ws);                           \
+        if (!summed) bn_stats_kernel<V_><<<p.stat_blocks, kBnThreads, 0, st>>>(rows, c, p.slab, p.nslots, y, ws, fin);   \
+        if (state == PN2_BN_WS_SUMMED) bn_fold_kernel<<<fold_blocks, kBnThreads, 0, st>>>(2 * c, p.nslots, ws);           \
         if (pool > 1)                                                                                                    \
             bn_apply_pool_kernel<V_><<<(int)pb, kBnThreads, 0, st>>>(rows, c, pool, y, acc, gamma, beta, bias, eps, decay, \
                                                                    relu, running_mean, running_var, save_mean,           \
@@ -690,45 +691,25 @@ extern "C" int pn2_bn_relu_forward(long long rows, int c, const float* y, const 
                                    float* running_var, void* workspace, size_t workspace_bytes, float* save_mean,
                                    float* save_invstd, float* z, float* ties, void* stream) {
     return bn_relu_forward_impl(rows, c, y, gamma, beta, bias, eps, decay, relu, pool, running_mean, running_var, workspace,
-                                workspace_bytes, save_mean, save_invstd, z, ties, stream, 0);
-}
-// the same with a workspace the CALLER has already zero-filled (one fill of an arena that holds the scratch of every layer
-// of a training step replaces one memset per call)
-extern "C" int pn2_bn_relu_forward_ws0(long long rows, int c, const float* y, const float* gamma, const float* beta,
-                                       const float* bias, float eps, float decay, int relu, int pool, float* running_mean,
-                                       float* running_var, void* workspace, size_t workspace_bytes, float* save_mean,
-                                       float* save_invstd, float* z, float* ties, void* stream) {
-    return bn_relu_forward_impl(rows, c, y, gamma, beta, bias, eps, decay, relu, pool, running_mean, running_var, workspace,
-                                workspace_bytes, save_mean, save_invstd, z, ties, stream, 1);
-}
-// the same for a y produced by pn2_linear_bn_stats with this workspace: the column sums are already there
-extern "C" int pn2_bn_relu_forward_stats(long long rows, int c, const float* y, const float* gamma, const float* beta,
-                                         const float* bias, float eps, float decay, int relu, int pool, float* running_mean,
-                                         float* running_var, void* workspace, size_t workspace_bytes, float* save_mean,
-                                         float* save_invstd, float* z, float* ties, void* stream) {
-    return bn_relu_forward_impl(rows, c, y, gamma, beta, bias, eps, decay, relu, pool, running_mean, running_var, workspace,
-                                workspace_bytes, save_mean, save_invstd, z, ties, stream, 2);
+                                workspace_bytes, save_mean, save_invstd, z, ties, stream, PN2_BN_WS_UNCLEARED);
 }
 
 // pn2_bn_relu_forward with pool > 1 that also keeps ysel (rows / pool, c): the pre-normalisation value of the first row attaining
 // each pooled maximum -- what lets the backward take its reduction from the pooled tensors alone (pn2_bn_grad_constants).
-// stats_mode 0: zero the workspace here; 1: the caller zeroed it; 2: pn2_linear_bn_stats already left the column sums in it;
-// 3: pn2_linear_bn_stats_fin left them there AND folded.
 extern "C" int pn2_bn_relu_forward_pool(long long rows, int c, const float* y, const float* gamma, const float* beta,
                                         const float* bias, float eps, float decay, int relu, int pool, float* running_mean,
                                         float* running_var, void* workspace, size_t workspace_bytes, int stats_mode,
                                         float* save_mean, float* save_invstd, float* zmax, float* ties, float* ysel,
                                         void* stream) {
-    if (pool <= 1 || stats_mode < 0 || stats_mode > 3) return PN2_EINVAL;
+    if (pool <= 1 || !bn_ws_state_known(stats_mode)) return PN2_EINVAL;
     if (!ysel) return PN2_ENULL;
     if ((c % 4 == 0) && ((uintptr_t)ysel % 16) != 0) return PN2_EINVAL;
     return bn_relu_forward_impl(rows, c, y, gamma, beta, bias, eps, decay, relu, pool, running_mean, running_var, workspace,
                                 workspace_bytes, save_mean, save_invstd, zmax, ties, stream, stats_mode, ysel);
 }
 
-// Batch norm of the training path WITHOUT writing the normalised activation: the statistics (stats_done = 1: already left in
-// the zeroed workspace by pn2_linear_bn_stats; 0: taken here with one pass over y, workspace zeroed by the caller) are folded
-// and turned into save_mean / save_invstd, the moving averages and the per-channel (scale, shift) of
+// Batch norm of the training path WITHOUT writing the normalised activation: the statistics (stats_done = 1: the workspace is
+// PN2_BN_WS_SUMMED; 0: PN2_BN_WS_ZEROED, taken here with one pass over y) are folded and turned into save_mean / save_invstd, the moving averages and the per-channel (scale, shift) of
 // z = relu?(fma(y, scale, shift)); the consumer applies them while it loads y (pn2_linear_bn_stats_xf /
 // pn2_linear_wgrad_accumulate_xf), so the write and the re-read of z disappear.  tf_util.py:555-581 followed by :186-204 of the
 // next layer.
@@ -741,7 +722,7 @@ extern "C" int pn2_bn_relu_forward_deferred(long long rows, int c, const float* 
     BnPlan p;
     const int rc = bn_plan(rows, c, y, y, y, p);
     if (rc != PN2_OK) return rc;
-    if (workspace_bytes < pn2_bn_workspace_bytes(c) || ((uintptr_t)workspace % 8) != 0) return PN2_EINVAL;
+    if (!pn2_bn_ws_fits(workspace, workspace_bytes, c)) return PN2_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* ws = static_cast<double*>(workspace);
     if (stats_done) {
@@ -765,35 +746,34 @@ extern "C" int pn2_bn_relu_forward_deferred(long long rows, int c, const float* 
 static int bn_relu_backward_impl(long long rows, int c, const float* dz, const float* y, const float* gamma,
                                  const float* beta, const float* save_mean, const float* save_invstd, int relu,
                                  int pool, const float* zmax, const float* ties, void* workspace,
-                                 size_t workspace_bytes, float* dy, float* dgamma, float* dbeta, void* stream, int mode) {
-    // mode 0: zero the workspace here; 1: the caller zeroed it; 2: the caller zeroed it AND pn2_linear_dgrad_bn_grad_stats has
-    // already added (sum g, sum g * xhat) to all kBnSlots slot copies while it produced dz (no reduction pass; pool <= 1);
-    // 3: ... and that GEMM's last workgroup has folded them (pn2_linear_dgrad_fin, finish kind 1)
+                                 size_t workspace_bytes, float* dy, float* dgamma, float* dbeta, void* stream, int state) {
+    // state: PN2_BN_WS_* (include/pn2_abi.h).  summed: a producer has left the sums in all kBnSlots copies, no reduction pass here
+    const bool summed = state >= PN2_BN_WS_SUMMED;
     if (!dz || !y || !gamma || !beta || !save_mean || !save_invstd || !workspace || !dy || !dgamma || !dbeta) return PN2_ENULL;
     if (pool > 1 && (!zmax || !ties)) return PN2_ENULL;
     if (pool > 1 && (rows % pool != 0 || dy == dz)) return PN2_EINVAL;
-    if (mode >= 2 && pool > 1) return PN2_EINVAL;
+    if (summed && pool > 1) return PN2_EINVAL;
     BnPlan p;
     int rc = bn_plan(rows, c, dz, y, dy, p);
     if (rc != PN2_OK) return rc;
     if (pool > 1 && p.vec == 4 && (((uintptr_t)zmax | (uintptr_t)ties) % 16) != 0) return PN2_EINVAL;
-    if (workspace_bytes < pn2_bn_workspace_bytes(c) || ((uintptr_t)workspace % 8) != 0) return PN2_EINVAL;
+    if (!pn2_bn_ws_fits(workspace, workspace_bytes, c)) return PN2_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* ws = static_cast<double*>(workspace);
     const double* acc = ws + kBnHead;
-    if (mode == 0) {
+    if (state == PN2_BN_WS_UNCLEARED) {
         hipError_t e = hipMemsetAsync(ws, 0, sizeof(double) * bn_ws_doubles(c, p.nslots), st);
         if (e != hipSuccess) return (int)e;
     }
-    if (mode >= 2) p.nslots = kBnSlots;
+    if (summed) p.nslots = kBnSlots;
     const int fold_blocks = (2 * c + kBnThreads - 1) / kBnThreads;
     const Pn2BnFinish fin = bn_finish_fold(rows, c, p.nslots, ws);  // the reduction's last workgroup folds the copies
 #define PN2_BN_BWD(V_)                                                                                                  \
     do {                                                                                                                \
-        if (mode < 2)                                                                                                   \
+        if (!summed)                                                                                                    \
             bn_grad_reduce_kernel<V_><<<p.stat_blocks, kBnThreads, 0, st>>>(rows, c, p.slab, p.nslots, dz, y, gamma, beta, \
                                                                           save_mean, save_invstd, relu, pool, zmax, ties, ws, fin); \
-        if (mode == 2) bn_fold_kernel<<<fold_blocks, kBnThreads, 0, st>>>(2 * c, p.nslots, ws);                          \
+        if (state == PN2_BN_WS_SUMMED) bn_fold_kernel<<<fold_blocks, kBnThreads, 0, st>>>(2 * c, p.nslots, ws);          \
         bn_grad_apply_kernel<V_><<<p.apply_blocks, kBnThreads, 0, st>>>(rows, c, dz, y, acc, gamma, beta, save_mean,     \
                                                                       save_invstd, relu, pool, zmax, ties, dy, dgamma,  \
                                                                       dbeta);                                           \
@@ -810,27 +790,11 @@ extern "C" int pn2_bn_relu_backward(long long rows, int c, const float* dz, cons
                                     int pool, const float* zmax, const float* ties, void* workspace,
                                     size_t workspace_bytes, float* dy, float* dgamma, float* dbeta, void* stream) {
     return bn_relu_backward_impl(rows, c, dz, y, gamma, beta, save_mean, save_invstd, relu, pool, zmax, ties, workspace,
-                                 workspace_bytes, dy, dgamma, dbeta, stream, 0);
-}
-extern "C" int pn2_bn_relu_backward_ws0(long long rows, int c, const float* dz, const float* y, const float* gamma,
-                                        const float* beta, const float* save_mean, const float* save_invstd, int relu,
-                                        int pool, const float* zmax, const float* ties, void* workspace,
-                                        size_t workspace_bytes, float* dy, float* dgamma, float* dbeta, void* stream) {
-    return bn_relu_backward_impl(rows, c, dz, y, gamma, beta, save_mean, save_invstd, relu, pool, zmax, ties, workspace,
-                                 workspace_bytes, dy, dgamma, dbeta, stream, 1);
-}
-// the same for a dz produced by pn2_linear_dgrad_bn_grad_stats with this workspace: the two sums are already there
-extern "C" int pn2_bn_relu_backward_stats(long long rows, int c, const float* dz, const float* y, const float* gamma,
-                                          const float* beta, const float* save_mean, const float* save_invstd, int relu,
-                                          int pool, const float* zmax, const float* ties, void* workspace,
-                                          size_t workspace_bytes, float* dy, float* dgamma, float* dbeta, void* stream) {
-    return bn_relu_backward_impl(rows, c, dz, y, gamma, beta, save_mean, save_invstd, relu, pool, zmax, ties, workspace,
-                                 workspace_bytes, dy, dgamma, dbeta, stream, 2);
+                                 workspace_bytes, dy, dgamma, dbeta, stream, PN2_BN_WS_UNCLEARED);
 }
 
-// The batch-norm gradient WITHOUT writing dy: the two per-channel sums (stats_done = 1: already left in the zeroed workspace by
-// pn2_linear_dgrad_bn_grad_stats; 0: taken here with one pass over (dz, y), workspace zeroed by the caller) are folded into dgamma,
-// dbeta and coef (6, c) = sc, sh, mean, invstd, k1, k2; the layer's data and weight gradient GEMMs apply them while they load
+// The batch-norm gradient WITHOUT writing dy: the two per-channel sums (stats_done = 1: the workspace is PN2_BN_WS_SUMMED;
+// 0: PN2_BN_WS_ZEROED, taken here with one pass over (dz, y)) are folded into dgamma, dbeta and coef (6, c) = sc, sh, mean, invstd, k1, k2; the layer's data and weight gradient GEMMs apply them while they load
 // (y, dz) (pn2_linear_dgrad_gx / pn2_linear_wgrad_gx), so the write of dy and its two re-reads disappear.  pool as in
 // pn2_bn_relu_backward.  util/tf_util.py:555-581 via tf.gradients.
 extern "C" int pn2_bn_grad_constants(long long rows, int c, const float* dz, const float* y, const float* gamma, const float* beta,
@@ -845,7 +809,7 @@ extern "C" int pn2_bn_grad_constants(long long rows, int c, const float* dz, con
     const int rc = bn_plan(rows, c, dz, y, y, p);
     if (rc != PN2_OK) return rc;
     if (pool > 1 && p.vec == 4 && (((uintptr_t)zmax | (uintptr_t)ties) % 16) != 0) return PN2_EINVAL;
-    if (workspace_bytes < pn2_bn_workspace_bytes(c) || ((uintptr_t)workspace % 8) != 0) return PN2_EINVAL;
+    if (!pn2_bn_ws_fits(workspace, workspace_bytes, c)) return PN2_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* ws = static_cast<double*>(workspace);
     if (stats_done) {
@@ -884,14 +848,12 @@ extern "C" int pn2_bn_grad_constants(long long rows, int c, const float* dz, con
     return PN2_OK;
 }
 
-// pn2_bn_relu_forward / pn2_bn_relu_backward with the state of the workspace given explicitly (the numbered modes of the two
-// implementations above; 3 = the sums are there AND folded, left by pn2_linear_bn_stats_fin / pn2_linear_dgrad_fin with finish
-// kind 1): the one-block fold launch between a GEMM and the normalisation pass is gone.
+// pn2_bn_relu_forward / pn2_bn_relu_backward with the state of the workspace given explicitly (stats_mode: PN2_BN_WS_*)
 extern "C" int pn2_bn_relu_forward_mode(long long rows, int c, const float* y, const float* gamma, const float* beta,
                                         const float* bias, float eps, float decay, int relu, float* running_mean,
                                         float* running_var, void* workspace, size_t workspace_bytes, int stats_mode,
                                         float* save_mean, float* save_invstd, float* z, void* stream) {
-    if (stats_mode < 0 || stats_mode > 3) return PN2_EINVAL;
+    if (!bn_ws_state_known(stats_mode)) return PN2_EINVAL;
     return bn_relu_forward_impl(rows, c, y, gamma, beta, bias, eps, decay, relu, 0, running_mean, running_var, workspace,
                                 workspace_bytes, save_mean, save_invstd, z, nullptr, stream, stats_mode);
 }
@@ -900,15 +862,15 @@ extern "C" int pn2_bn_relu_backward_mode(long long rows, int c, const float* dz,
                                          int pool, const float* zmax, const float* ties, void* workspace,
                                          size_t workspace_bytes, int stats_mode, float* dy, float* dgamma, float* dbeta,
                                          void* stream) {
-    if (stats_mode < 0 || stats_mode > 3) return PN2_EINVAL;
+    if (!bn_ws_state_known(stats_mode)) return PN2_EINVAL;
     return bn_relu_backward_impl(rows, c, dz, y, gamma, beta, save_mean, save_invstd, relu, pool, zmax, ties, workspace,
                                  workspace_bytes, dy, dgamma, dbeta, stream, stats_mode);
 }
 
 // First layer of an SA module with few point channels (c <= 5: the level-0 module's colours), training path, in ONE launch:
 // gather + centre + concat (pn2_sa_group_concat) + the (3 + c) -> cout product (tf_util.py:181-186) + the batch statistics of y
-// (workspace ZEROED by the caller) + their fold by the launch's last workgroup (finish 1; pn2_bn_relu_forward_mode /
-// pn2_bn_relu_forward_pool with stats_mode 3 normalise) or fold + the constants pn2_bn_relu_forward_deferred publishes
+// (workspace ZEROED by the caller) + their fold by the launch's last workgroup (finish 1, PN2_BN_WS_FOLDED: pn2_bn_relu_forward_mode /
+// pn2_bn_relu_forward_pool normalise) or fold + the constants pn2_bn_relu_forward_deferred publishes
 // (finish 2).  y (b, m, nsample, cout) un-normalised; xg (b, m, nsample, 3 + c), optional: the grouped input, operand of the
 // weight gradient.  cout % 4 == 0, cout <= 1024, 16-byte aligned w / y.
 extern "C" int pn2_sa_first_layer_bn(int b, int n, int m, int nsample, int c, int cout, const float* xyz, const float* new_xyz,
@@ -926,7 +888,7 @@ extern "C" int pn2_sa_first_layer_bn(int b, int n, int m, int nsample, int c, in
     const int rc = bn_plan(rows, cout, y, y, y, p);
     if (rc != PN2_OK) return rc;
     if (p.vec != 4) return PN2_EUNSUP;
-    if (workspace_bytes < pn2_bn_workspace_bytes(cout) || ((uintptr_t)workspace % 8) != 0) return PN2_EINVAL;
+    if (!pn2_bn_ws_fits(workspace, workspace_bytes, cout)) return PN2_EINVAL;
     double* ws = static_cast<double*>(workspace);
     Pn2BnFinish f{};
     f.kind = finish; f.c = cout; f.nslots = p.nslots; f.rows = rows; f.ws = ws;

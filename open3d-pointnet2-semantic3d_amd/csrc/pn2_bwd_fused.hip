@@ -225,7 +225,7 @@ extern "C" int pn2_linear_bwd_fused(int rows, int cin, int cout, const float* x,
     Pn2BnFinish f{};
     if (y_below) {
         if (!gamma_below || !beta_below || !mean_below || !invstd_below || !ws_below) return PN2_ENULL;
-        if (ws_below_bytes < sizeof(double) * pn2_bn_ws_doubles(cin, kPn2BnSlots) || ((uintptr_t)ws_below % 8) != 0) return PN2_EINVAL;
+        if (!pn2_bn_ws_fits(ws_below, ws_below_bytes, cin)) return PN2_EINVAL;
         e = Pn2BnGradEpilogue{y_below, gamma_below, beta_below, mean_below, invstd_below, static_cast<double*>(ws_below), relu_below};
         if (finish_below != 0 && finish_below != 1 && finish_below != 3) return PN2_EINVAL;
         if (finish_below == 3 && (!coef_below || !dgamma_below || !dbeta_below)) return PN2_ENULL;

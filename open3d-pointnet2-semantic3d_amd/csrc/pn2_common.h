@@ -62,6 +62,10 @@ constexpr int kPn2BnTickets = 64;
 #endif
 constexpr int kPn2FoldDepth = PN2_FOLD_DEPTH;  // slot copies a folding thread keeps in flight (a device-scope load is a ~1 us round trip)
 __host__ __device__ inline size_t pn2_bn_ws_doubles(int c, int nslots) { return kPn2BnHead + (size_t)(1 + nslots) * 2 * (size_t)c; }
+// may `ws` (`bytes` long) serve as the workspace of c channels?  (pn2_bn_workspace_bytes(c) bytes, 8-byte aligned; NULL is the caller's check)
+inline bool pn2_bn_ws_fits(const void* ws, size_t bytes, int c) {
+    return c > 0 && bytes >= sizeof(double) * pn2_bn_ws_doubles(c, kPn2BnSlots) && ((uintptr_t)ws % 8) == 0;
+}
 
 // per-channel constants of the normalisation, identical float expressions in the forward and the backward kernels so
 // that the ReLU mask recomputed in the backward is the forward's: z = fma(y, sc, sh), sc = gamma*invstd,

@@ -259,7 +259,7 @@ static int hoist_stats_args(HoistParams& p, long long rows_total, int cout, void
                             float* running_var, float* save_mean, float* save_invstd, float* scale, float* shift) {
     if (!bn_workspace) return PN2_ENULL;
     if (finish < 0 || finish > 2) return PN2_EINVAL;
-    if (workspace_bytes < sizeof(double) * pn2_bn_ws_doubles(cout, kPn2BnSlots) || ((uintptr_t)bn_workspace % 8) != 0) return PN2_EINVAL;
+    if (!pn2_bn_ws_fits(bn_workspace, workspace_bytes, cout)) return PN2_EINVAL;
     p.stats_ws = static_cast<double*>(bn_workspace);
     p.nslots = kPn2BnSlots;
     Pn2BnFinish f{};

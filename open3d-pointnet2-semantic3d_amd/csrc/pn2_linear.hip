@@ -1069,13 +1069,12 @@ extern "C" int pn2_linear_narrow(int rows, int cin, int cout, const float* x, co
 
 // y = x . w (no bias, no activation) AND the per-column sums the following training-mode batch norm needs (tf_util.py:186-204:
 // conv2d -> batch_norm_template): every wave adds its tile's column sums of y and y^2 (16 fp32 terms per lane, then fp64) to
-// one of kPn2BnSlots copies of the accumulators in `bn_workspace` (pn2_bn_workspace_bytes(cout), ZEROED by the caller);
-// pn2_bn_relu_forward_stats folds the copies and normalises.  Saves the statistics pass over y.
+// one of kPn2BnSlots copies of the accumulators in `bn_workspace` (pn2_bn_workspace_bytes(cout), ZEROED by the caller), which is
+// then PN2_BN_WS_SUMMED: pn2_bn_relu_forward_mode folds the copies and normalises.  Saves the statistics pass over y.
 extern "C" int pn2_linear_bn_stats(int rows, int cin, int cout, const float* x, const float* w, float* y,
                                    void* bn_workspace, size_t workspace_bytes, void* stream) {
     if (!bn_workspace) return PN2_ENULL;
-    if (cout <= 0 || workspace_bytes < sizeof(double) * pn2_bn_ws_doubles(cout, kPn2BnSlots) || ((uintptr_t)bn_workspace % 8) != 0)
-        return PN2_EINVAL;
+    if (!pn2_bn_ws_fits(bn_workspace, workspace_bytes, cout)) return PN2_EINVAL;
     return linear_impl(rows, cin, cout, x, w, nullptr, 0, 0, y, stream, static_cast<double*>(bn_workspace));
 }
 
@@ -1088,7 +1087,7 @@ static int linear_bn_stats_xf_impl(int rows, int cin, int cout, const float* x_r
                                    int a_relu, void* stream, const Pn2BnFinish* fin) {
     if (rows <= 0 || cin <= 0 || cout <= 0) return PN2_EINVAL;
     if (!x_raw || !w || !y || !bn_workspace || !a_scale || !a_shift) return PN2_ENULL;
-    if (workspace_bytes < sizeof(double) * pn2_bn_ws_doubles(cout, kPn2BnSlots) || ((uintptr_t)bn_workspace % 8) != 0) return PN2_EINVAL;
+    if (!pn2_bn_ws_fits(bn_workspace, workspace_bytes, cout)) return PN2_EINVAL;
     if (cout % 32 != 0 || cin % 4 != 0 || rows <= 2048) return PN2_EUNSUP;
     if ((((uintptr_t)x_raw | (uintptr_t)w | (uintptr_t)a_scale | (uintptr_t)a_shift) % 16) != 0) return PN2_EUNSUP;
     if ((long long)rows + 128 > 0x7fffffffLL) return PN2_ERANGE;
@@ -1120,8 +1119,8 @@ extern "C" int pn2_linear_bn_stats_xf(int rows, int cin, int cout, const float* 
 }
 
 // pn2_linear_bn_stats (a_scale == NULL) / pn2_linear_bn_stats_xf whose LAST WORKGROUP also does what used to be the next launch
-// (pn2_common.h pn2_bn_finish): finish = 1 folds the slot copies of the column sums (then pn2_bn_relu_forward_mode /
-// pn2_bn_relu_forward_pool with stats_mode 3 normalise); finish = 2 also derives what pn2_bn_relu_forward_deferred publishes --
+// (pn2_common.h pn2_bn_finish): finish = 1 folds the slot copies of the column sums (PN2_BN_WS_FOLDED: pn2_bn_relu_forward_mode /
+// pn2_bn_relu_forward_pool normalise); finish = 2 also derives what pn2_bn_relu_forward_deferred publishes --
 // save_mean / save_invstd, the moving averages, per-channel (scale, shift) -- so a layer that hands its un-normalised output on
 // is ONE launch.  tf_util.py:186-204 + :555-581.
 extern "C" int pn2_linear_bn_stats_fin(int rows, int cin, int cout, const float* x, const float* w, float* y, void* bn_workspace,
@@ -1131,8 +1130,7 @@ extern "C" int pn2_linear_bn_stats_fin(int rows, int cin, int cout, const float*
                                        float* save_invstd, float* scale, float* shift, void* stream) {
     if (!bn_workspace) return PN2_ENULL;
     if (finish != 1 && finish != 2) return PN2_EINVAL;
-    if (cout <= 0 || workspace_bytes < sizeof(double) * pn2_bn_ws_doubles(cout, kPn2BnSlots) || ((uintptr_t)bn_workspace % 8) != 0)
-        return PN2_EINVAL;
+    if (!pn2_bn_ws_fits(bn_workspace, workspace_bytes, cout)) return PN2_EINVAL;
     if ((a_scale == nullptr) != (a_shift == nullptr)) return PN2_ENULL;
     Pn2BnFinish f{};
     f.kind = finish; f.c = cout; f.nslots = kPn2BnSlots; f.rows = rows; f.ws = static_cast<double*>(bn_workspace);
@@ -1194,7 +1192,7 @@ extern "C" int pn2_linear_dgrad(int rows, int cin, int cout, const float* dy, co
 // layer that produced this layer's input): y_below (rows, cin) is that layer's pre-normalisation output, gamma / beta /
 // save_mean / save_invstd its batch-norm parameters and saved moments.  While the accumulator tiles of dx are at hand the
 // kernel adds sum g and sum g * xhat per channel (g = dx * [relu mask]) to the ZEROED batch-norm workspace of that layer
-// (pn2_bn_workspace_bytes(cin)); pn2_bn_relu_backward_stats then skips its reduction pass over (dz, y) -- one of the two
+// (pn2_bn_workspace_bytes(cin)), then PN2_BN_WS_SUMMED; pn2_bn_relu_backward_mode skips its reduction pass over (dz, y) -- one of the two
 // passes of the reference's batch-norm gradient (util/tf_util.py:555-581 via tf.gradients).  PN2_EUNSUP for cout <= 16
 // (streaming kernel): call pn2_linear_dgrad + pn2_bn_relu_backward.
 extern "C" int pn2_linear_dgrad_bn_grad_stats(int rows, int cin, int cout, const float* dy, const float* w, float* dx,
@@ -1202,8 +1200,7 @@ extern "C" int pn2_linear_dgrad_bn_grad_stats(int rows, int cin, int cout, const
                                               const float* save_mean, const float* save_invstd, int relu,
                                               void* bn_workspace, size_t workspace_bytes, void* stream) {
     if (!y_below || !gamma || !beta || !save_mean || !save_invstd || !bn_workspace) return PN2_ENULL;
-    if (cin <= 0 || workspace_bytes < sizeof(double) * pn2_bn_ws_doubles(cin, kPn2BnSlots) || ((uintptr_t)bn_workspace % 8) != 0)
-        return PN2_EINVAL;
+    if (!pn2_bn_ws_fits(bn_workspace, workspace_bytes, cin)) return PN2_EINVAL;
     Pn2BnGradEpilogue e{y_below, gamma, beta, save_mean, save_invstd, static_cast<double*>(bn_workspace), relu};
     return linear_dgrad_impl(rows, cin, cout, dy, w, dx, stream, e);
 }
@@ -1222,8 +1219,7 @@ extern "C" int pn2_linear_dgrad_gx(int rows, int cin, int cout, const float* y, 
     Pn2BnGradEpilogue e{};
     if (y_below) {
         if (!gamma_below || !beta_below || !mean_below || !invstd_below || !ws_below) return PN2_ENULL;
-        if (cin <= 0 || ws_below_bytes < sizeof(double) * pn2_bn_ws_doubles(cin, kPn2BnSlots) || ((uintptr_t)ws_below % 8) != 0)
-            return PN2_EINVAL;
+        if (!pn2_bn_ws_fits(ws_below, ws_below_bytes, cin)) return PN2_EINVAL;
         e = Pn2BnGradEpilogue{y_below, gamma_below, beta_below, mean_below, invstd_below, static_cast<double*>(ws_below), relu_below};
     }
     const Pn2GradOnLoad gx{y, dz, coef, zmax, ties, relu, pool};
@@ -1235,7 +1231,7 @@ extern "C" int pn2_linear_dgrad_gx(int rows, int cin, int cout, const float* y, 
 //   upstream gradient: dy (rows, cout) given (y == NULL) as in pn2_linear_dgrad, or formed on load from (y, dz, coef, relu, pool,
 //     zmax, ties) as in pn2_linear_dgrad_gx (dy == NULL);
 //   y_below != NULL: pn2_linear_dgrad_bn_grad_stats' epilogue for the layer below, and finish_below = 1: its slot copies folded
-//     (pn2_bn_relu_backward_mode with stats_mode 3 follows), 3: folded AND turned into coef_below (6, cin), dgamma_below,
+//     (PN2_BN_WS_FOLDED for pn2_bn_relu_backward_mode), 3: folded AND turned into coef_below (6, cin), dgamma_below,
 //     dbeta_below (what pn2_bn_grad_constants publishes), 0: left as they are.
 // A layer inside a stack then costs two launches in the backward pass (this + its weight gradient) instead of four.
 extern "C" int pn2_linear_dgrad_fin(int rows, int cin, int cout, const float* dy, const float* y, const float* dz,
@@ -1249,8 +1245,7 @@ extern "C" int pn2_linear_dgrad_fin(int rows, int cin, int cout, const float* dy
     Pn2BnFinish f{};
     if (y_below) {
         if (!gamma_below || !beta_below || !mean_below || !invstd_below || !ws_below) return PN2_ENULL;
-        if (cin <= 0 || ws_below_bytes < sizeof(double) * pn2_bn_ws_doubles(cin, kPn2BnSlots) || ((uintptr_t)ws_below % 8) != 0)
-            return PN2_EINVAL;
+        if (!pn2_bn_ws_fits(ws_below, ws_below_bytes, cin)) return PN2_EINVAL;
         e = Pn2BnGradEpilogue{y_below, gamma_below, beta_below, mean_below, invstd_below, static_cast<double*>(ws_below), relu_below};
         if (finish_below != 0 && finish_below != 1 && finish_below != 3) return PN2_EINVAL;
         if (finish_below == 3 && (!coef_below || !dgamma_below || !dbeta_below)) return PN2_ENULL;

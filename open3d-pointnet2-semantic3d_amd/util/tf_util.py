@@ -22,6 +22,7 @@ import weakref
 import torch
 import torch.nn.functional as F
 
+from .._lib import BN_WS_FOLDED, BN_WS_SUMMED, BN_WS_UNCLEARED, BN_WS_ZEROED
 from .._lib import int_array, launch, layer_arrays, lib, nbytes, ptr, ptr_table, require_cuda, rows_in_place, u64_array
 
 BN_EPSILON = 1e-3  # tf.contrib.layers.batch_norm default (tf_util.py:571-581)
@@ -514,7 +515,7 @@ def hip_matmul(x2d, w):
 
 def hip_matmul_bn_stats(x2d, w, ws):
     """y = x2d @ w on pn2_linear_bn_stats: the GEMM also leaves the column sums of y and y^2 in the ZEROED batch-norm
-    workspace `ws` (pn2_bn_workspace_bytes(cout) bytes) for pn2_bn_relu_forward_stats.  cout % 32 == 0."""
+    workspace `ws` (pn2_bn_workspace_bytes(cout) bytes), which is then BN_WS_SUMMED.  cout % 32 == 0."""
     require_cuda(x2d, w)
     rows, cin = x2d.shape
     cout = w.shape[1]
@@ -545,14 +546,14 @@ def hip_linear_dgrad(dy, w):
     return dx
 
 
-def _bn_scratch(c, device, fn, fn_ws0):
-    """batch-norm accumulators: a slice of the step's zero arena (+ the NAME of the entry point that trusts it) when there is one"""
+def _bn_scratch(c, device):
+    """batch-norm accumulators and their state (BN_WS_*): a slice of the step's zero arena when there is one, else uncleared memory"""
     nbytes = lib.pn2_bn_workspace_bytes(c)
     arena = get_default_store().zero_arena
     v = arena.take(nbytes) if arena is not None else None
     if v is not None:
-        return v, fn_ws0
-    return torch.empty(nbytes // 8, dtype=torch.float64, device=device), fn
+        return v, BN_WS_ZEROED
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device), BN_WS_UNCLEARED
 
 
 USE_GEMM_BN_STATS = True  # batch statistics from the forward GEMM's epilogue (set False: separate pass over y; tests / A-B)
@@ -716,7 +717,7 @@ def _train_dense(inputs, w2d, b, relu=False):
 # When the output z of a dense+BN(+ReLU) layer is consumed by exactly one other such layer, the gradient dz reaching the
 # batch norm is the dX of that consumer's data-gradient GEMM.  pn2_linear_dgrad_bn_grad_stats forms the two per-channel
 # sums of the batch-norm gradient (sum g, sum g * xhat) from its accumulator tiles, so the producer's backward skips the
-# reduction pass over (dz, y) (pn2_bn_relu_backward_stats).  The link is keyed by the storage address of z and checked
+# reduction pass over (dz, y) (pn2_bn_relu_backward_mode, BN_WS_SUMMED).  The link is keyed by the storage address of z and checked
 # again in the backward: only when the tensor arriving as dz IS the linked GEMM's output (a second consumer makes autograd
 # hand over a sum in a new tensor) is the shortcut taken.
 USE_DGRAD_BN_STATS = True
@@ -728,7 +729,7 @@ _bn_links = weakref.WeakValueDictionary()
 
 class _BnLink:
     __slots__ = ("shape", "y", "gamma", "beta", "mean", "invstd", "relu", "ws", "dz_ptr", "dz_keep", "sc", "sh", "consumed",
-                 "gx", "folded", "coef", "dgamma", "dbeta", "__weakref__")
+                 "gx", "ws_state", "coef", "dgamma", "dbeta", "__weakref__")
 
 
 # ---- deferred normalisation: layer i publishes (scale, shift) and hands its PRE-normalisation output y to layer i+1 -------
@@ -776,18 +777,15 @@ def hip_linear_dgrad_linked(dy, w, link):
     dx = torch.empty((rows, cin), dtype=torch.float32, device=dy.device)
     launch("pn2_linear_dgrad_bn_grad_stats", dy, rows, cin, w.shape[1], ptr(dy), ptr(w.contiguous()), ptr(dx), ptr(link.y),
            ptr(link.gamma), ptr(link.beta), ptr(link.mean), ptr(link.invstd), int(link.relu), ptr(pws), nbytes(pws))
-    link.ws, link.dz_ptr, link.dz_keep = pws, dx.data_ptr(), dx
+    link.ws, link.ws_state, link.dz_ptr, link.dz_keep = pws, BN_WS_SUMMED, dx.data_ptr(), dx
     return dx
 
 
-def _bn_train_forward(y, b, gamma, beta, running_mean, running_var, decay, relu, pool, stats_ws=None, folded=False):
-    """batch norm (+ReLU, + max over groups of `pool` rows) of a layer output y (rows, c) on pn2_bn_relu_forward; stats_ws: the
-    workspace pn2_linear_bn_stats has already left the column sums in.  -> z, ties, save_mean, save_invstd"""
+def _bn_train_forward(y, b, gamma, beta, running_mean, running_var, decay, relu, pool, stats=None):
+    """batch norm (+ReLU, + max over groups of `pool` rows) of a layer output y (rows, c); stats: (workspace, BN_WS_* state) from the
+    producer of y that has already left the column sums there.  -> z, ties, save_mean, save_invstd"""
     rows, c = y.shape
-    if stats_ws is not None:
-        ws, fwd = stats_ws, "pn2_bn_relu_forward_stats"
-    else:
-        ws, fwd = _bn_scratch(c, y.device, "pn2_bn_relu_forward", "pn2_bn_relu_forward_ws0")
+    ws, state = stats if stats is not None else _bn_scratch(c, y.device)
     pooled = pool > 1
     z = torch.empty((rows // pool, c) if pooled else (rows, c), dtype=y.dtype, device=y.device)
     save_mean = torch.empty(c, dtype=torch.float32, device=y.device)
@@ -798,25 +796,26 @@ def _bn_train_forward(y, b, gamma, beta, running_mean, running_var, decay, relu,
         # ties = [tie counts | ysel]: ysel = the pre-normalisation value of the first row attaining each maximum, which lets the
         # backward take its reduction from the pooled tensors (pn2_bn_grad_constants) instead of a pass over y
         ties = torch.empty((2,) + tuple(z.shape), dtype=y.dtype, device=y.device)
-        mode = (3 if folded else 2) if stats_ws is not None else (1 if fwd == "pn2_bn_relu_forward_ws0" else 0)
-        launch("pn2_bn_relu_forward_pool", y, *head, int(pool), ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), mode,
+        launch("pn2_bn_relu_forward_pool", y, *head, int(pool), ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), state,
                ptr(save_mean), ptr(save_invstd), ptr(z), ptr(ties[0]), ptr(ties[1]))
-    elif folded and stats_ws is not None:  # the GEMM's last workgroup has folded the sums: only the normalisation pass is left
-        launch("pn2_bn_relu_forward_mode", y, *head, ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), 3, ptr(save_mean),
-               ptr(save_invstd), ptr(z))
     else:
-        launch(fwd, y, *head, int(pool), ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), ptr(save_mean), ptr(save_invstd),
-               ptr(z), None)
+        launch("pn2_bn_relu_forward_mode", y, *head, ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), state, ptr(save_mean),
+               ptr(save_invstd), ptr(z))
     return z, ties, save_mean, save_invstd
 
 
-def _bn_train_forward_deferred(y, b, gamma, beta, running_mean, running_var, decay, stats_ws=None):
+def _stats_done(state):
+    """the stats_done argument of pn2_bn_relu_forward_deferred / pn2_bn_grad_constants for a (zeroed) workspace in `state`"""
+    return int(state >= BN_WS_SUMMED)
+
+
+def _bn_train_forward_deferred(y, b, gamma, beta, running_mean, running_var, decay, stats=None):
     """the statistics half of _bn_train_forward only (pn2_bn_relu_forward_deferred) -> save_mean, save_invstd, scale, shift"""
     rows, c = y.shape
-    ws = stats_ws if stats_ws is not None else _bn_zeroed_scratch(c, y.device)
+    ws, state = stats if stats is not None else (_bn_zeroed_scratch(c, y.device), BN_WS_ZEROED)
     consts = _bn_consts_out(c, y.device)
     launch("pn2_bn_relu_forward_deferred", y, rows, c, ptr(y), ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, decay,
-           int(stats_ws is not None), ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), *map(ptr, consts))
+           _stats_done(state), ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), *map(ptr, consts))
     return consts
 
 
@@ -827,11 +826,11 @@ def _bn_register_producer(z, y, gamma, beta, save_mean, save_invstd, relu, poole
         return None
     lk = _BnLink()
     lk.shape, lk.y, lk.gamma, lk.beta, lk.mean, lk.invstd, lk.relu = tuple(z.shape), y, gamma, beta, save_mean, save_invstd, bool(relu)
-    lk.ws = lk.dz_ptr = lk.dz_keep = None
+    lk.ws = lk.ws_state = lk.dz_ptr = lk.dz_keep = None
     lk.sc, lk.sh, lk.consumed = sc, sh, False
     # gx: this layer's backward forms its batch-norm gradient on load -- the consumer's data-gradient GEMM may then publish the
-    # gradient constants itself (finish kind 3); folded / coef / dgamma / dbeta: what that GEMM's last workgroup has left
-    lk.gx, lk.folded, lk.coef, lk.dgamma, lk.dbeta = bool(gx), False, None, None, None
+    # gradient constants itself (finish kind 3); coef / dgamma / dbeta: what that GEMM's last workgroup has left
+    lk.gx, lk.coef, lk.dgamma, lk.dbeta = bool(gx), None, None, None
     _bn_links[z.data_ptr()] = lk
     return lk
 
@@ -850,32 +849,27 @@ def _bn_link_spend(lk):
     if lk.sc is not None and not lk.consumed:
         # the un-normalised output went somewhere else than into the next dense layer: whatever read it saw wrong values
         raise RuntimeError("a deferred batch-norm output (conv2d(..., defer_bn=True)) was not consumed by a following conv2d")
-    lk.ws = lk.dz_keep = lk.dz_ptr = lk.y = lk.gamma = lk.beta = lk.mean = lk.invstd = lk.sc = lk.sh = None
+    lk.ws = lk.ws_state = lk.dz_keep = lk.dz_ptr = lk.y = lk.gamma = lk.beta = lk.mean = lk.invstd = lk.sc = lk.sh = None
     lk.coef = lk.dgamma = lk.dbeta = None
 
 
 def _bn_train_backward(dz, y, gamma, beta, save_mean, save_invstd, relu, pool, zmax, ties, lk):
-    """gradient of _bn_train_forward on pn2_bn_relu_backward -> dy (rows, c), dgamma, dbeta.  lk: this layer's producer
+    """gradient of _bn_train_forward on pn2_bn_relu_backward_mode -> dy (rows, c), dgamma, dbeta.  lk: this layer's producer
     record; when the consumer's data-gradient GEMM has already left the two reduction sums there (and dz is that GEMM's
     output), the reduction pass is skipped."""
     rows, c = y.shape
     dz = dz.contiguous()
     dy = torch.empty_like(y)
     dgamma, dbeta = _param_grad_out(gamma), _param_grad_out(beta)
-    mode3 = False
     if lk is not None and lk.ws is not None and lk.dz_ptr == dz.data_ptr() and dz.shape == y.shape:
-        ws, bwd, mode3 = lk.ws, "pn2_bn_relu_backward_stats", bool(lk.folded)
+        ws, state = lk.ws, lk.ws_state  # SUMMED, or FOLDED by the consumer's data-gradient GEMM (pn2_linear_dgrad_fin)
     else:
-        ws, bwd = _bn_scratch(c, y.device, "pn2_bn_relu_backward", "pn2_bn_relu_backward_ws0")
+        ws, state = _bn_scratch(c, y.device)
     _bn_link_spend(lk)
     if ties is not None and ties.dim() == zmax.dim() + 1:
         ties = ties[0]  # [tie counts | ysel] of _bn_train_forward
-    head = (rows, c, ptr(dz), ptr(y), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), int(relu), int(pool), ptr(zmax),
-            ptr(ties), ptr(ws), nbytes(ws))
-    if mode3:  # the consumer's data-gradient GEMM has left the sums AND folded them (pn2_linear_dgrad_fin)
-        launch("pn2_bn_relu_backward_mode", y, *head, 3, ptr(dy), ptr(dgamma), ptr(dbeta))
-    else:
-        launch(bwd, y, *head, ptr(dy), ptr(dgamma), ptr(dbeta))
+    launch("pn2_bn_relu_backward_mode", y, rows, c, ptr(dz), ptr(y), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), int(relu),
+           int(pool), ptr(zmax), ptr(ties), ptr(ws), nbytes(ws), state, ptr(dy), ptr(dgamma), ptr(dbeta))
     return dy, dgamma, dbeta
 
 
@@ -902,11 +896,11 @@ def _bn_grad_constants(dz, y, gamma, beta, save_mean, save_invstd, relu, pool, z
     rows, c = y.shape
     ready = None
     if lk is not None and lk.ws is not None and lk.dz_ptr == dz.data_ptr() and dz.shape == y.shape:
-        ws, done = lk.ws, 1
+        ws, state = lk.ws, lk.ws_state
         if lk.coef is not None:  # the consumer's data-gradient GEMM has published them already (finish kind 3)
             ready = (lk.coef, lk.dgamma, lk.dbeta)
     else:
-        ws, done = _bn_zeroed_scratch(c, y.device), 0
+        ws, state = _bn_zeroed_scratch(c, y.device), BN_WS_ZEROED
     _bn_link_spend(lk)
     if ready is not None:
         return ready
@@ -916,7 +910,7 @@ def _bn_grad_constants(dz, y, gamma, beta, save_mean, save_invstd, relu, pool, z
     if ties is not None and ties.dim() == zmax.dim() + 1:
         ties, ysel = ties[0], (ties[1] if USE_POOLED_BN_REDUCE else None)
     launch("pn2_bn_grad_constants", y, rows, c, ptr(dz), ptr(y), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), int(relu),
-           int(pool), ptr(zmax), ptr(ties), ptr(ysel), done, ptr(ws), nbytes(ws), ptr(coef), ptr(dgamma), ptr(dbeta))
+           int(pool), ptr(zmax), ptr(ties), ptr(ysel), _stats_done(state), ptr(ws), nbytes(ws), ptr(coef), ptr(dgamma), ptr(dbeta))
     return coef, dgamma, dbeta
 
 
@@ -929,10 +923,9 @@ def _below_args(link, rows, cin, dx, fin):
         return (None, None, None, None, None, 0, None, 0), (0, None, None, None), {}
     pws = _bn_zeroed_scratch(cin, dx.device)
     below = (ptr(link.y), ptr(link.gamma), ptr(link.beta), ptr(link.mean), ptr(link.invstd), int(link.relu), ptr(pws), nbytes(pws))
-    notes = dict(ws=pws, dz_ptr=dx.data_ptr(), dz_keep=dx)
+    notes = dict(ws=pws, ws_state=BN_WS_FOLDED if fin else BN_WS_SUMMED, dz_ptr=dx.data_ptr(), dz_keep=dx)
     fin_out = (1, None, None, None)
     if fin:
-        notes["folded"] = True
         if link.gx and _gx_usable(rows, cin, 0, dx, link.y):
             coef = torch.empty((6, cin), dtype=torch.float32, device=dx.device)
             dgamma, dbeta = _param_grad_out(link.gamma), _param_grad_out(link.beta)
@@ -1029,7 +1022,7 @@ class _TrainDenseBnRelu(torch.autograd.Function):
         #                                    (the callers also drop the request when no tape is being recorded at all)
         if xf and c % 32 != 0:
             raise RuntimeError("a deferred batch-norm output reached a layer that cannot apply it")
-        consts, folded = None, False
+        consts, stats = None, None  # stats: (workspace, BN_WS_* state) once the GEMM has left the column sums of y there
         if front is not None:
             # the first layer of an SA module with few point channels: gather + centre + concat + product + statistics + their
             # fold / constants in ONE launch (pn2_sa_first_layer_bn); x2d = the grouped input it leaves for the weight gradient
@@ -1046,23 +1039,25 @@ class _TrainDenseBnRelu(torch.autograd.Function):
             launch("pn2_sa_first_layer_bn", xyz, bsz, n, m, ns, cpts, c, ptr(xyz), ptr(new_xyz), ptr(points), ptr(idx),
                    ptr(w.contiguous()), ptr(y), ptr(x2d), ptr(ws), nbytes(ws), 2 if defer else 1, ptr(gamma), ptr(beta), ptr(b),
                    BN_EPSILON, float(decay), ptr(running_mean), ptr(running_var), ptr(cs[0]), ptr(cs[1]), ptr(cs[2]), ptr(cs[3]))
-            folded = True
+            stats = (ws, BN_WS_FOLDED)
         elif (xf or (USE_GEMM_BN_STATS and c % 32 == 0)) and USE_BN_FINISH_IN_PRODUCER:
             # ONE launch: GEMM (batch norm of the layer below applied on load when it was deferred) + column sums of y + -- in the
             # launch's last workgroup -- their fold and, for a layer that defers its own batch norm, its constants
             ws = _bn_zeroed_scratch(c, x2d.device)
             y, consts = hip_matmul_bn_stats_fin(x2d, w, ws, (prev.sc, prev.sh, prev.relu) if xf else None, 2 if defer else 1,
                                                 gamma, beta, b, decay, running_mean, running_var)
-            folded = True
+            stats = (ws, BN_WS_FOLDED)
         elif xf:
             ws = _bn_zeroed_scratch(c, x2d.device)
             y = hip_matmul_bn_stats_xf(x2d, w, ws, prev.sc, prev.sh, prev.relu)
+            stats = (ws, BN_WS_SUMMED)
         elif USE_GEMM_BN_STATS and c % 32 == 0:
             # the GEMM's epilogue leaves the column sums of y in the batch-norm workspace: no statistics pass over y
             ws = _bn_zeroed_scratch(c, x2d.device)
             y = hip_matmul_bn_stats(x2d, w, ws)
+            stats = (ws, BN_WS_SUMMED)
         else:
-            ws, y = None, hip_matmul(x2d, w)
+            y = hip_matmul(x2d, w)
         if xf:
             prev.consumed = True
         ctx.xf = (prev.sc, prev.sh, bool(prev.relu)) if xf else None
@@ -1073,14 +1068,13 @@ class _TrainDenseBnRelu(torch.autograd.Function):
             if consts is not None:
                 save_mean, save_invstd, sc, sh = consts
             else:
-                save_mean, save_invstd, sc, sh = _bn_train_forward_deferred(y, b, gamma, beta, running_mean, running_var, decay, ws)
+                save_mean, save_invstd, sc, sh = _bn_train_forward_deferred(y, b, gamma, beta, running_mean, running_var, decay, stats)
             ctx.save_for_backward(x2d, w, y, gamma, beta, save_mean, save_invstd)
             ctx.link = _bn_register_producer(y, y, gamma, beta, save_mean, save_invstd, relu, False, sc, sh, gx=gx)
             if ctx.link is None:
                 raise RuntimeError("deferred batch norm needs the producer links (USE_DGRAD_BN_STATS)")
             return y  # un-normalised: only the next dense layer of the stack may consume it
-        z, ties, save_mean, save_invstd = _bn_train_forward(y, b, gamma, beta, running_mean, running_var, decay, relu, pool, ws,
-                                                            folded=folded)
+        z, ties, save_mean, save_invstd = _bn_train_forward(y, b, gamma, beta, running_mean, running_var, decay, relu, pool, stats)
         if pooled:
             ctx.save_for_backward(x2d, w, y, gamma, beta, save_mean, save_invstd, z, ties)
         else:
@@ -1298,6 +1292,7 @@ class _TrainHoistedMsgBnRelu(torch.autograd.Function):
         defers = [bool(d) and not pools[s] and needs for s, d in enumerate(defers)]  # as _TrainDenseBnRelu
         fin = bool(USE_BN_FINISH_IN_PRODUCER)
         finish = [(2 if d else 1) if fin else 0 for d in defers]
+        left = BN_WS_FOLDED if fin else BN_WS_SUMMED  # state of a scale's workspace after the launch (finish 1 / 0)
         ys = [torch.empty((bsz * m * k, co), dtype=torch.float32, device=src.device) for k, co in zip(ks, couts)]
         gx = [torch.empty((bsz * m * k, 3), dtype=torch.float32, device=src.device) for k in ks]
         wss = [_bn_zeroed_scratch(co, src.device) for co in couts]
@@ -1315,7 +1310,7 @@ class _TrainHoistedMsgBnRelu(torch.autograd.Function):
                     save_mean, save_invstd, sc, sh = consts[s]
                 else:
                     save_mean, save_invstd, sc, sh = _bn_train_forward_deferred(y, bs_[s], gammas[s], betas[s], rms[s], rvs[s], decay,
-                                                                                wss[s])
+                                                                                (wss[s], left))
                 saved += [ws_[s], y, gammas[s], betas[s], save_mean, save_invstd, gx[s], plans[s]]
                 lk = _bn_register_producer(y, y, gammas[s], betas[s], save_mean, save_invstd, True, False, sc, sh)
                 if lk is None:
@@ -1323,7 +1318,7 @@ class _TrainHoistedMsgBnRelu(torch.autograd.Function):
                 outs.append(y)
             else:
                 zact, ties, save_mean, save_invstd = _bn_train_forward(y, bs_[s], gammas[s], betas[s], rms[s], rvs[s], decay, True,
-                                                                       pool, wss[s], folded=fin)
+                                                                       pool, (wss[s], left))
                 saved += [ws_[s], y, gammas[s], betas[s], save_mean, save_invstd, gx[s], plans[s]]
                 if pool > 1:
                     saved += [zact, ties]

@@ -27,10 +27,45 @@ def test_library_exports_every_declared_symbol(pn2):
     lib = ctypes.CDLL(pn2._lib.LIB_PATH)
     for n in _declared():
         assert hasattr(lib, n), n
-    assert pn2._lib.lib.pn2_abi_version() == 1
+    assert pn2._lib.lib.pn2_abi_version() == 2
     assert b"gfx950" in pn2._lib.lib.pn2_build_info()
     # the shipped library has no tuning hooks: no process-global kernel-selection state behind the ABI
     assert not hasattr(lib, "pn2_debug_set") and not hasattr(lib, "pn2_debug_set_grouping")
+
+
+def test_bn_workspace_states_match_the_header(pn2):
+    """PN2_BN_WS_* of include/pn2_abi.h are 0..3 in the documented order and _lib.BN_WS_* are the same numbers"""
+    src = open(os.path.join(ROOT, "include", "pn2_abi.h")).read()
+    states = {k: int(v) for k, v in re.findall(r"\bPN2_BN_WS_([A-Z]+)\s*=?\s*(\d+)", re.sub(r"/\*.*?\*/", "", src, flags=re.S))}
+    assert states == {"UNCLEARED": 0, "ZEROED": 1, "SUMMED": 2, "FOLDED": 3}
+    for name, value in states.items():
+        assert getattr(pn2._lib, "BN_WS_" + name) == value, name
+
+
+# forward / backward x the suffixes for a caller-zeroed workspace and for one that already holds the sums
+REMOVED_BN_ALIASES = ["pn2_bn_relu_%s_%s" % (d, sfx) for d in ("forward", "backward") for sfx in ("ws" + "0", "stats")]
+
+
+def test_bn_alias_entry_points_are_gone(pn2):
+    """ABI version 2 dropped the entry points that only passed a constant state to the _mode forms"""
+    lib = ctypes.CDLL(pn2._lib.LIB_PATH)
+    for n in REMOVED_BN_ALIASES:
+        assert not hasattr(lib, n), n
+        assert n not in pn2._lib.SIGNATURES and n not in _declared(), n
+
+
+def test_bn_state_range_is_checked_before_the_pointers(pn2):
+    """a stats_mode outside PN2_BN_WS_UNCLEARED .. PN2_BN_WS_FOLDED is PN2_EINVAL even when every pointer is NULL (PN2_ENULL
+    otherwise): the range check comes first"""
+    L, nul = pn2._lib.lib, None
+    for mode in (-1, 4):
+        assert L.pn2_bn_relu_forward_mode(64, 32, nul, nul, nul, nul, 1e-3, 0.9, 1, nul, nul, nul, 0, mode, nul, nul, nul, nul) == -1
+        assert L.pn2_bn_relu_forward_pool(64, 32, nul, nul, nul, nul, 1e-3, 0.9, 1, 32, nul, nul, nul, 0, mode, nul, nul, nul, nul,
+                                          nul, nul) == -1
+        assert L.pn2_bn_relu_backward_mode(64, 32, nul, nul, nul, nul, nul, nul, 1, 0, nul, nul, nul, 0, mode, nul, nul, nul, nul) == -1
+    for mode in range(4):  # a known state reaches the pointer checks
+        assert L.pn2_bn_relu_forward_mode(64, 32, nul, nul, nul, nul, 1e-3, 0.9, 1, nul, nul, nul, 0, mode, nul, nul, nul, nul) == -2
+        assert L.pn2_bn_relu_backward_mode(64, 32, nul, nul, nul, nul, nul, nul, 1, 0, nul, nul, nul, 0, mode, nul, nul, nul, nul) == -2
 
 
 def test_python_signatures_cover_the_header(pn2):

@@ -1,6 +1,6 @@
 """The training-mode batch-norm kernels (csrc/pn2_bn.hip, pn2_bn_finish / bn_scale_shift in csrc/pn2_common.h) at their edges,
 entry point by entry point through the C ABI: pn2_bn_relu_forward, _mode, _pool, _deferred, pn2_bn_relu_backward, _mode and
-pn2_bn_grad_constants (and _stats through mode 2) against the float64 oracle and the float32 restatement of tests/bn_ref.py.
+pn2_bn_grad_constants (every PN2_BN_WS_* state of the workspace) against the float64 oracle and the float32 restatement of tests/bn_ref.py.
 
 Shapes come from the kernels' thread mapping (cv = c / vec columns, rp = 256 // cv row slots; one reduction block while
 rows <= 8 * rp; two slot copies of the accumulators from 33 blocks).  Every output is a 16-byte aligned view inside a larger

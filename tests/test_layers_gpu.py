@@ -2125,7 +2125,7 @@ def test_train_layer_takes_any_batch_norm_width(pn2, cuda, cout, pool):
 ])
 def test_bn_grad_sums_from_the_next_layers_dgrad(pn2, cuda, widths, pool, rows_shape):
     """The first reduction of a layer's batch-norm gradient taken from the accumulator tiles of the NEXT layer's data-gradient
-    GEMM (pn2_linear_dgrad_bn_grad_stats + pn2_bn_relu_backward_stats, tf_util._BnLink) against the two-pass backward
+    GEMM (pn2_linear_dgrad_bn_grad_stats + pn2_bn_relu_backward_mode on the SUMMED workspace, tf_util._BnLink) against the two-pass backward
     (pn2_linear_dgrad + pn2_bn_relu_backward): same gradients up to fp64 summation order, and the shortcut really ran for
     every link of the stack.  Reference semantics: tf.gradients through conv2d -> batch_norm -> relu, tf_util.py:186-204."""
     import torch
@@ -2143,7 +2143,8 @@ def test_bn_grad_sums_from_the_next_layers_dgrad(pn2, cuda, widths, pool, rows_s
         oshape[-2] //= pool
     probe = torch.cos(torch.arange(int(np.prod(oshape)), device=cuda).float() * 0.37).reshape(oshape)
     calls = []
-    real, real_gx = pn2._lib.lib.pn2_bn_relu_backward_stats, pn2._lib.lib.pn2_bn_grad_constants
+    real, real_gx = pn2._lib.lib.pn2_bn_relu_backward_mode, pn2._lib.lib.pn2_bn_grad_constants
+    summed = pn2._lib.BN_WS_SUMMED
     real_fin, real_both = pn2._lib.lib.pn2_linear_dgrad_fin, pn2._lib.lib.pn2_linear_bwd_fused
     outs = {}
     for use in (True, False):
@@ -2151,7 +2152,8 @@ def test_bn_grad_sums_from_the_next_layers_dgrad(pn2, cuda, widths, pool, rows_s
         tfu.reset_bn_links()
         try:
             if use:
-                pn2._lib.lib.pn2_bn_relu_backward_stats = lambda *a: (calls.append(a[1]), real(*a))[1]
+                # stats_mode = a[14]; a FOLDED workspace is counted where it was folded (pn2_linear_dgrad_fin below)
+                pn2._lib.lib.pn2_bn_relu_backward_mode = lambda *a: (calls.append(a[1]) if a[14] == summed else None, real(*a))[1]
                 # the on-load form of the batch-norm gradient (round 6) takes the sums the same way: stats_done = a[13]
                 pn2._lib.lib.pn2_bn_grad_constants = lambda *a: (calls.append(a[1]) if a[13] else None, real_gx(*a))[1]
                 # ... and with the finish inside the producer the data-gradient GEMM of the layer above leaves sums, fold and
@@ -2174,7 +2176,7 @@ def test_bn_grad_sums_from_the_next_layers_dgrad(pn2, cuda, widths, pool, rows_s
             outs[use] = [h.detach(), xx.grad] + [p_.grad for p_ in params]
         finally:
             tfu.USE_DGRAD_BN_STATS = True
-            pn2._lib.lib.pn2_bn_relu_backward_stats = real
+            pn2._lib.lib.pn2_bn_relu_backward_mode = real
             pn2._lib.lib.pn2_bn_grad_constants = real_gx
             pn2._lib.lib.pn2_linear_dgrad_fin = real_fin
             pn2._lib.lib.pn2_linear_bwd_fused = real_both
@@ -2182,6 +2184,79 @@ def test_bn_grad_sums_from_the_next_layers_dgrad(pn2, cuda, widths, pool, rows_s
     for a, r in zip(outs[True], outs[False]):
         s = max(float(r.abs().max()), 1e-3)
         assert float((a - r).abs().max()) <= 2e-5 * s
+
+
+@pytest.mark.parametrize("pool", [0, 32])
+@pytest.mark.parametrize("arena", [False, True])
+def test_bn_workspace_state_handed_to_the_library(pn2, cuda, pool, arena):
+    """tf_util hands pn2_bn_relu_forward_mode / _pool / pn2_bn_relu_backward_mode the state its workspace is really in
+    (include/pn2_abi.h PN2_BN_WS_*): a two-layer stack (96 rows: not a multiple of 64; widths 32 -> 64; below can_defer_bn's 2048
+    rows, so nothing is deferred), last layer pooled or not, with and without the step's zero arena, under (USE_GEMM_BN_STATS,
+    USE_BN_FINISH_IN_PRODUCER) = (off, off), (on, off), (on, on) and the materialised backward (USE_BN_GRAD_ON_LOAD off).
+    Forward: UNCLEARED / ZEROED (arena) without GEMM statistics, SUMMED with them, FOLDED with the finish in the producer.  Backward:
+    the last layer UNCLEARED / ZEROED, the first layer SUMMED, or FOLDED with the finish in the producer.  The three settings agree up
+    to fp64 summation order (the bound of test_bn_grad_sums_from_the_next_layers_dgrad)."""
+    import torch
+    tfu, L = pn2.util.tf_util, pn2._lib
+    widths, cin = (32, 64), 6
+    torch.manual_seed(11)
+    x0 = torch.randn(3, 32, cin, device=cuda)  # 96 rows; pool 32: one maximum per cloud
+    ws, c = [], cin
+    for wd in widths:
+        ws.append(torch.randn(c, wd, device=cuda) / np.sqrt(c))
+        c = wd
+    oshape = (3, 1 if pool else 32, widths[-1])
+    probe = torch.cos(torch.arange(int(np.prod(oshape)), device=cuda).float() * 0.37).reshape(oshape)
+    hooked = {"pn2_bn_relu_forward_mode": ("fwd", 13), "pn2_bn_relu_forward_pool": ("fwd", 14), "pn2_bn_relu_backward_mode": ("bwd", 14)}
+    real = {name: getattr(L.lib, name) for name in hooked}
+    seen = []
+
+    def hook(name):
+        kind, at = hooked[name]
+        return lambda *a: (seen.append((kind, a[1], a[at])), real[name](*a))[1]
+
+    store = tfu.get_default_store()
+    saved = (tfu.USE_GEMM_BN_STATS, tfu.USE_BN_FINISH_IN_PRODUCER, tfu.USE_BN_GRAD_ON_LOAD, store.zero_arena)
+    scratch = L.BN_WS_ZEROED if arena else L.BN_WS_UNCLEARED
+    outs = []
+    try:
+        for name in hooked:
+            setattr(L.lib, name, hook(name))
+        tfu.USE_BN_GRAD_ON_LOAD = False
+        if arena:
+            store.zero_arena = tfu.ZeroArena(cuda)
+            store.zero_arena.needed = 1 << 20  # four batch-norm workspaces of <= 66944 bytes + two weight-gradient tiles
+            store.zero_arena.allocate()
+        for gemm_stats, fin in ((False, False), (True, False), (True, True)):
+            tfu.USE_GEMM_BN_STATS, tfu.USE_BN_FINISH_IN_PRODUCER = gemm_stats, fin
+            tfu.reset_bn_links()
+            if arena:
+                store.zero_arena.reset()
+            del seen[:]
+            xx = x0.clone().requires_grad_(True)
+            params, h = [], xx
+            for i, wd in enumerate(widths):
+                w = ws[i].clone().requires_grad_(True)
+                gamma = (1.0 + 0.1 * torch.sin(torch.arange(wd, device=cuda).float())).requires_grad_(True)
+                beta = (0.05 * torch.cos(torch.arange(wd, device=cuda).float())).requires_grad_(True)
+                mean, var = torch.zeros(wd, device=cuda), torch.ones(wd, device=cuda)
+                h = tfu._train_layer(h, w, torch.zeros(wd, device=cuda), (beta, gamma, mean, var), None, True,
+                                     pool if i == len(widths) - 1 else 0)
+                params += [w, gamma, beta]
+            (h * probe).sum().backward()
+            left = L.BN_WS_FOLDED if fin else L.BN_WS_SUMMED
+            fwd = left if gemm_stats else scratch
+            assert seen == [("fwd", 32, fwd), ("fwd", 64, fwd), ("bwd", 64, scratch), ("bwd", 32, left)], (gemm_stats, fin, seen)
+            # clones: with the arena the weight gradients are slices of it, and the next setting's reset clears them
+            outs.append([t.detach().clone() for t in [h, xx.grad] + [p_.grad for p_ in params]])
+    finally:
+        tfu.USE_GEMM_BN_STATS, tfu.USE_BN_FINISH_IN_PRODUCER, tfu.USE_BN_GRAD_ON_LOAD, store.zero_arena = saved
+        for name in hooked:
+            setattr(L.lib, name, real[name])
+    for other in outs[1:]:
+        for a, r in zip(other, outs[0]):
+            s = max(float(r.abs().max()), 1e-3)
+            assert float((a - r).abs().max()) <= 2e-5 * s
 
 
 @pytest.mark.parametrize("rows,cin,widths,pool,relu_last", [

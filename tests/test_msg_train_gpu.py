@@ -121,7 +121,7 @@ def test_hoist_multi_equals_the_single_scale_kernel_and_float64_statistics(pn2, 
             assert _intact(lst[s][0]), "scale %d: a write outside an output" % s
         if not two:  # finish 1: the folded sums are in the workspace; the project's normalisation kernel turns them into moments
             rm, rv = torch.zeros(c, device=cuda), torch.ones(c, device=cuda)
-            _, _, sm, si = tfu._bn_train_forward(y, bias[s], gamma[s], beta[s], rm, rv, 0.5, True, 0, wsb[s][1], folded=True)
+            _, _, sm, si = tfu._bn_train_forward(y, bias[s], gamma[s], beta[s], rm, rv, 0.5, True, 0, (wsb[s][1], L.BN_WS_FOLDED))
             sc = sh = None
         else:
             sm, si, sc, sh, rm, rv = (lst[s][1] for lst in (smb, sib, scb, shb, rmb, rvb))

@@ -31,7 +31,7 @@ def test_linear_dgrad_and_matmul_vs_fp64(pn2, cuda, rows, cin, cout):
                                                 (1024, 768, 256, 0), (131072, 128, 128, 0), (2048, 256, 512, 32), (16384, 320, 256, 0),
                                                 (33, 32, 32, 0)])
 def test_gemm_epilogue_batch_statistics(pn2, cuda, rows, cin, cout, pool):
-    """pn2_linear_bn_stats + pn2_bn_relu_forward_stats (column sums from the GEMM's accumulators) against float64 moments of
+    """pn2_linear_bn_stats + pn2_bn_relu_forward_mode on the SUMMED workspace (column sums from the GEMM's accumulators) against float64 moments of
     the same y, and against the two-pass path (GEMM, then a statistics pass): every tile shape of pn2_linear, ragged row
     counts, a channel with |mean| >> std (cancellation in E[y^2] - E[y]^2)."""
     import torch
