@@ -4,6 +4,10 @@ There is deliberately NO fallback: if the HIP library cannot be loaded the
 import fails loudly.  The library must be loaded after `import torch` so that it
 binds to the HIP runtime torch already mapped (same soname libamdhip64.so.7);
 tensors and streams are then shared with torch without copies.
+
+The binding is read from the header (_abi.py): argument types, return types, the PN2_* constants and the benchmark trace's
+table all come from its prototypes.  A new entry point is added in include/pn2_abi.h and its .hip file -- and to _STATEFUL
+below if it changes caller state beyond its outputs, which no prototype says.  Nothing else changes on the Python side.
 """
 import ctypes
 import os
@@ -11,187 +15,39 @@ import sys
 
 import torch  # noqa: F401  (must precede CDLL: maps torch's libamdhip64.so.7)
 
+from . import _abi, build as _build
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PN2_HIP_LIBRARY: load another build of the same ABI instead (the tuning build of the A/B scripts under tools/)
 LIB_PATH = os.environ.get("PN2_HIP_LIBRARY") or os.path.join(_HERE, "libpn2_hip.so")
 
 c_int, c_float, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 
-# name -> argtypes, in the order of include/pn2_abi.h
-SIGNATURES = {
-    "pn2_farthest_point_sample": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "pn2_fps_gather": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "pn2_fps_nested": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "pn2_fps_nested_ld": [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "pn2_coarse_geometry": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                            c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
-    "pn2_prob_sample": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_fps_large": [c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_int, c_void_p],
-    "pn2_gather_point": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_gather_point_grad": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_query_ball_point": [c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "pn2_query_ball_point_ld": [c_int, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "pn2_query_ball_point_kernel": [c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                    c_void_p],
-    "pn2_query_ball_point_multi": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_int, c_void_p],
-    "pn2_selection_sort": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_group_point": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_group_point_grad": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_three_nn": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_three_nn_ld": [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_three_interpolate": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_three_interpolate_grad": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_group_point_grad_ws": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t,
-                                c_void_p],
-    "pn2_three_interpolate_grad_ws": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      ctypes.c_size_t, c_void_p],
-    "pn2_linear": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
-    "pn2_linear_wgrad": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_bn_relu_forward": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int,
-                            c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_bn_relu_backward": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                             c_int, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_set_sa_row_packing": [c_int],
-    "pn2_sa_mlp_max_fused": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_sa_mlp_max_fused_ld": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_sa_mlp_max_fused_bf16": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_sa_mlp_rows_fused": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_fp_interp_concat": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_void_p, c_int, c_void_p],
-    "pn2_mlp_chain": [c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
-    "pn2_fp_mlp_fused": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_interpolate_label_with_color": [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                                         ctypes.c_size_t, c_void_p],
-    "pn2_sa_group_concat": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                            c_void_p, c_void_p],
-    "pn2_mlp_wide": [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
-    "pn2_sa_mlp_wide": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                        c_void_p, c_int, c_void_p, c_void_p],
-    "pn2_fp_mlp_wide": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                        c_void_p, c_void_p, c_void_p],
-    "pn2_multi_copy": [c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_multi_copy_fill": [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_scatter_plan_build": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p],
-    "pn2_scatter_plan_build_multi": [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     ctypes.c_size_t, c_void_p],
-    "pn2_scatter_plan_apply": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p],
-    "pn2_scatter_plan_apply_multi": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_void_p],
-    "pn2_linear_bn_stats": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p],
-    "pn2_linear_wgrad_accumulate": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_linear_dgrad": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_bn_relu_forward_deferred": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int,
-                                     c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_linear_bn_stats_xf": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p,
-                               c_int, c_void_p],
-    "pn2_linear_wgrad_accumulate_xf": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "pn2_sa_hoist_rows": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                          c_void_p],
-    "pn2_fp_hoist_rows": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_sa_hoist_rows_bn": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_fp_hoist_rows_bn": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_sa_hoist_rows_multi_bn": [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_linear_dgrad_bn_grad_stats": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p],
-    "pn2_linear_bn_stats_fin": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p,
-                                c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_linear_dgrad_fin": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                             ctypes.c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_bn_relu_forward_mode": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int,
-                                 c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_bn_relu_backward_mode": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                  c_int, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p, c_void_p,
-                                  c_void_p],
-    "pn2_sa_first_layer_bn": [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                              c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float,
-                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_linear_bwd_fused": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_int, c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_linear_narrow": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_bn_grad_constants": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                              c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_bn_relu_forward_pool": [ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int,
-                                 c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_void_p],
-    "pn2_linear_dgrad_gx": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p],
-    "pn2_linear_wgrad_gx": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                            c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_weighted_ce_forward": [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_weighted_ce_backward": [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p],
-    "pn2_confusion_update": [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_void_p],
-    "pn2_dropout": [ctypes.c_longlong, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_dropout_grad": [ctypes.c_longlong, c_void_p, c_void_p, c_float, c_void_p, c_void_p],
-    "pn2_relu_grad": [ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_adam_step": [ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_momentum_step": [ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_scene_extract_z_box": [c_int, c_void_p, c_int, c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int,
-                                c_void_p, c_void_p, c_void_p],
-    "pn2_scene_sample": [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double,
-                         ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_fp_mlp_fused_pre": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                             c_void_p, c_void_p, c_void_p],
-    "pn2_fp_mlp_fused_pre_ld": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p],
-    "pn2_fp_mlp_fused_pre_schedule": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "pn2_sa_mlp_fused_pre": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                             c_void_p, c_int, c_void_p, c_void_p],
-    "pn2_fp_mlp_wide_pre": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                            c_void_p, c_void_p, c_void_p],
-    "pn2_sa_mlp_wide_pre": [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                            c_void_p, c_int, c_void_p, c_void_p],
-    "pn2_ball_query_bin": [c_int, c_int, c_float, c_void_p, c_void_p, ctypes.c_size_t, c_void_p],
-    "pn2_ball_query_bin_ld": [c_int, c_int, c_float, c_void_p, c_int, c_void_p, ctypes.c_size_t, c_void_p],
-    "pn2_query_ball_point_binned": [c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                    c_void_p],
-    "pn2_group_pool": [ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_group_pool_grad": [ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "pn2_voxel_downsample": [c_int, c_void_p, c_void_p, c_void_p, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_void_p, c_void_p, ctypes.c_size_t, c_void_p],
-    "pn2_dataset_workspace_size": [c_int, c_int, c_void_p],
-    "pn2_dataset_sample": [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                           c_void_p, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p,
-                           c_void_p, c_int, c_void_p, c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
-                           c_void_p, c_void_p, c_void_p],
-}
-PN2_EUNSUP = -4
+ABI = _abi.load(_build.HEADER)
+# the entry points (-> int: 0, PN2_E* or a hipError_t): name -> argtypes, in the order of the header
+SIGNATURES = {name: f.argtypes for name, f in ABI.functions.items() if f.restype is c_int and name != "pn2_abi_version"}
+PN2_EUNSUP = ABI.constants["PN2_EUNSUP"]
 # state of a batch-norm workspace when a call arrives: PN2_BN_WS_* of include/pn2_abi.h (the stats_mode argument)
-BN_WS_UNCLEARED, BN_WS_ZEROED, BN_WS_SUMMED, BN_WS_FOLDED = range(4)
-# workspace-size queries (-> size_t): name -> number of int arguments
-_SIZE_QUERIES = {"pn2_fps_large_workspace_bytes": 2, "pn2_ball_query_bin_bytes": 1, "pn2_interpolate_label_workspace_bytes": 1,
-                 "pn2_three_interpolate_grad_workspace_bytes": 3, "pn2_scatter_plan_bytes": 3,
-                 "pn2_group_point_grad_workspace_bytes": 4, "pn2_voxel_downsample_workspace_bytes": 1, "pn2_bn_workspace_bytes": 1}
-# What the benchmark trace decodes besides the numeric arguments: entry point -> (index of nlayers, index of the host widths[]
-# array in the argument list -- both None when there is none --, trace key, positions AMONG THE NUMERIC ARGUMENTS to drop).  An
-# in-place (row-strided) *_ld call is the dense entry point's kernel: recorded under the dense name with its strides dropped.
-_TRACE_ARGS = {"pn2_sa_mlp_max_fused": (9, 10, None, ()), "pn2_sa_mlp_rows_fused": (9, 10, None, ()),
-               "pn2_sa_mlp_max_fused_bf16": (9, 10, None, ()), "pn2_fp_mlp_fused": (9, 10, None, ()),
-               "pn2_fp_mlp_wide_pre": (8, 9, None, ()), "pn2_sa_mlp_wide_pre": (8, 9, None, ()),
-               "pn2_sa_mlp_fused_pre": (8, 9, None, ()), "pn2_fp_mlp_fused_pre": (8, 9, None, ()),
-               "pn2_fp_mlp_fused_pre_schedule": (8, 9, None, ()), "pn2_mlp_chain": (3, 4, None, ()),
-               "pn2_mlp_wide": (4, 5, None, ()), "pn2_fp_mlp_wide": (9, 10, None, ()), "pn2_sa_mlp_wide": (9, 10, None, ()),
-               "pn2_fps_nested_ld": (None, None, "pn2_fps_nested", (3,)),
-               "pn2_query_ball_point_ld": (None, None, "pn2_query_ball_point", (5,)),
-               "pn2_three_nn_ld": (None, None, "pn2_three_nn", (3,)),
-               "pn2_ball_query_bin_ld": (None, None, "pn2_ball_query_bin", (3,)),
-               "pn2_sa_mlp_max_fused_ld": (11, 12, "pn2_sa_mlp_max_fused", (5, 6)),
-               "pn2_fp_mlp_fused_pre_ld": (9, 10, "pn2_fp_mlp_fused_pre", (4,))}
+BN_WS_UNCLEARED, BN_WS_ZEROED, BN_WS_SUMMED, BN_WS_FOLDED = (
+    ABI.constants["PN2_BN_WS_" + state] for state in ("UNCLEARED", "ZEROED", "SUMMED", "FOLDED"))
+
+
+def _trace_args():
+    """What the benchmark trace decodes besides the numeric arguments: entry point -> (index of nlayers, index of the host widths[]
+    array in the argument list -- both None when there is none --, trace key, positions AMONG THE NUMERIC ARGUMENTS to drop).  An
+    in-place (row-strided) *_ld call is the dense entry point's kernel: recorded under the dense name with its strides dropped.
+    Read off the header's parameter names: `nlayers`, `widths`, and `ld*` for a row stride."""
+    table = {}
+    for name, f in ABI.functions.items():
+        at = {arg: i for i, arg in enumerate(f.argnames)}
+        numeric = [arg for arg, t in zip(f.argnames, f.argtypes) if t is not c_void_p]
+        drop = tuple(i for i, arg in enumerate(numeric) if arg.startswith("ld"))
+        if drop or "nlayers" in at or "widths" in at:
+            table[name] = (at.get("nlayers"), at.get("widths"), name[:-3] if name.endswith("_ld") else None, drop)
+    return table
+
+
+_TRACE_ARGS = _trace_args()
 
 
 class Pn2Error(RuntimeError):
@@ -205,7 +61,6 @@ def _load():
     # rank can dlopen a half-written library.  An up-to-date library is loaded without touching the tree (it may be
     # read-only to the user who runs it); the lock is taken only when a build may be needed.
     import fcntl
-    from . import build as _build
     if not os.environ.get("PN2_HIP_LIBRARY") and _build._stale():
         if not os.access(_HERE, os.W_OK) and os.path.exists(_build.LIB):
             sys.stderr.write("pn2: %s is older than its sources but %s is not writable: loading the library as built\n"
@@ -223,19 +78,10 @@ def _load():
     except OSError as e:  # pragma: no cover
         raise ImportError("cannot load the HIP extension %s: %s -- there is no CPU fallback; "
                           "build it with `python open3d-pointnet2-semantic3d_amd/build.py`" % (LIB_PATH, e))
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the ABI and the library disagree
-        fn.argtypes = argtypes
-        fn.restype = c_int
-    for name, nargs in _SIZE_QUERIES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = [c_int] * nargs
-        fn.restype = ctypes.c_size_t
-    lib.pn2_abi_version.restype = c_int
-    lib.pn2_build_info.restype = ctypes.c_char_p
-    lib.pn2_strerror.restype = ctypes.c_char_p
-    lib.pn2_strerror.argtypes = [c_int]
-    if lib.pn2_abi_version() != 2:
+    for name, f in ABI.functions.items():
+        fn = getattr(lib, name)  # AttributeError if the header and the library disagree
+        fn.argtypes, fn.restype = f.argtypes, f.restype
+    if lib.pn2_abi_version() != ABI.constants["PN2_ABI_VERSION"]:
         raise ImportError("libpn2_hip.so ABI version mismatch")
     return lib
 

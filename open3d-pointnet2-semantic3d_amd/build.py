@@ -13,6 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpn2_hip.so")
+HEADER = os.path.join(os.path.dirname(HERE), "include", "pn2_abi.h")  # the C ABI: compiled into the library, parsed by _lib.py
 SOURCES = ["pn2_abi.hip", "pn2_sampling.hip", "pn2_grouping.hip", "pn2_interpolate.hip",
            "pn2_linear.hip", "pn2_sa_fused.hip", "pn2_sa_fused_bf16.hip", "pn2_label_interp.hip", "pn2_fps_bucket.hip",
            "pn2_bn.hip", "pn2_scene.hip", "pn2_train.hip", "pn2_mlp_wide.hip", "pn2_pool.hip", "pn2_hoist.hip",
@@ -37,7 +38,7 @@ def _stale():
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [
-        os.path.join(HERE, "..", "include", "pn2_abi.h"), os.path.abspath(__file__)]
+        HEADER, os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

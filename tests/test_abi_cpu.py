@@ -2,17 +2,20 @@
 symbol include/pn2_abi.h declares, and validates arguments before touching the device."""
 import ctypes
 import os
-import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _header():
+    """include/pn2_abi.h through the package's own parser (the one parser in the tree), from this file's idea of the path"""
+    from pn2_amd import _abi
+    return _abi.load(os.path.join(ROOT, "include", "pn2_abi.h"))
+
+
 def _declared():
-    src = open(os.path.join(ROOT, "include", "pn2_abi.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(pn2_[a-z0-9_]+)\s*\(", src)))
+    return sorted(_header().functions)
 
 
 def test_header_declares_the_nine_reference_ops():
@@ -35,9 +38,9 @@ def test_library_exports_every_declared_symbol(pn2):
 
 def test_bn_workspace_states_match_the_header(pn2):
     """PN2_BN_WS_* of include/pn2_abi.h are 0..3 in the documented order and _lib.BN_WS_* are the same numbers"""
-    src = open(os.path.join(ROOT, "include", "pn2_abi.h")).read()
-    states = {k: int(v) for k, v in re.findall(r"\bPN2_BN_WS_([A-Z]+)\s*=?\s*(\d+)", re.sub(r"/\*.*?\*/", "", src, flags=re.S))}
+    states = {k[len("PN2_BN_WS_"):]: v for k, v in _header().constants.items() if k.startswith("PN2_BN_WS_")}
     assert states == {"UNCLEARED": 0, "ZEROED": 1, "SUMMED": 2, "FOLDED": 3}
+    assert list(states) == ["UNCLEARED", "ZEROED", "SUMMED", "FOLDED"]
     for name, value in states.items():
         assert getattr(pn2._lib, "BN_WS_" + name) == value, name
 
@@ -104,10 +107,119 @@ def test_trace_table_positions_match_the_signatures(pn2):
             assert dense is None and drop == (), name
     # every *_ld entry point is in the table: none is recorded under its own name
     assert {n for n in L.SIGNATURES if n.endswith("_ld")} <= set(L._TRACE_ARGS)
-    # the size_t queries are bound from their table
-    for name, nargs in L._SIZE_QUERIES.items():
+    # the size_t queries are bound from the header: name -> number of int arguments
+    queries = {"pn2_fps_large_workspace_bytes": 2, "pn2_ball_query_bin_bytes": 1, "pn2_interpolate_label_workspace_bytes": 1,
+               "pn2_three_interpolate_grad_workspace_bytes": 3, "pn2_scatter_plan_bytes": 3,
+               "pn2_group_point_grad_workspace_bytes": 4, "pn2_voxel_downsample_workspace_bytes": 1, "pn2_bn_workspace_bytes": 1}
+    assert {name for name, f in _header().functions.items() if f.restype is ctypes.c_size_t} == set(queries)
+    for name, nargs in queries.items():
         fn = getattr(L._raw, name)
         assert fn.restype is ctypes.c_size_t and fn.argtypes == [ctypes.c_int] * nargs, name
+
+
+def test_every_traced_parameter_name_is_in_the_trace_table(pn2):
+    """a prototype with a parameter named nlayers, widths or ld* is decoded by the benchmark trace"""
+    for name, f in _header().functions.items():
+        if any(a in ("nlayers", "widths") or a.startswith("ld") for a in f.argnames):
+            assert name in pn2._lib._TRACE_ARGS, name
+
+
+def test_stateful_set_names_bound_entry_points(pn2):
+    L = pn2._lib
+    assert L._STATEFUL <= set(L.SIGNATURES)
+    for name, f in _header().functions.items():  # a moving average is caller state: never launched twice by the dup hook
+        if "running_mean" in f.argnames:
+            assert name in L._STATEFUL, name
+
+
+def test_six_signatures_by_hand(pn2):
+    """one entry point per kind of scalar the header uses, written out by hand against the derived table"""
+    i, f, d, p, z, ll = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong
+    S = pn2._lib.SIGNATURES
+    assert S["pn2_farthest_point_sample"] == [i, i, i, p, p, p, i, p]
+    assert S["pn2_fps_large"] == [i, i, i, p, p, z, p, p, i, p]
+    assert S["pn2_bn_relu_forward_mode"] == [ll, i, p, p, p, p, f, f, i, p, p, p, z, i, p, p, p, p]
+    assert S["pn2_scene_extract_z_box"] == [i, p, i, p, d, d, d, i, p, p, p]
+    assert S["pn2_dataset_sample"] == [i] * 6 + [p] * 7 + [i, d, d, ctypes.c_ulonglong, p, p, p, p, i, p, p, z] + [p] * 7
+    assert "pn2_fps_large_workspace_bytes" not in S
+    for name, sig in S.items():
+        fn = getattr(pn2._lib._raw, name)
+        assert fn.argtypes == sig and fn.restype is i, name
+    q = pn2._lib._raw.pn2_fps_large_workspace_bytes
+    assert q.restype is z and q.argtypes == [i, i]
+    assert pn2._lib._raw.pn2_build_info.restype is ctypes.c_char_p and pn2._lib._raw.pn2_strerror.argtypes == [i]
+
+
+MINI_HEADER = """
+/* a block comment that mentions pn2_x(int a); and spans
+ * lines */
+#ifndef MINI_H_
+#define MINI_H_
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define PN2_ABI_VERSION 7
+#define PN2_EBAD (-3)  /* parenthesised */
+enum { PN2_A = 0, PN2_B = 1, PN2_C = (-2) };
+int pn2_none(void);
+const char *pn2_name(int code);
+size_t pn2_bytes(int b, int n);
+int pn2_many(const float *inp, int *const *table, float* const* x, size_t nbytes, long long rows,
+             unsigned long long seed, double half_x,
+             const int ld1, float eps, void *stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_parser_on_an_inline_header():
+    from pn2_amd import _abi
+    i, p = ctypes.c_int, ctypes.c_void_p
+    abi = _abi.parse(MINI_HEADER)
+    assert list(abi.functions) == ["pn2_none", "pn2_name", "pn2_bytes", "pn2_many"]  # pn2_x lives in a comment
+    assert abi.functions["pn2_none"] == (i, [], ())
+    assert abi.functions["pn2_name"] == (ctypes.c_char_p, [i], ("code",))
+    assert abi.functions["pn2_bytes"] == (ctypes.c_size_t, [i, i], ("b", "n"))
+    many = abi.functions["pn2_many"]
+    assert many.restype is i
+    assert many.argtypes == [p, p, p, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_double, i, ctypes.c_float, p]
+    assert many.argnames == ("inp", "table", "x", "nbytes", "rows", "seed", "half_x", "ld1", "eps", "stream")
+    assert abi.constants == {"PN2_ABI_VERSION": 7, "PN2_EBAD": -3, "PN2_A": 0, "PN2_B": 1, "PN2_C": -2}
+
+
+@pytest.mark.parametrize("proto, message", [
+    ("int pn2_bad(short n);", "pn2_bad"),                        # unknown scalar: never bound as int
+    ("int pn2_bad(unsigned n);", "pn2_bad"),
+    ("int pn2_bad(int);", "pn2_bad"),                            # no parameter name
+    ("int pn2_bad(int widths[4]);", "array or function-pointer"),
+    ("int pn2_bad(int (*cb)(int, int), void *stream);", "array or function-pointer"),
+    ("void pn2_bad(int n);", "pn2_bad"),                         # unknown return type
+    ("int pn2_bad(int n)", "pn2_bad"),                           # no `;`: cannot be split
+    ("int pn2_bad int n;", "pn2_bad"),
+    ("int pn2_none(int a);", "declared twice"),
+    ("#define PN2_HALF 0.5", "PN2_HALF"),
+    ("enum { PN2_A = 0, PN2_NEXT };", "PN2_NEXT"),             # an implicit value is not guessed
+])
+def test_parser_refuses_what_it_does_not_understand(proto, message):
+    from pn2_amd import _abi
+    with pytest.raises(ValueError, match=message.replace("(", r"\(")):
+        _abi.parse("int pn2_none(void);\n" + proto + "\n")
+
+
+def test_parser_says_where_it_looked_for_a_missing_header(tmp_path):
+    from pn2_amd import _abi
+    missing = str(tmp_path / "include" / "pn2_abi.h")
+    with pytest.raises(ImportError, match=missing):
+        _abi.load(missing)
+
+
+def test_header_path_is_shared_with_the_build(pn2):
+    assert os.path.samefile(pn2.build.HEADER, os.path.join(ROOT, "include", "pn2_abi.h"))
+    assert pn2._lib.ABI.constants["PN2_ABI_VERSION"] == 2 and pn2._lib.ABI.constants["PN2_FPS_MAX_REG_POINTS"] == 16384
+    assert (pn2._lib.PN2_EUNSUP, pn2._lib.ABI.constants["PN2_ARITH_FMA_ALT"]) == (-4, 2)
 
 
 def test_launch_helper_host_arrays(pn2):

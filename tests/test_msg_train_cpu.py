@@ -2,18 +2,14 @@
 pn2_scatter_plan_apply_multi): exported, bound with the header's arity, and refusing bad call shapes before touching the device."""
 import ctypes
 import os
-import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("pn2_sa_hoist_rows_multi_bn", "pn2_scatter_plan_apply_multi")
 
 
 def _header_arity(name):
-    src = open(os.path.join(ROOT, "include", "pn2_abi.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\b%s\s*\(([^;]*?)\)\s*;" % name, src, flags=re.S)
-    assert m, name
-    return len([a for a in m.group(1).split(",") if a.strip()])
+    from pn2_amd import _abi
+    return len(_abi.load(os.path.join(ROOT, "include", "pn2_abi.h")).functions[name].argnames)
 
 
 def test_library_exports_and_binds_the_multi_scale_entry_points(pn2):
