@@ -1,7 +1,8 @@
 """End-to-end inference on one MI355X, mirroring what the reference's Predictor does per batch (predict.py:15-118):
     get_model (SA x4 + FP x4 + head)  ->  argmax  ->  interpolate_label_with_color onto the dense cloud,
 on synthetic scenes with random-init weights (no dataset / checkpoint is available offline).  Everything between the
-input batch and the dense labels stays on the device; the forward is replayed from one hipGraph.
+input batch and the dense labels stays on the device: pn2.predict.Predictor replays forward + argmax from one hipGraph and
+its interpolate_labels is the 3-NN vote.
 
     python examples/predict_synthetic.py [--batch 16] [--points 8192] [--dense 4000000]
 """
@@ -36,28 +37,25 @@ def main():
     rs = np.random.RandomState(0)
     hp = dict(pn2.model.SEMANTIC_HYPERPARAMS)
     hp["batch_size"], hp["num_point"] = args.batch, args.points
-    pn2.util.tf_util.set_default_store(pn2.util.tf_util.VariableStore(device=dev, seed=0))
     batch = torch.from_numpy(scene(rs, args.batch, args.points)).to(dev)
-
-    def forward(pc):
-        logits, _ = pn2.model.get_model(pc, False, args.num_class, hp)
-        return logits.argmax(dim=2).to(torch.int32)
-
-    predictor = pn2.runtime.CapturedForward(forward, batch)  # one hipGraph: ~40 kernels, no Python in the loop
+    # no checkpoint: fresh Xavier variables.  The first predict() captures forward + argmax (pn2_confusion_update's pred output,
+    # np.argmax semantics) into one hipGraph: ~40 kernels, no Python in the loop
+    predictor = pn2.predict.Predictor(None, args.num_class, hp, device=dev, seed=0)
+    predictor.predict(batch)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(10):
-        pred = predictor(batch)
+        pred = predictor.predict(batch)
     torch.cuda.synchronize()
     t_fwd = (time.perf_counter() - t0) / 10
     # label the dense cloud from the sparse predictions (predict.py:86-103: batch flattened to one sparse set)
     sparse_points = batch[:, :, :3].reshape(-1, 3).contiguous()
     sparse_labels = pred.reshape(-1).contiguous()
     dense = torch.from_numpy(scene(rs, 1, args.dense)[0, :, :3]).to(dev)
-    pn2.interpolate_label_with_color(sparse_points, sparse_labels, dense, 3)
+    predictor.interpolate_labels(sparse_points, sparse_labels, dense)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    dense_labels, dense_colors = pn2.interpolate_label_with_color(sparse_points, sparse_labels, dense, 3)
+    dense_labels, dense_colors = predictor.interpolate_labels(sparse_points, sparse_labels, dense)
     torch.cuda.synchronize()
     t_int = time.perf_counter() - t0
     hist = torch.bincount(dense_labels.clamp(min=0), minlength=args.num_class).tolist()

@@ -500,6 +500,16 @@ int pn2_weighted_ce_backward(int rows, int num_class, const float *logits, const
 int pn2_confusion_update(int rows, int num_class, const float *logits, const void *labels, int label64, int *pred,
                          long long *confusion, long long *invalid, const float *loss, double *loss_acc, void *stream);
 
+/* ConfusionMatrix.increment_from_list (util/metric.py) on the device: confusion[gt*C + pd] += 1 for every pair with both
+ * labels in [0, C); other pairs are dropped (sklearn's confusion_matrix(labels=range(C))) and, when dropped != NULL,
+ * counted there.  gt / pd: n labels each, int32 (label64 == 0) or int64 (label64 != 0: values beyond int32 must not wrap).
+ * confusion (C*C) and *dropped accumulate across calls and are never zeroed here.  Exact, independent of arrival order: each
+ * workgroup counts into a private uint32 histogram and adds its non-zero bins once, which bounds n at 2^39 pairs per call.
+ * PN2_EINVAL: n <= 0, n > 2^39 or num_class <= 0; PN2_EUNSUP: num_class > 64; PN2_ENULL: gt, pd or confusion NULL.
+ * No host synchronisation, no allocation: capturable into a graph. */
+int pn2_label_confusion(long long n, int num_class, const void *gt, const void *pd, int label64,
+                        long long *confusion, long long *dropped, void *stream);
+
 /* tf_util.dropout  util/tf_util.py:646-665 (tf.nn.dropout): y = x / keep_prob where kept, else 0; mask (n bytes) for the
  * backward.  state: device int64[2] = {seed, step}; the draw is a pure function of (seed, step, element index), so a
  * captured graph can be replayed while the caller advances `step` in device memory.  keep_prob = 1 keeps every element

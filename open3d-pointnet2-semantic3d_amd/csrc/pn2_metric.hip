@@ -83,6 +83,60 @@ confusion_update_kernel(int rows, int C, const float* __restrict__ logits, const
     }
 }
 
+// Confusion counts from two label arrays (ConfusionMatrix.increment_from_list): the same scheme as above without the logits.
+// Each lane takes kLabelUnroll pairs a grid sweep apart per iteration, all loads issued before the first use (plain 4- or
+// 8-byte loads, coalesced per wave: no alignment demand beyond the element's own).  A pair with either label outside [0, C)
+// -- compared at the labels' full width -- is left out of the matrix and counted per lane, summed per wave at the end.
+constexpr int kLabelUnroll = 4;
+// A workgroup counts at most n / (256 workgroups) + kLabelUnroll * 256 pairs into one uint32 bin (and into its uint32 count
+// of dropped pairs) once the grid is full: n <= 2^39 keeps that below 2^31 + 2^10.
+constexpr long long kLabelMaxPairs = 1ll << 39;
+
+template <typename LabelT>
+__global__ void __launch_bounds__(kMetricThreads)
+label_confusion_kernel(long long n, int C, const LabelT* __restrict__ gt, const LabelT* __restrict__ pd,
+                       unsigned long long* __restrict__ confusion, unsigned long long* __restrict__ dropped) {
+    __shared__ unsigned hist[kMetricMaxClasses * kMetricMaxClasses];
+    __shared__ unsigned s_dropped;
+    const int bins = C * C;
+    for (int i = threadIdx.x; i < bins; i += kMetricThreads) hist[i] = 0u;
+    if (threadIdx.x == 0) s_dropped = 0u;
+    __syncthreads();
+
+    const unsigned long long uc = (unsigned long long)C;
+    const long long sweep = (long long)gridDim.x * kMetricThreads;
+    unsigned my_dropped = 0u;
+    for (long long r = (long long)blockIdx.x * kMetricThreads + threadIdx.x; r < n; r += sweep * kLabelUnroll) {
+        LabelT g[kLabelUnroll], p[kLabelUnroll];
+#pragma unroll
+        for (int u = 0; u < kLabelUnroll; ++u) {
+            const long long i = r + u * sweep;
+            g[u] = i < n ? gt[i] : (LabelT)0;
+            p[u] = i < n ? pd[i] : (LabelT)0;
+        }
+#pragma unroll
+        for (int u = 0; u < kLabelUnroll; ++u) {
+            if (r + u * sweep >= n) break;
+            // sign-extended to 64 bits, then unsigned: a negative label and an int64 beyond int32 both compare >= C
+            const unsigned long long ug = (unsigned long long)(long long)g[u], up = (unsigned long long)(long long)p[u];
+            if (ug < uc && up < uc) atomicAdd(&hist[(int)ug * C + (int)up], 1u);
+            else ++my_dropped;
+        }
+    }
+    if (dropped) {
+#pragma unroll
+        for (int o = PN2_WAVE / 2; o >= 1; o >>= 1) my_dropped += __shfl_xor(my_dropped, o);
+        if ((threadIdx.x & (PN2_WAVE - 1)) == 0 && my_dropped) atomicAdd(&s_dropped, my_dropped);
+    }
+    __syncthreads();
+
+    for (int i = threadIdx.x; i < bins; i += kMetricThreads) {
+        const unsigned v = hist[i];
+        if (v) atomicAdd(&confusion[i], (unsigned long long)v);
+    }
+    if (threadIdx.x == 0 && dropped && s_dropped) atomicAdd(dropped, (unsigned long long)s_dropped);
+}
+
 }  // namespace
 
 // argmax + confusion-matrix update (+ running loss sum) of one batch; see include/pn2_abi.h.  Every argument check comes
@@ -106,6 +160,27 @@ extern "C" int pn2_confusion_update(int rows, int num_class, const float* logits
     else
         confusion_update_kernel<int><<<(int)blocks, kMetricThreads, 0, st>>>(
             rows, num_class, logits, static_cast<const int*>(labels), pred, cm, inv, loss, loss_acc);
+    PN2_RETURN_IF_LAUNCH_FAILED();
+    return PN2_OK;
+}
+
+// confusion counts of n (gt, pd) label pairs; see include/pn2_abi.h.  Every argument check comes before the first HIP call.
+extern "C" int pn2_label_confusion(long long n, int num_class, const void* gt, const void* pd, int label64,
+                                   long long* confusion, long long* dropped, void* stream) {
+    if (n <= 0 || num_class <= 0 || n > kLabelMaxPairs) return PN2_EINVAL;
+    if (num_class > kMetricMaxClasses) return PN2_EUNSUP;
+    if (!gt || !pd || !confusion) return PN2_ENULL;
+    long long blocks = (n + kMetricThreads - 1) / kMetricThreads;
+    if (blocks > kMetricMaxBlocks) blocks = kMetricMaxBlocks;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned long long* cm = reinterpret_cast<unsigned long long*>(confusion);
+    unsigned long long* dr = reinterpret_cast<unsigned long long*>(dropped);
+    if (label64)
+        label_confusion_kernel<long long><<<(int)blocks, kMetricThreads, 0, st>>>(
+            n, num_class, static_cast<const long long*>(gt), static_cast<const long long*>(pd), cm, dr);
+    else
+        label_confusion_kernel<int><<<(int)blocks, kMetricThreads, 0, st>>>(
+            n, num_class, static_cast<const int*>(gt), static_cast<const int*>(pd), cm, dr);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

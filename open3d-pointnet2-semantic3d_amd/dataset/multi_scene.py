@@ -143,9 +143,11 @@ class SemanticDataset:
 
     # ---- device store ------------------------------------------------------------------------------------------------
     def _upload(self, batch_size):
+        """the resident store (uploaded once) with `workspace` = the workspace of this batch size.  One workspace per batch
+        size: pn2_dataset_sample lays its workspace out by b and keeps only the histogram and candidate counts of THAT layout
+        zero between calls, so a workspace shared between batch sizes would hand a larger b the candidate lists of a smaller one
+        where it expects zeros (samples rejected with "candidate list full")."""
         d = self._dev
-        if d is not None and d["b"] >= batch_size:
-            return d
         dev = self.device
         if d is None:
             t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
@@ -154,12 +156,15 @@ class SemanticDataset:
                      labels=t(np.concatenate(self.scene_labels).astype(np.uint8), np.uint8),
                      offsets=t(self.scene_offsets, np.int32), cdf=t(self.scene_cdf, np.float64),
                      zsize=t(self.scene_z_size, np.float64), lw=t(self.label_weights, np.float32),
-                     counter=torch.zeros(1, dtype=torch.int64, device=dev))
-        nbytes = u64_array([0])  # written by the query
-        launch("pn2_dataset_workspace_size", dev, batch_size, self.max_chunks, nbytes, stream=False)
-        d["workspace"] = torch.zeros(nbytes[0] + 256, dtype=torch.uint8, device=dev)  # kept zero by the kernels
-        d["b"] = batch_size
-        self._dev = d
+                     counter=torch.zeros(1, dtype=torch.int64, device=dev), workspaces={})
+            self._dev = d
+        ws = d["workspaces"].get(batch_size)
+        if ws is None:
+            nbytes = u64_array([0])  # written by the query
+            launch("pn2_dataset_workspace_size", dev, batch_size, self.max_chunks, nbytes, stream=False)
+            ws = torch.zeros(nbytes[0] + 256, dtype=torch.uint8, device=dev)  # kept zero by the kernels
+            d["workspaces"][batch_size] = ws
+        d["workspace"] = ws
         return d
 
     @property
@@ -221,6 +226,60 @@ class SemanticDataset:
         self.last_scene, self.last_center, self.last_cnt = info[:, 0], info[:, 1], info[:, 2]
         self.last_status, self.last_sel, self.last_angle = info[:, 7], sel, finfo[:, 0]
         return data, label, weights
+
+    def _scene_view(self, d, scene):
+        """the one-scene view of the store pn2_dataset_sample reads for `scene`: its slices of points / colours / labels and its
+        small tables (offsets [0, count], cdf [1.0], its scene_z_size), made once per scene and kept on the device"""
+        views = d.setdefault("views", {})
+        v = views.get(scene)
+        if v is None:
+            dev = self.device
+            o, e = int(self.scene_offsets[scene]), int(self.scene_offsets[scene + 1])
+            v = dict(offset=o, points=d["points"][o:e], colors=None if d["colors"] is None else d["colors"][o:e],
+                     labels=d["labels"][o:e], offsets=torch.tensor([0, e - o], dtype=torch.int32).to(dev),
+                     cdf=torch.ones(1, dtype=torch.float64).to(dev),
+                     zsize=torch.tensor([self.scene_z_size[scene]], dtype=torch.float64).to(dev),
+                     max_chunks=int(max(1, (e - o + _CHUNK - 1) // _CHUNK)))
+            views[scene] = v
+        return v
+
+    def sample_batch_in_file(self, scene, batch_size):
+        """The reference's list_file_data[scene].sample_batch(batch_size, num_points_per_sample) (semantic_dataset.py:57-82, as
+        predict.py:163 calls it) on the resident store: every sample is a column of scene `scene`, un-augmented, drawn from
+        the device random numbers.  -> data (B,N,6|3) float32 (centred xyz [| rgb]), points_raw (B,N,3) float64 (the same
+        points as they lie in the scene), labels (B,N) int32, on the device.  pn2_dataset_sample on a one-scene view of the
+        store: no (B, len(scene)) tensor, no host synchronisation.  Advances batch_counter like any other batch; afterwards
+        last_scene (= scene), last_center, last_cnt, last_sel (store indices) and last_status describe the batch."""
+        b, n = int(batch_size), self.num_points_per_sample
+        if b <= 0:
+            raise ValueError("batch_size must be positive")
+        scene = int(scene)
+        if not 0 <= scene < self.num_scenes:
+            raise ValueError("scene %d: the store holds scenes 0 .. %d" % (scene, self.num_scenes - 1))
+        d = self._upload(b)
+        v = self._scene_view(d, scene)
+        dev = self.device
+        data = torch.empty((b, n, 6 if self.use_color else 3), dtype=torch.float32, device=dev)
+        label = torch.empty((b, n), dtype=torch.int32, device=dev)
+        weights = torch.empty((b, n), dtype=torch.float32, device=dev)
+        sel = torch.empty((b, n), dtype=torch.int32, device=dev)
+        info = torch.empty((b, _INFO), dtype=torch.int32, device=dev)
+        finfo = torch.empty((b, 3), dtype=torch.float64, device=dev)
+        ws = d["workspace"]  # this batch size's own, sized for the store's longest scene: enough for any one of them
+        base = (-ws.data_ptr()) % 256
+        launch("pn2_dataset_sample", dev,
+               b, n, 1, v["max_chunks"], int(self.use_color), 0, ptr(v["points"]), ptr(v["colors"]), ptr(v["labels"]),
+               ptr(v["offsets"]), ptr(v["cdf"]), ptr(v["zsize"]), None, 0, self.box_size_x / 2, self.box_size_y / 2, self.seed,
+               ptr(d["counter"]), None, None, None, 0, None, ptr(ws[base:]), ws.numel() - base, ptr(info), ptr(finfo), ptr(sel),
+               ptr(data), ptr(label), ptr(weights))
+        # view-local -> store indices; a rejected sample keeps its -1 (its rows of points_raw are then the store's last point:
+        # check_last() tells)
+        self.last_sel = torch.where(sel < 0, sel, sel + v["offset"])
+        points_raw = d["points"][self.last_sel.long()]
+        self.last_scene = torch.full((b,), scene, dtype=torch.int32, device=dev)
+        self.last_center, self.last_cnt = info[:, 1], info[:, 2]
+        self.last_status, self.last_angle = info[:, 7], finfo[:, 0]
+        return data, points_raw, label
 
     def check_last(self):
         """raise if a sample of the last batch was rejected (zero-filled); one host synchronisation."""

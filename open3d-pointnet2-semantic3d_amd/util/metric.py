@@ -5,6 +5,8 @@ per point after reading the logits back to the host.  Here the same class keeps 
 reference's behaviour, `device=None`) or in a device int64 tensor (`device="cuda"`): `increment_from_logits` then runs
 pn2_confusion_update -- argmax and counting in one launch, no host synchronisation -- so it can sit inside a captured
 training step.  Reading `confusion_matrix` or any `get_*` is the only synchronisation.
+`increment_from_list` on device label tensors (predict.py, interpolate.py) runs pn2_label_confusion: the same counting from two
+label arrays, without temporaries.
 
 Semantic3D convention (the reference's): ground-truth label 0 ("unlabeled") is ignored by the IoU and the accuracy.
 """
@@ -26,7 +28,7 @@ SEMANTIC3D_LABELS_NAMES = [
     "cars",
 ]
 
-MAX_CLASSES = 64  # pn2_confusion_update (= the cross-entropy kernel's limit)
+MAX_CLASSES = 64  # pn2_confusion_update, pn2_label_confusion (= the cross-entropy kernel's limit)
 
 
 def _flat_labels(labels):
@@ -57,6 +59,25 @@ def confusion_update(logits, labels, confusion=None, invalid=None, pred=None, lo
             raise ValueError("%s: a contiguous %s tensor of %d elements on %s expected" % (name, dt, n, z.device))
     launch("pn2_confusion_update", z, rows, c, ptr(z), ptr(lab), int(lab.dtype == torch.int64), ptr(pred), ptr(confusion), ptr(invalid),
            ptr(loss), ptr(loss_acc))
+
+
+def label_confusion(gt_labels, pd_labels, confusion, dropped=None):
+    """One pn2_label_confusion launch on the current stream: confusion (C*C int64, added to)[gt * C + pd] += 1 for every pair
+    of the two flat, contiguous device label tensors (both int32 or both int64) with both labels in [0, C); the other pairs
+    are left out and counted in dropped (int64 tensor of one element, added to) when given."""
+    from .._lib import launch, ptr, require_cuda
+    require_cuda(gt_labels, pd_labels, confusion, dropped)
+    n = gt_labels.numel()
+    if gt_labels.dtype != pd_labels.dtype or gt_labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError("gt_labels and pd_labels: both int32 or both int64")
+    if pd_labels.numel() != n or not (gt_labels.is_contiguous() and pd_labels.is_contiguous()):
+        raise ValueError("gt_labels and pd_labels: contiguous and of one length")
+    c = int(round(confusion.numel() ** 0.5))
+    for name, t, m in (("confusion", confusion, c * c), ("dropped", dropped, 1)):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != m or not t.is_contiguous() or t.device != gt_labels.device):
+            raise ValueError("%s: a contiguous int64 tensor of %d elements on %s expected" % (name, m, gt_labels.device))
+    launch("pn2_label_confusion", gt_labels, n, c, ptr(gt_labels), ptr(pd_labels), int(gt_labels.dtype == torch.int64),
+           ptr(confusion), ptr(dropped))
 
 
 class ConfusionMatrix:
@@ -143,6 +164,18 @@ class ConfusionMatrix:
         labels=range(num_classes), as the reference calls it).  Device storage and device tensors: stays on the device."""
         c = self.num_classes
         if self.device is not None and torch.is_tensor(gt_labels) and gt_labels.is_cuda:
+            if c <= MAX_CLASSES:
+                # pn2_label_confusion: int32 / int64 contiguous inputs go in as they are, anything else is cast once
+                gt, pd = gt_labels.reshape(-1), torch.as_tensor(pd_labels, device=gt_labels.device).reshape(-1)
+                if gt.numel() != pd.numel():
+                    raise ValueError("gt_labels and pd_labels differ in length")
+                if gt.dtype != pd.dtype or gt.dtype not in (torch.int32, torch.int64):
+                    gt, pd = gt.long(), pd.long()
+                gt, pd = gt.contiguous(), pd.contiguous()
+                if gt.numel():
+                    label_confusion(gt, pd, self.counts[:c * c])
+                return
+            # above the kernel's class limit: torch
             gt = gt_labels.reshape(-1).long()
             pd = torch.as_tensor(pd_labels, device=gt.device).reshape(-1).long()
             if gt.numel() != pd.numel():
