@@ -622,11 +622,12 @@ int pn2_fp_mlp_fused_pre_schedule(int b, int n, int m, int c1, const float *dist
                                   const float *const *bias, float *y, int schedule, void *stream);
 
 /* Row packing of the pooled nsample = 32 set-abstraction kernels (pn2_sa_mlp_max_fused, _ld, pn2_sa_mlp_fused_pre with
- * pool): the ball query pads a short row with copies of its first hit; the kernels find the live prefix of every index row
- * (the smallest s in {8, 16, 32} with idx[j] == idx[0] for all j >= s, read from idx itself) and put four centres with
- * s = 8 or two with s = 16 into one 32-row matrix tile.  Same bits as without it for ANY index table.  Process-wide; on
- * (non-zero) by default; read when a launch is issued (a captured graph keeps the choice it was captured with).  The switch
- * exists for A/B timing and the parity test. */
+ * pool; pn2_sa_mlp_wide and pn2_sa_mlp_wide_pre with pool and an idx that is 16-byte aligned): the ball query pads a short
+ * row with copies of its first hit; the kernels find the live prefix of every index row (the smallest s in {8, 16, 32} with
+ * idx[j] == idx[0] for all j >= s, read from idx itself) and put four centres with s = 8 or two with s = 16 into one 32-row
+ * matrix tile.  Same bits as without it for ANY index table.  One switch for all of them.  Process-wide; on (non-zero) by
+ * default; read when a launch is issued (a captured graph keeps the choice it was captured with).  The switch exists for
+ * A/B timing and the parity tests. */
 int pn2_set_sa_row_packing(int on);
 
 /* pn2_sa_mlp_max_fused / pn2_sa_mlp_rows_fused with the FEATURE part of the first layer hoisted by linearity:

@@ -47,6 +47,10 @@ int pn2_allow_lds(int bytes) {
     return 0;
 }
 
+// Is the row packing of the pooled nsample = 32 set-abstraction kernels on?  (pn2_set_sa_row_packing, include/pn2_abi.h: one
+// process-wide switch for pn2_sa_fused.hip and pn2_mlp_wide.hip, defined in the former.)  Read when a launch is issued.
+__attribute__((visibility("hidden"))) bool pn2_sa_row_packing_enabled();
+
 // Training-mode batch-norm workspace (pn2_bn.hip; pn2_linear_bn_stats in pn2_linear.hip writes into it), in doubles:
 //   head[kPn2BnHead] | final[2][c] | slot[nslots][2][c], nslots <= kPn2BnSlots chosen per call
 // head (zeroed with the rest of the workspace) holds the ticket counters of pn2_bn_finish: 64 first-level + 1 second-level.

@@ -53,7 +53,7 @@ struct WideParams {
     // (FP, b*m rows) or points @ W0[feature rows] (SA, b*n rows).  The layer-0 tile then holds only the skip-link channels
     // (FP: cin = c1) or dx dy dz (SA: cin = 3), and the layer-0 epilogue adds the blended / gathered rows of zpre.
     const float* zpre;
-    int rowtab_off;     // floats from the start of LDS: the FP front end's 32 x 8 row table when zpre is set
+    int rowtab_off;     // floats from the start of LDS: the FP front end's 32 x 8 row table when zpre is set; PACK: kPackLdsInts
     int sa[2];          // row strides (floats) of the two activation buffers
     int scratch_off;    // floats from the start of LDS (dedicated scratch)
     int scratch_alias;  // 1: the K-slice partial sums are parked in the layer's (consumed) input buffer
@@ -63,11 +63,26 @@ struct WideParams {
 // host hands over W0 with its rows in that order.
 // INTERP: the A tile of layer 0 is the FP front end [three_interpolate(points2, idx, w(dist)) | points1]
 // (pointnet_util.py:300-311), formed with the float expressions of fp_interp_concat_* / the reference ops.
+//
+// PACK (GATHER with pool == 32): the ball query pads a short index row with copies of its first hit, a padded row's MLP output is
+// a copy too and the max does not count copies (pn2_sa_fused.hip, PACK).  A group's class is the smallest s in {8, 16, 32} with
+// idx[j] == idx[0] for all j >= s; four class-8 or two class-16 groups share one 32-row tile.  A workgroup still carries ONE tile
+// (a tile is ~27 us of matrix time on its CU: a loop over tiles would multiply the single-batch latency), so the packing is
+// decided per chunk of kPackChunk consecutive groups, redundantly by every workgroup of the chunk: thread i classifies group i
+// of the chunk, ranks come from ballots and popcounts through LDS, workgroup j of the chunk takes tile j of the chunk's list
+// (class-32 tiles, then pairs of class 16, then fours of class 8) and the workgroups behind the list return.  No atomics, no
+// second launch; the grid stays one workgroup per group.  The tile's 32 source rows (cloud base included: a tile may mix clouds)
+// and its groups live in LDS, nothing of it in vector registers across the layer loop.  Every row keeps its own MFMA row and the
+// contraction is cut and added as without PACK: same bits for any index table.
 enum { kWidePlain = 0, kWideGather = 1, kWideInterp = 2 };
-template <int MODE>
+constexpr int kPackChunk = 256;  // groups per chunk = threads per workgroup
+// PACK's LDS region (ints, at rowtab_off): source row of each tile row | groups of the slots | log2(slot rows), filled slots | counts
+constexpr int kPackRows = 0, kPackGroups = 32, kPackMeta = 36, kPackCounts = 40, kPackLdsInts = 64;
+template <int MODE, bool PACK = false>
 __global__ void __launch_bounds__(256, 2)
 mlp_wide_kernel(WideParams p) {
     constexpr bool GATHER = MODE == kWideGather;
+    static_assert(!PACK || GATHER, "PACK: the pooled gather mode only");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63, half = lane >> 5, l31 = lane & 31;
@@ -109,7 +124,74 @@ mlp_wide_kernel(WideParams p) {
         for (int u = 0; u < kWideDepth; ++u) fetch_b(c, c.g0 + u < c.g1 ? c.g0 + u : c.g1 - 1, bq[u]);
     };
     const LayerCfg first = make_cfg(0, p.cin);
-    prefetch_b(first);
+    int* const pk = reinterpret_cast<int*>(smem + p.rowtab_off);  // PACK only
+    (void)pk;
+    if constexpr (PACK) {
+        const int groups = p.rows >> 5;
+        const int cbase = (tile / kPackChunk) * kPackChunk, mytile = tile - cbase;
+        const int cnt = min(kPackChunk, groups - cbase);
+        // classify: live slots = 1 + the last position that differs from position 0 (NOT the number of distinct values)
+        int cls = 0;
+        if (tid < cnt) {
+            const int4* __restrict__ ip = reinterpret_cast<const int4*>(p.idx + (size_t)(cbase + tid) * 32);
+            int4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = ip[u];
+            const int head = v[0].x;
+            int live = 1;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                if (v[u].x != head) live = 4 * u + 1;
+                if (v[u].y != head) live = 4 * u + 2;
+                if (v[u].z != head) live = 4 * u + 3;
+                if (v[u].w != head) live = 4 * u + 4;
+            }
+            cls = live <= 8 ? 8 : (live <= 16 ? 16 : 32);
+        }
+        const unsigned long long m32 = __ballot(cls == 32), m16 = __ballot(cls == 16), m8 = __ballot(cls == 8);
+        if (lane == 0) {
+            pk[kPackCounts + 3 * wave + 0] = __popcll(m32);
+            pk[kPackCounts + 3 * wave + 1] = __popcll(m16);
+            pk[kPackCounts + 3 * wave + 2] = __popcll(m8);
+        }
+        __syncthreads();
+        int n32 = 0, n16 = 0, n8 = 0, b32 = 0, b16 = 0, b8 = 0;  // totals of the chunk, counts of the waves below this one
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int c32 = pk[kPackCounts + 3 * w], c16 = pk[kPackCounts + 3 * w + 1], c8 = pk[kPackCounts + 3 * w + 2];
+            n32 += c32; n16 += c16; n8 += c8;
+            if (w < wave) { b32 += c32; b16 += c16; b8 += c8; }
+        }
+        n32 = __builtin_amdgcn_readfirstlane(n32); n16 = __builtin_amdgcn_readfirstlane(n16); n8 = __builtin_amdgcn_readfirstlane(n8);
+        // an odd class-16 group shares its tile with the last class-8 group when that saves the class-8 tile it would open
+        const int promote = ((n16 & 1) && (n8 & 3) == 1) ? 1 : 0;
+        const int k16 = n16 + promote, k8 = n8 - promote, t16 = (k16 + 1) >> 1;
+        const int ntiles = n32 + t16 + ((k8 + 3) >> 2);
+        if (mytile >= ntiles) return;  // uniform: the chunk packed into fewer tiles than it has groups
+        prefetch_b(first);  // after the decision (a returning workgroup streams no weights), in flight under the ranking and the staging
+        if (cls != 0) {
+            const unsigned long long below = (1ull << lane) - 1ull;
+            int t, slot;
+            if (cls == 32) { t = b32 + __popcll(m32 & below); slot = 0; }
+            else {
+                int c = cls, r = cls == 16 ? b16 + __popcll(m16 & below) : b8 + __popcll(m8 & below);
+                if (promote && c == 8 && r == n8 - 1) { c = 16; r = n16; }
+                if (c == 16) { t = n32 + (r >> 1); slot = r & 1; }
+                else { t = n32 + t16 + (r >> 2); slot = r & 3; }
+            }
+            if (t == mytile) pk[kPackGroups + slot] = cbase + tid;
+        }
+        if (tid == 0) {  // tile `mytile` of the list: slot size and filled slots (the last tile of a class may be short)
+            int sshift, nvalid;
+            if (mytile < n32) { sshift = 5; nvalid = 1; }
+            else if (mytile < n32 + t16) { sshift = 4; nvalid = min(2, k16 - 2 * (mytile - n32)); }
+            else { sshift = 3; nvalid = min(4, k8 - 4 * (mytile - n32 - t16)); }
+            pk[kPackMeta] = sshift; pk[kPackMeta + 1] = nvalid;
+        }
+        __syncthreads();
+    } else {
+        prefetch_b(first);
+    }
 
     // ---- stage the input tile ------------------------------------------------------------------------------------
     const int K0 = (p.cin + 7) & ~7;
@@ -137,12 +219,26 @@ mlp_wide_kernel(WideParams p) {
     };
     if constexpr (GATHER) {
         const int c = p.c, cv = c >> 2;  // c % 4 == 0
-        const int bi = tile / p.m;       // one tile = one centre (K = 32)
+        const int bi = PACK ? 0 : tile / p.m;  // one tile = one centre (K = 32); PACK: the row table holds rows of (b*n, c)
         const float* __restrict__ pts = p.points + (size_t)bi * p.n * c;
-        const int* __restrict__ idx = p.idx + (size_t)tile * 32;
+        const int* __restrict__ idx = PACK ? pk + kPackRows : p.idx + (size_t)tile * 32;
         float* myrow = buf0 + (tid & 31) * p.sa[0];
         float dx = 0.f, dy = 0.f, dz = 0.f;
-        if (tid < 32) {
+        if constexpr (PACK) {
+            // row r of the tile: slot r >> sshift, position r & (slot rows - 1) of that slot's group; the empty slots of a short
+            // tile repeat the first group (their maxima are not stored)
+            if (tid < 32) {
+                const int sshift = pk[kPackMeta], nvalid = pk[kPackMeta + 1];
+                const int q = tid >> sshift;
+                const int g = pk[kPackGroups + (q < nvalid ? q : 0)];
+                const int src = (g / p.m) * p.n + p.idx[(size_t)g * 32 + (tid & ((1 << sshift) - 1))];
+                pk[kPackRows + tid] = src;
+                const float* __restrict__ q3 = p.xyz + (size_t)src * 3;
+                const float* __restrict__ ctr = p.new_xyz + (size_t)g * 3;
+                dx = q3[0] - ctr[0]; dy = q3[1] - ctr[1]; dz = q3[2] - ctr[2];
+            }
+            __syncthreads();  // the row table is read by every thread (here or in the layer-0 epilogue)
+        } else if (tid < 32) {
             const float* __restrict__ q = p.xyz + ((size_t)bi * p.n + idx[tid]) * 3;
             const float* __restrict__ ctr = p.new_xyz + (size_t)tile * 3;
             dx = q[0] - ctr[0]; dy = q[1] - ctr[1]; dz = q[2] - ctr[2];  // pointnet_util.py:44-46
@@ -370,8 +466,8 @@ mlp_wide_kernel(WideParams p) {
                     for (int t = 0; t < 4; ++t) acc[t][r] += z[t];
                 }
             } else if constexpr (MODE == kWideGather) {
-                const float* __restrict__ zb = p.zpre + (size_t)(tile / p.m) * p.n * N + cb + 4 * l31;
-                const int* __restrict__ idx = p.idx + (size_t)tile * 32;
+                const float* __restrict__ zb = p.zpre + (PACK ? (size_t)0 : (size_t)(tile / p.m) * p.n * N) + cb + 4 * l31;
+                const int* __restrict__ idx = PACK ? pk + kPackRows : p.idx + (size_t)tile * 32;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
@@ -393,6 +489,40 @@ mlp_wide_kernel(WideParams p) {
                     f32x4 v = {acc[0][r] + bv[0], acc[1][r] + bv[1], acc[2][r] + bv[2], acc[3][r] + bv[3]};
                     v = {fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
                     *reinterpret_cast<f32x4*>(out + row * so + cb + 4 * l31) = v;
+                }
+            } else if constexpr (PACK) {
+                // segmented max: rows 8q .. 8q+7 are registers 4q .. 4q+3 of both half-waves; a slot of 8 / 16 / 32 rows is one /
+                // two / four of these quarters.  A maximum does not depend on the order it is taken in, nor on how often a value
+                // occurs: the bits of the un-packed epilogue over the group's 32 rows.
+                const int sshift = __builtin_amdgcn_readfirstlane(pk[kPackMeta]);
+                const int nvalid = __builtin_amdgcn_readfirstlane(pk[kPackMeta + 1]);
+                f32x4 qm[4];  // qm[q][t]: quarter q of column tile t
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const float mx = fmaxf(fmaxf(acc[t][4 * q], acc[t][4 * q + 1]), fmaxf(acc[t][4 * q + 2], acc[t][4 * q + 3]));
+                        qm[q][t] = fmaxf(mx, __shfl_xor(mx, 32));
+                    }
+                auto store = [&](int slot, const f32x4& mx) {
+                    if (half == 0 && slot < nvalid) {
+                        f32x4 v = mx + bv;
+                        if (relu) v = {fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+                        const int g = pk[kPackGroups + slot];
+                        *reinterpret_cast<f32x4*>(p.y + (size_t)g * N + cb + 4 * l31) = v;
+                    }
+                };
+                auto vmax = [](const f32x4& a, const f32x4& b) {
+                    return f32x4{fmaxf(a[0], b[0]), fmaxf(a[1], b[1]), fmaxf(a[2], b[2]), fmaxf(a[3], b[3])};
+                };
+                if (sshift == 3) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) store(q, qm[q]);
+                } else if (sshift == 4) {
+                    store(0, vmax(qm[0], qm[1]));
+                    store(1, vmax(qm[2], qm[3]));
+                } else {
+                    store(0, vmax(vmax(qm[0], qm[1]), vmax(qm[2], qm[3])));
                 }
             } else if (p.pool == 32) {
                 f32x4 v;
@@ -421,10 +551,10 @@ mlp_wide_kernel(WideParams p) {
     }
 }
 
-template <int MODE>
+template <int MODE, bool PACK = false>
 int launch_mlp_wide_mode(const WideParams& p, size_t lds, hipStream_t st) {
-    if (int e = pn2_allow_lds<mlp_wide_kernel<MODE>>(kPn2CuLdsBytes)) return e;
-    mlp_wide_kernel<MODE><<<(p.rows + 31) / 32, 256, lds, st>>>(p);
+    if (int e = pn2_allow_lds<mlp_wide_kernel<MODE, PACK>>(kPn2CuLdsBytes)) return e;
+    mlp_wide_kernel<MODE, PACK><<<(p.rows + 31) / 32, 256, lds, st>>>(p);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }
@@ -452,8 +582,13 @@ int launch_mlp_wide(WideParams& p, int mode, hipStream_t st) {
     p.scratch_off = 32 * (p.sa[0] + p.sa[1]);
     p.scratch_alias = sliced && alias_ok;
     p.rowtab_off = p.scratch_off + (sliced && !alias_ok ? 2 * 64 * 64 : 0);
-    const size_t lds = sizeof(float) * ((size_t)p.rowtab_off + (p.zpre && mode == kWideInterp ? 32 * 8 : 0));
+    // row packing (see the kernel): the pooled gather mode, the process-wide switch of the SA kernels read at launch (a captured
+    // graph keeps what it was captured with); idx is read 16 bytes at a time and a source row is an int
+    const bool pack = mode == kWideGather && p.pool == 32 && pn2_sa_row_packing_enabled() && (((uintptr_t)p.idx) & 15) == 0 &&
+                      (long long)(p.rows / 32 / p.m) * p.n <= 0x7fffffffLL;
+    const size_t lds = sizeof(float) * ((size_t)p.rowtab_off + (p.zpre && mode == kWideInterp ? 32 * 8 : 0) + (pack ? kPackLdsInts : 0));
     if (lds > kPn2CuLdsBytes) return PN2_EUNSUP;
+    if (pack) return launch_mlp_wide_mode<kWideGather, true>(p, lds, st);
     if (mode == kWideGather) return launch_mlp_wide_mode<kWideGather>(p, lds, st);
     if (mode == kWideInterp) return launch_mlp_wide_mode<kWideInterp>(p, lds, st);
     return launch_mlp_wide_mode<kWidePlain>(p, lds, st);

@@ -1173,6 +1173,8 @@ extern "C" int pn2_debug_set_fused(int what, int value) {
 
 // Row packing of the pooled K = 32 set-abstraction kernels on (non-zero, the default) or off: same bits either way (the A/B and
 // parity switch).  Takes effect for launches issued after the call.
+bool pn2_sa_row_packing_enabled() { return g_sa_row_packing.load(std::memory_order_relaxed) != 0; }
+
 extern "C" int pn2_set_sa_row_packing(int on) {
     g_sa_row_packing.store(on != 0, std::memory_order_relaxed);
     return PN2_OK;

@@ -388,6 +388,7 @@ def sa_features_inference(xyz, new_xyz, points, idx, mlp, bn=True, bn_decay=None
                 else:
                     folded.append(tf_util.folded_dense(cprev, cout, bn, (1, 1, cprev, cout), pad_to=32))
             cprev = cout
+        _sync_sa_row_packing(xyz)  # the pooled wide kernel packs rows too (csrc/pn2_mlp_wide.hip, PACK)
         if USE_HOISTED_SA:
             new_points = tf_util.hip_sa_mlp_wide_pre(xyz, new_xyz, points, idx, [f[0] for f in folded], [f[1] for f in folded])
         if new_points is None:

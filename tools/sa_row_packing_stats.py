@@ -2,12 +2,13 @@
 """The premise of the SA row packing (csrc/pn2_sa_fused.hip, PACK), counted on the CPU: for a benchmark input, how many of the
 32 rows of a ball-query group are live, and how many 32-row tiles the packed kernels run per tile of the un-packed ones.
 
-    python tools/sa_row_packing_stats.py [--input s_scene|s_randn|s_dup25] [--clouds 16] [--points 8192] [--block 64]
+    python tools/sa_row_packing_stats.py [--input s_scene|s_randn|s_dup25] [--clouds 16] [--points 8192] [--block 64] [--wide]
 
 Geometry from the CPU oracle (oracle/), inputs from benchlib.inputs (seed 0), levels from SEMANTIC_HYPERPARAMS.  A group's
 class is the smallest s in {8, 16, 32} with idx[j] == idx[0] for all j >= s; a block of `--block` consecutive centres packs
 four class-8 or two class-16 groups into a tile (an odd class-16 group takes one class-8 group along when that saves a tile),
-exactly as the kernel does.  No GPU needed.
+exactly as the kernel does.  --wide: the wide kernel's packer (csrc/pn2_mlp_wide.hip, PACK) -- chunks of 256 consecutive groups,
+one workgroup per tile of the chunk's list (chunk_tiles below restates it); the count is then that of --block 256.  No GPU needed.
 """
 import argparse
 import os
@@ -46,13 +47,37 @@ def packed_tiles(cls, block):
     return tiles
 
 
+WIDE_CHUNK = 256  # groups per chunk of the wide kernel's packer = threads of a workgroup
+
+
+def chunk_tiles(cls, base=0):
+    """The wide kernel's tile list of ONE chunk: cls = classes of its (at most WIDE_CHUNK) consecutive groups, base = id of the
+    first.  -> [(slot rows, [group ids, one per filled slot])]: class-32 tiles, then pairs of class 16, then fours of class 8, the
+    groups of a class in their own order; an odd class-16 group takes the LAST class-8 group along when that saves a tile.
+    Workgroup j of the chunk runs tile j; the workgroups behind the list return."""
+    cls = np.asarray(cls)
+    assert 0 < len(cls) <= WIDE_CHUNK
+    g32 = [base + i for i in np.flatnonzero(cls == 32)]
+    g16 = [base + i for i in np.flatnonzero(cls == 16)]
+    g8 = [base + i for i in np.flatnonzero(cls == 8)]
+    if (len(g16) & 1) and (len(g8) & 3) == 1:
+        g16.append(g8.pop())
+    tiles = [(32, [g]) for g in g32]
+    tiles += [(16, g16[i:i + 2]) for i in range(0, len(g16), 2)]
+    tiles += [(8, g8[i:i + 4]) for i in range(0, len(g8), 4)]
+    return tiles
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--input", default="s_scene", choices=("s_scene", "s_randn", "s_dup25"))
     ap.add_argument("--clouds", type=int, default=16)
     ap.add_argument("--points", type=int, default=8192)
     ap.add_argument("--block", type=int, default=64)
+    ap.add_argument("--wide", action="store_true", help="the wide kernel's packer: chunks of %d groups" % WIDE_CHUNK)
     args = ap.parse_args()
+    if args.wide and args.block != ap.get_default("block"):
+        ap.error("--wide fixes the chunk at %d groups: do not give --block with it" % WIDE_CHUNK)
     from benchlib import inputs
     from oracle import oracle as O
     O.build()
@@ -65,7 +90,8 @@ def main():
         cls = classes(idx)
         print("%-8s SA%d   %7d %14.1f   %.2f / %.2f / %.2f     %.2f" % (
             args.input, lv, len(cls), live_slots(idx).mean(), (cls == 8).mean(), (cls == 16).mean(), (cls == 32).mean(),
-            packed_tiles(cls, args.block) / float(len(cls))))
+            (sum(len(chunk_tiles(cls[lo:lo + WIDE_CHUNK], lo)) for lo in range(0, len(cls), WIDE_CHUNK)) if args.wide
+             else packed_tiles(cls, args.block)) / float(len(cls))))
         xyz = new_xyz
 
 
