@@ -22,7 +22,13 @@
 //     before the current layer's epilogue (weights do not depend on it);
 //   * the weights stream from L2 once per workgroup and layer (256 KB x rows/32: 64 MB per 256-wide layer at 8192 rows,
 //     ~5 us of the XCDs' aggregate L2 bandwidth beside ~9 us of MFMA time).
+//
+// Host side (the end of this file): the five entry points (pn2_mlp_wide, pn2_sa_mlp_wide, pn2_fp_mlp_wide and the two *_pre
+// forms with a hoisted first layer) keep their own argument checks and front-end fields; fill_wide reads the layer stack
+// (pn2_layer_stack.h: 1 .. 3 layers of 128 / 256 / 512, weights and biases 16-byte aligned), checks the row count and fills
+// what every mode shares; launch_mlp_wide lays out LDS and picks the kernel (plain / gather / gather + PACK / interp).
 #include "pn2_common.h"
+#include "pn2_layer_stack.h"
 
 namespace {
 
@@ -594,14 +600,18 @@ int launch_mlp_wide(WideParams& p, int mode, hipStream_t st) {
     return launch_mlp_wide_mode<kWidePlain>(p, lds, st);
 }
 
-int check_layers(int nlayers, const int* widths, const float* const* w, const float* const* bias) {
-    if (nlayers < 1 || nlayers > 3) return PN2_EUNSUP;
-    if (!widths || !w || !bias) return PN2_ENULL;
-    for (int l = 0; l < nlayers; ++l) {
-        if (widths[l] != 128 && widths[l] != 256 && widths[l] != 512) return PN2_EUNSUP;
-        if (!w[l] || !bias[l]) return PN2_ENULL;
-        if ((((uintptr_t)w[l]) | ((uintptr_t)bias[l])) & 15) return PN2_EUNSUP;
-    }
+constexpr Pn2LayerRule kWideLayers = {3, kPn2WidthsWide, kPn2AlignWeightsAndBias, false};
+
+// What the five entry points fill the same way, behind their own argument checks: the layer stack (pn2_layer_stack.h holds the
+// rule and the precedence of its refusals), then the row count -- handed over as long long, b * m * 32 is not formed in an int
+// before it is known to fit -- and the fields of every mode.  `between`: the result of the checks an entry point ranks behind
+// the layer stack's faults and ahead of PN2_ERANGE (pn2_mlp_wide's pool and y).
+int fill_wide(WideParams& p, long long rows, int cin, int nlayers, const int* widths, const float* const* w,
+              const float* const* bias, int pool, int relu_last, float* y, int between = PN2_OK) {
+    if (int rc = pn2_read_layers(p, kWideLayers, nlayers, widths, w, bias)) return rc;
+    if (between != PN2_OK) return between;
+    if (rows + 64 > 0x7fffffffLL) return PN2_ERANGE;
+    p.rows = (int)rows; p.cin = cin; p.nlayers = nlayers; p.pool = pool; p.relu_last = relu_last; p.y = y;
     return PN2_OK;
 }
 
@@ -611,16 +621,12 @@ extern "C" int pn2_mlp_wide(int rows, int cin, int x_stride, const float* x, int
                             const float* const* w, const float* const* bias, int relu_last, int pool, float* y, void* stream) {
     if (rows <= 0 || cin <= 0 || x_stride < cin) return PN2_EINVAL;
     if (!x || !y) return PN2_ENULL;
-    int rc = check_layers(nlayers, widths, w, bias);
-    if (rc != PN2_OK) return rc;
-    if (pool != 0 && pool != 32) return PN2_EUNSUP;
-    if (pool == 32 && rows % 32 != 0) return PN2_EINVAL;
-    if (((uintptr_t)y) & 15) return PN2_EUNSUP;
-    if ((long long)rows + 64 > 0x7fffffffLL) return PN2_ERANGE;
+    const int own = (pool != 0 && pool != 32) ? PN2_EUNSUP
+                    : (pool == 32 && rows % 32 != 0) ? PN2_EINVAL
+                    : (((uintptr_t)y) & 15) ? PN2_EUNSUP : PN2_OK;
     WideParams p = {};
-    p.rows = rows; p.cin = cin; p.x_stride = x_stride; p.nlayers = nlayers; p.pool = pool; p.relu_last = relu_last;
-    p.x = x; p.y = y;
-    for (int l = 0; l < nlayers; ++l) { p.w[l] = widths[l]; p.W[l] = w[l]; p.bias[l] = bias[l]; }
+    if (int rc = fill_wide(p, rows, cin, nlayers, widths, w, bias, pool, relu_last, y, own)) return rc;
+    p.x_stride = x_stride; p.x = x;
     return launch_mlp_wide(p, kWidePlain, static_cast<hipStream_t>(stream));
 }
 
@@ -630,13 +636,9 @@ extern "C" int pn2_sa_mlp_wide(int b, int n, int m, int nsample, int c, const fl
     if (b <= 0 || n <= 0 || m <= 0 || c <= 0) return PN2_EINVAL;
     if (!xyz || !new_xyz || !points || !idx || !y) return PN2_ENULL;
     if (nsample != 32 || c % 4 != 0 || (((uintptr_t)points | (uintptr_t)y) & 15)) return PN2_EUNSUP;
-    int rc = check_layers(nlayers, widths, w, bias);
-    if (rc != PN2_OK) return rc;
-    if ((long long)b * m * 32 + 64 > 0x7fffffffLL) return PN2_ERANGE;
     WideParams p = {};
-    p.rows = b * m * 32; p.cin = 3 + c; p.x_stride = 0; p.nlayers = nlayers; p.pool = pool ? 32 : 0; p.relu_last = 1;
-    p.n = n; p.m = m; p.c = c; p.xyz = xyz; p.new_xyz = new_xyz; p.points = points; p.idx = idx; p.y = y;
-    for (int l = 0; l < nlayers; ++l) { p.w[l] = widths[l]; p.W[l] = w[l]; p.bias[l] = bias[l]; }
+    if (int rc = fill_wide(p, (long long)b * m * 32, 3 + c, nlayers, widths, w, bias, pool ? 32 : 0, 1, y)) return rc;
+    p.n = n; p.m = m; p.c = c; p.xyz = xyz; p.new_xyz = new_xyz; p.points = points; p.idx = idx;
     return launch_mlp_wide(p, kWideGather, static_cast<hipStream_t>(stream));
 }
 
@@ -646,13 +648,9 @@ extern "C" int pn2_fp_mlp_wide(int b, int n, int m, int c1, int c2, const float*
     if (b <= 0 || n <= 0 || m < 3 || c2 <= 0 || c1 < 0) return PN2_EINVAL;
     if (!dist || !idx || !points2 || !y || (c1 > 0 && !points1)) return PN2_ENULL;
     if (n % 32 != 0 || c2 % 4 != 0 || c1 % 4 != 0 || (((uintptr_t)points2 | (uintptr_t)points1 | (uintptr_t)y) & 15)) return PN2_EUNSUP;
-    int rc = check_layers(nlayers, widths, w, bias);
-    if (rc != PN2_OK) return rc;
-    if ((long long)b * n + 64 > 0x7fffffffLL) return PN2_ERANGE;
     WideParams p = {};
-    p.rows = b * n; p.cin = c2 + c1; p.nlayers = nlayers; p.pool = 0; p.relu_last = 1;
-    p.n = n; p.m = m; p.c1 = c1; p.c2 = c2; p.dist = dist; p.idx = idx; p.points = points2; p.points1 = points1; p.y = y;
-    for (int l = 0; l < nlayers; ++l) { p.w[l] = widths[l]; p.W[l] = w[l]; p.bias[l] = bias[l]; }
+    if (int rc = fill_wide(p, (long long)b * n, c2 + c1, nlayers, widths, w, bias, 0, 1, y)) return rc;
+    p.n = n; p.m = m; p.c1 = c1; p.c2 = c2; p.dist = dist; p.idx = idx; p.points = points2; p.points1 = points1;
     return launch_mlp_wide(p, kWideInterp, static_cast<hipStream_t>(stream));
 }
 
@@ -665,13 +663,9 @@ extern "C" int pn2_fp_mlp_wide_pre(int b, int n, int m, int c1, const float* dis
     if (b <= 0 || n <= 0 || m < 3 || c1 <= 0) return PN2_EINVAL;
     if (!dist || !idx || !z || !y || !points1) return PN2_ENULL;
     if (n % 32 != 0 || c1 % 4 != 0 || (((uintptr_t)z | (uintptr_t)points1 | (uintptr_t)y) & 15)) return PN2_EUNSUP;
-    int rc = check_layers(nlayers, widths, w, bias);
-    if (rc != PN2_OK) return rc;
-    if ((long long)b * n + 64 > 0x7fffffffLL) return PN2_ERANGE;
     WideParams p = {};
-    p.rows = b * n; p.cin = c1; p.nlayers = nlayers; p.pool = 0; p.relu_last = 1;
-    p.n = n; p.m = m; p.c1 = c1; p.c2 = 0; p.dist = dist; p.idx = idx; p.points = nullptr; p.points1 = points1; p.y = y; p.zpre = z;
-    for (int l = 0; l < nlayers; ++l) { p.w[l] = widths[l]; p.W[l] = w[l]; p.bias[l] = bias[l]; }
+    if (int rc = fill_wide(p, (long long)b * n, c1, nlayers, widths, w, bias, 0, 1, y)) return rc;
+    p.n = n; p.m = m; p.c1 = c1; p.c2 = 0; p.dist = dist; p.idx = idx; p.points1 = points1; p.zpre = z;
     return launch_mlp_wide(p, kWideInterp, static_cast<hipStream_t>(stream));
 }
 
@@ -683,12 +677,8 @@ extern "C" int pn2_sa_mlp_wide_pre(int b, int n, int m, int nsample, const float
     if (b <= 0 || n <= 0 || m <= 0) return PN2_EINVAL;
     if (!xyz || !new_xyz || !zf || !idx || !y) return PN2_ENULL;
     if (nsample != 32 || (((uintptr_t)zf | (uintptr_t)y) & 15)) return PN2_EUNSUP;
-    int rc = check_layers(nlayers, widths, w, bias);
-    if (rc != PN2_OK) return rc;
-    if ((long long)b * m * 32 + 64 > 0x7fffffffLL) return PN2_ERANGE;
     WideParams p = {};
-    p.rows = b * m * 32; p.cin = 3; p.x_stride = 0; p.nlayers = nlayers; p.pool = pool ? 32 : 0; p.relu_last = 1;
-    p.n = n; p.m = m; p.c = 4; p.xyz = xyz; p.new_xyz = new_xyz; p.points = zf; p.idx = idx; p.y = y; p.zpre = zf;
-    for (int l = 0; l < nlayers; ++l) { p.w[l] = widths[l]; p.W[l] = w[l]; p.bias[l] = bias[l]; }
+    if (int rc = fill_wide(p, (long long)b * m * 32, 3, nlayers, widths, w, bias, pool ? 32 : 0, 1, y)) return rc;
+    p.n = n; p.m = m; p.c = 4; p.xyz = xyz; p.new_xyz = new_xyz; p.points = zf; p.idx = idx; p.zpre = zf;
     return launch_mlp_wide(p, kWideGather, static_cast<hipStream_t>(stream));
 }

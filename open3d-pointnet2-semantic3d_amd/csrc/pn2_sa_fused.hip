@@ -1,7 +1,7 @@
 // pn2_sa_fused.hip -- fused set-abstraction MLP for gfx950:
 //   gather(idx) -> [xyz - centre | features] -> up to 3 x (1x1 conv + bias + ReLU)
-//   -> max over the K=32 neighbours, with the grouped (B,M,K,C) tensor and all
-//   intermediate activations living only in VGPRs.
+//   -> max over the K neighbours (K = 32 is the native tile; 16, 64, 128 and 256 reuse it), with the grouped (B,M,K,C)
+//   tensor and all intermediate activations living only in VGPRs.
 // Replaces the TF sub-graph util/pointnet_util.py:43-54 (group/centre/concat) +
 // :150-162 (conv2d stack, util/tf_util.py:181-203 with inference BN folded by the
 // host) + :167-170 (reduce_max over K).  No reference kernel exists for it.
@@ -22,7 +22,15 @@
 //     half-wave exchange, and the pooled row is written as 128-byte segments.
 // Weights (<= 3 layers, widths <= 128) stay resident in LDS for the whole
 // persistent workgroup.
+//
+// Host side (the end of this file): pn2_sa_mlp_max_fused / _ld / pn2_sa_mlp_rows_fused, pn2_mlp_chain, pn2_fp_mlp_fused,
+// pn2_fp_mlp_fused_pre / _ld / _schedule and pn2_sa_mlp_fused_pre check their own arguments, read the layer stack through
+// pn2_read_layers (pn2_layer_stack.h: the width / NULL / alignment rule and the precedence of its refusals), pick the
+// instantiation by the layers' tile counts and hand over to launch_chain.  launch_chain refuses what does not fit LDS and
+// only then queues anything: for K > 32 the zero-fill of `out`, on the same stream right in front of the kernel -- a
+// refused call has not touched `out`.
 #include "pn2_common.h"
+#include "pn2_layer_stack.h"
 #include <atomic>
 #include <type_traits>
 #include <utility>
@@ -1085,6 +1093,12 @@ int launch_chain(const SaFusedParams& p_in, hipStream_t st) {
     if (L >= 3) floats += (size_t)W2 * W3 + W3;
     const size_t bytes = floats * sizeof(float) + 64;  // + the stagger flags
     if (bytes > 150 * 1024) return PN2_EUNSUP;
+    // from here on the call is accepted: every path below launches on st
+    if (POOL && !DENSE && !INTERP && p.kshift > 5) {  // K > 32: the tiles of one centre merge through atomicMax, start from +0
+        const size_t centres = (size_t)(((long long)p.groups * 32) >> p.kshift);
+        hipError_t e = hipMemsetAsync(p.out, 0, sizeof(float) * centres * (L == 1 ? W1 : L == 2 ? W2 : W3), st);
+        if (e != hipSuccess) return (int)e;
+    }
     const int need4 = (p.groups + 3) / 4;
     if constexpr (L == 1) {
         if (g_chain_nw == 16 && p.groups >= 4096) {  // one 16-wave workgroup per CU: 4 waves/SIMD share the MFMA pipe
@@ -1180,38 +1194,12 @@ extern "C" int pn2_set_sa_row_packing(int on) {
     return PN2_OK;
 }
 
-static int sa_fused_impl(int b, int n, int m, int nsample, int c, const float* xyz,
-                         const float* new_xyz, const float* points, const int* idx,
-                         int nlayers, const int* widths, const float* const* w,
-                         const float* const* bias, float* out, bool pool, void* stream, int ld_xyz, int ld_points);
-
-extern "C" int pn2_sa_mlp_max_fused(int b, int n, int m, int nsample, int c, const float* xyz,
-                                    const float* new_xyz, const float* points, const int* idx,
-                                    int nlayers, const int* widths, const float* const* w,
-                                    const float* const* bias, float* out, void* stream) {
-    return sa_fused_impl(b, n, m, nsample, c, xyz, new_xyz, points, idx, nlayers, widths, w, bias, out, true, stream, 3, c);
-}
-
-// pn2_sa_mlp_max_fused with the rows of xyz / points ld_xyz / ld_points floats apart (>= 3 / >= c): the xyz and rgb columns
-// of a (b,n,6) batch gathered in place (model.py:26-29 slices them out of the input tensor; here no copy is made).
-// ld_points != c needs the un-vectorised feature path (c % 8 != 0): PN2_EUNSUP otherwise.  Same bits as the dense call.
-extern "C" int pn2_sa_mlp_max_fused_ld(int b, int n, int m, int nsample, int c, const float* xyz, int ld_xyz,
-                                       const float* new_xyz, const float* points, int ld_points, const int* idx,
-                                       int nlayers, const int* widths, const float* const* w,
-                                       const float* const* bias, float* out, void* stream) {
-    return sa_fused_impl(b, n, m, nsample, c, xyz, new_xyz, points, idx, nlayers, widths, w, bias, out, true, stream, ld_xyz,
-                         c > 0 ? ld_points : 0);
-}
-
-// Same gather + MLP chain WITHOUT the max over the neighbours: out is (b, m, nsample, widths[last])
-// with ReLU applied -- the input of a wider following layer that runs on pn2_linear (+pool).  Used
-// when an SA stack starts with <= 128-wide layers and ends with a wider one ([128,128,256]).
-extern "C" int pn2_sa_mlp_rows_fused(int b, int n, int m, int nsample, int c, const float* xyz,
-                                     const float* new_xyz, const float* points, const int* idx,
-                                     int nlayers, const int* widths, const float* const* w,
-                                     const float* const* bias, float* out, void* stream) {
-    return sa_fused_impl(b, n, m, nsample, c, xyz, new_xyz, points, idx, nlayers, widths, w, bias, out, false, stream, 3, c);
-}
+// The layer stacks of the chain entry points (pn2_layer_stack.h holds the reader and the precedence of its refusals): widths
+// that stay resident in LDS, weights staged 16 bytes at a time, biases read float by float.  Every entry point below refuses
+// nlayers <= 0 (PN2_EINVAL) and NULL tables (PN2_ENULL) in its leading checks, ahead of its shape and range checks.
+constexpr Pn2LayerRule kChainLayers3 = {3, kPn2WidthsChain, kPn2AlignWeights, false};
+constexpr Pn2LayerRule kChainLayers2 = {2, kPn2WidthsChain, kPn2AlignWeights, false};
+constexpr Pn2LayerRule kChainLayersHoistedFp = {3, kPn2WidthsChain, kPn2AlignWeights, true};  // c1 == 0: no first-layer rows left
 
 static int sa_fused_impl(int b, int n, int m, int nsample, int c, const float* xyz,
                          const float* new_xyz, const float* points, const int* idx,
@@ -1232,23 +1220,13 @@ static int sa_fused_impl(int b, int n, int m, int nsample, int c, const float* x
     p.n = n; p.m = m; p.c = c; p.kshift = kshift;
     p.groups = (int)(((long long)b * m * nsample) / 32); p.rows = p.groups * 32;
     p.xyz = xyz; p.new_xyz = new_xyz; p.points = points; p.idx = idx; p.out = out;
-    int nt[3] = {0, 0, 0};
-    for (int l = 0; l < nlayers; ++l) {
-        if (widths[l] <= 0 || widths[l] % 32 != 0 || widths[l] > 128) return PN2_EUNSUP;
-        if (!w[l] || !bias[l]) return PN2_ENULL;
-        if ((uintptr_t)w[l] % 16 != 0) return PN2_EUNSUP;  // 16-byte weight staging
-        p.w[l] = widths[l]; p.W[l] = w[l]; p.bias[l] = bias[l];
-        nt[l] = widths[l] / 32;
-    }
+    int nt[3];
+    if (int rc = pn2_read_layers(p, kChainLayers3, nlayers, widths, w, bias, nt)) return rc;
     const bool vec8 = c > 0 && (c % 8 == 0) && ((uintptr_t)points % 16 == 0);
     if (ld_xyz < 3 || (c > 0 && ld_points < c)) return PN2_EINVAL;
     if (vec8 && ld_points != c) return PN2_EUNSUP;  // the 16-byte feature gathers read dense rows
     p.ldx = ld_xyz; p.ldp = ld_points;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (kshift > 5) {  // tiles of one centre merge through atomicMax: start from +0
-        hipError_t e = hipMemsetAsync(out, 0, sizeof(float) * (size_t)b * m * widths[nlayers - 1], st);
-        if (e != hipSuccess) return (int)e;
-    }
     const int key = nlayers * 1000 + nt[0] * 100 + nt[1] * 10 + nt[2];
     if (!pool) {
         // un-pooled variant: only the shapes the model needs ([*,128,128] prefixes)
@@ -1278,6 +1256,34 @@ static int sa_fused_impl(int b, int n, int m, int nsample, int c, const float* x
 #undef PN2_SA_CASE
 }
 
+extern "C" int pn2_sa_mlp_max_fused(int b, int n, int m, int nsample, int c, const float* xyz,
+                                    const float* new_xyz, const float* points, const int* idx,
+                                    int nlayers, const int* widths, const float* const* w,
+                                    const float* const* bias, float* out, void* stream) {
+    return sa_fused_impl(b, n, m, nsample, c, xyz, new_xyz, points, idx, nlayers, widths, w, bias, out, true, stream, 3, c);
+}
+
+// pn2_sa_mlp_max_fused with the rows of xyz / points ld_xyz / ld_points floats apart (>= 3 / >= c): the xyz and rgb columns
+// of a (b,n,6) batch gathered in place (model.py:26-29 slices them out of the input tensor; here no copy is made).
+// ld_points != c needs the un-vectorised feature path (c % 8 != 0): PN2_EUNSUP otherwise.  Same bits as the dense call.
+extern "C" int pn2_sa_mlp_max_fused_ld(int b, int n, int m, int nsample, int c, const float* xyz, int ld_xyz,
+                                       const float* new_xyz, const float* points, int ld_points, const int* idx,
+                                       int nlayers, const int* widths, const float* const* w,
+                                       const float* const* bias, float* out, void* stream) {
+    return sa_fused_impl(b, n, m, nsample, c, xyz, new_xyz, points, idx, nlayers, widths, w, bias, out, true, stream, ld_xyz,
+                         c > 0 ? ld_points : 0);
+}
+
+// Same gather + MLP chain WITHOUT the max over the neighbours: out is (b, m, nsample, widths[last])
+// with ReLU applied -- the input of a wider following layer that runs on pn2_linear (+pool).  Used
+// when an SA stack starts with <= 128-wide layers and ends with a wider one ([128,128,256]).
+extern "C" int pn2_sa_mlp_rows_fused(int b, int n, int m, int nsample, int c, const float* xyz,
+                                     const float* new_xyz, const float* points, const int* idx,
+                                     int nlayers, const int* widths, const float* const* w,
+                                     const float* const* bias, float* out, void* stream) {
+    return sa_fused_impl(b, n, m, nsample, c, xyz, new_xyz, points, idx, nlayers, widths, w, bias, out, false, stream, 3, c);
+}
+
 // Dense-row MLP chain (feature-propagation layers, pointnet_util.py:312-325 with inference BN
 // folded): y = relu(...relu(x @ W0 + b0)... @ W_{L-1} + b_{L-1}), optionally max-pooled over each
 // consecutive group of 32 rows.  Same kernel as the fused SA MLP with the gather switched off: the
@@ -1296,14 +1302,8 @@ extern "C" int pn2_mlp_chain(int rows, int cin, const float* x, int nlayers, con
     p.schedule = -1;
     p.c = cin; p.rows = rows; p.groups = (rows + 31) / 32;
     p.points = x; p.out = y;
-    int nt[2] = {0, 0};
-    for (int l = 0; l < nlayers; ++l) {
-        if (widths[l] <= 0 || widths[l] % 32 != 0 || widths[l] > 128) return PN2_EUNSUP;
-        if (!w[l] || !bias[l]) return PN2_ENULL;
-        if ((uintptr_t)w[l] % 16 != 0) return PN2_EUNSUP;  // 16-byte weight staging
-        p.w[l] = widths[l]; p.W[l] = w[l]; p.bias[l] = bias[l];
-        nt[l] = widths[l] / 32;
-    }
+    int nt[3];
+    if (int rc = pn2_read_layers(p, kChainLayers2, nlayers, widths, w, bias, nt)) return rc;
     const bool vec8 = (cin % 8 == 0) && ((uintptr_t)x % 16 == 0);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int key = nlayers * 100 + nt[0] * 10 + nt[1];
@@ -1342,14 +1342,8 @@ extern "C" int pn2_fp_mlp_fused(int b, int n, int m, int c1, int c2, const float
     p.schedule = -1;
     p.n = n; p.m = m; p.c = c2; p.c1 = c1; p.rows = b * n; p.groups = (b * n + 31) / 32;
     p.points = points2; p.points1 = points1; p.dist = dist; p.idx = idx; p.out = y;
-    int nt[2] = {0, 0};
-    for (int l = 0; l < nlayers; ++l) {
-        if (widths[l] <= 0 || widths[l] % 32 != 0 || widths[l] > 128) return PN2_EUNSUP;
-        if (!w[l] || !bias[l]) return PN2_ENULL;
-        if ((uintptr_t)w[l] % 16 != 0) return PN2_EUNSUP;
-        p.w[l] = widths[l]; p.W[l] = w[l]; p.bias[l] = bias[l];
-        nt[l] = widths[l] / 32;
-    }
+    int nt[3];
+    if (int rc = pn2_read_layers(p, kChainLayers2, nlayers, widths, w, bias, nt)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (nlayers * 100 + nt[0] * 10 + nt[1]) {
         case 244: return launch_chain<2, 4, 4, 1, true, true, false, true>(p, st);
@@ -1368,7 +1362,25 @@ extern "C" int pn2_fp_mlp_fused(int b, int n, int m, int c1, int c2, const float
 // rounding only (1e-7 of the activation scale; tests/test_layers_gpu.py holds both to the fp64 oracle at 1e-5).
 static int fp_mlp_fused_pre_impl(int b, int n, int m, int c1, const float* dist, const int* idx, const float* points1,
                                  const float* z, int nlayers, const int* widths, const float* const* w,
-                                 const float* const* bias, float* y, int schedule, void* stream, int ld_points1 = 0);
+                                 const float* const* bias, float* y, int schedule, void* stream, int ld_points1 = 0) {
+    if (ld_points1 != 0 && ld_points1 < c1) return PN2_EINVAL;
+    if (b <= 0 || n <= 0 || m <= 0 || c1 < 0 || nlayers <= 0) return PN2_EINVAL;
+    if (!dist || !idx || !z || !widths || !w || !bias || !y || (c1 > 0 && (!points1 || !w[0]))) return PN2_ENULL;
+    if ((long long)b * n > 0x7fffffffLL - 32) return PN2_ERANGE;
+    if (nlayers < 2 || nlayers > 3 || (uintptr_t)z % 16 != 0) return PN2_EUNSUP;
+    SaFusedParams p{};
+    p.schedule = schedule;
+    p.n = n; p.m = m; p.c = widths[0]; p.c1 = c1; p.rows = b * n; p.groups = (b * n + 31) / 32;
+    p.points = z; p.points1 = points1; p.dist = dist; p.idx = idx; p.out = y; p.ld1 = ld_points1;
+    int nt[3];  // (c1 > 0 with w[0] NULL was refused above)
+    if (int rc = pn2_read_layers(p, kChainLayersHoistedFp, nlayers, widths, w, bias, nt)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (nlayers * 1000 + nt[0] * 100 + nt[1] * 10 + nt[2]) {
+        case 3444: return launch_chain<3, 4, 4, 4, true, true, false, true, true>(p, st);  // FP4 of semantic.json: 131 -> 128 -> 128 -> 128
+        case 2440: return schedule == 1 ? PN2_EUNSUP : launch_chain<2, 4, 4, 1, true, true, false, true, true>(p, st);
+        default: return PN2_EUNSUP;
+    }
+}
 
 extern "C" int pn2_fp_mlp_fused_pre(int b, int n, int m, int c1, const float* dist, const int* idx, const float* points1,
                                     const float* z, int nlayers, const int* widths, const float* const* w,
@@ -1396,34 +1408,6 @@ extern "C" int pn2_fp_mlp_fused_pre_schedule(int b, int n, int m, int c1, const 
     return fp_mlp_fused_pre_impl(b, n, m, c1, dist, idx, points1, z, nlayers, widths, w, bias, y, schedule, stream);
 }
 
-static int fp_mlp_fused_pre_impl(int b, int n, int m, int c1, const float* dist, const int* idx, const float* points1,
-                                 const float* z, int nlayers, const int* widths, const float* const* w,
-                                 const float* const* bias, float* y, int schedule, void* stream, int ld_points1) {
-    if (ld_points1 != 0 && ld_points1 < c1) return PN2_EINVAL;
-    if (b <= 0 || n <= 0 || m <= 0 || c1 < 0 || nlayers <= 0) return PN2_EINVAL;
-    if (!dist || !idx || !z || !widths || !w || !bias || !y || (c1 > 0 && (!points1 || !w[0]))) return PN2_ENULL;
-    if ((long long)b * n > 0x7fffffffLL - 32) return PN2_ERANGE;
-    if (nlayers < 2 || nlayers > 3 || (uintptr_t)z % 16 != 0) return PN2_EUNSUP;
-    SaFusedParams p{};
-    p.schedule = schedule;
-    p.n = n; p.m = m; p.c = widths[0]; p.c1 = c1; p.rows = b * n; p.groups = (b * n + 31) / 32;
-    p.points = z; p.points1 = points1; p.dist = dist; p.idx = idx; p.out = y; p.ld1 = ld_points1;
-    int nt[3] = {0, 0, 0};
-    for (int l = 0; l < nlayers; ++l) {
-        if (widths[l] <= 0 || widths[l] % 32 != 0 || widths[l] > 128) return PN2_EUNSUP;
-        if (!bias[l] || (l > 0 && !w[l])) return PN2_ENULL;
-        if (w[l] && (uintptr_t)w[l] % 16 != 0) return PN2_EUNSUP;
-        p.w[l] = widths[l]; p.W[l] = w[l] ? w[l] : bias[l] /* never read: c1 == 0 */; p.bias[l] = bias[l];
-        nt[l] = widths[l] / 32;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (nlayers * 1000 + nt[0] * 100 + nt[1] * 10 + nt[2]) {
-        case 3444: return launch_chain<3, 4, 4, 4, true, true, false, true, true>(p, st);  // FP4 of semantic.json: 131 -> 128 -> 128 -> 128
-        case 2440: return schedule == 1 ? PN2_EUNSUP : launch_chain<2, 4, 4, 1, true, true, false, true, true>(p, st);
-        default: return PN2_EUNSUP;
-    }
-}
-
 // pn2_sa_mlp_max_fused / pn2_sa_mlp_rows_fused with the FEATURE part of the first layer hoisted by linearity:
 // zf = points @ W1[3:] (b*n rows, widths[0] wide: one per source point, computed by the caller with pn2_linear) replaces
 // `points`; w[0] = the 3 xyz rows of the folded first-layer weight (3 x widths[0]).  pool != 0: max over the K neighbours
@@ -1440,14 +1424,8 @@ extern "C" int pn2_sa_mlp_fused_pre(int b, int n, int m, int nsample, const floa
     p.n = n; p.m = m; p.c = widths[0]; p.kshift = 5;
     p.groups = (int)(((long long)b * m * nsample) / 32); p.rows = p.groups * 32;
     p.xyz = xyz; p.new_xyz = new_xyz; p.points = zf; p.idx = idx; p.out = out;
-    int nt[3] = {0, 0, 0};
-    for (int l = 0; l < nlayers; ++l) {
-        if (widths[l] <= 0 || widths[l] % 32 != 0 || widths[l] > 128) return PN2_EUNSUP;
-        if (!w[l] || !bias[l]) return PN2_ENULL;
-        if ((uintptr_t)w[l] % 16 != 0) return PN2_EUNSUP;
-        p.w[l] = widths[l]; p.W[l] = w[l]; p.bias[l] = bias[l];
-        nt[l] = widths[l] / 32;
-    }
+    int nt[3];
+    if (int rc = pn2_read_layers(p, kChainLayers3, nlayers, widths, w, bias, nt)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int key = nlayers * 1000 + nt[0] * 100 + nt[1] * 10 + nt[2];
     if (pool) {

@@ -18,7 +18,10 @@
 // of A and B elements matters, so no assumption is made about which k a (half, j) slot "really" is.
 // The last layer is computed un-transposed so the K-max is in-lane + one half-wave exchange.  Every weight
 // fragment read from LDS (16 B per lane) feeds the MFMAs of all RT row tiles.
+// Host side: pn2_sa_mlp_max_fused_bf16 reads its layer stack through pn2_read_layers (pn2_layer_stack.h; no alignment is
+// asked of the fp32 weights, they are staged float by float) and picks the instantiation by tile counts and K (32 / 64).
 #include "pn2_common.h"
+#include "pn2_layer_stack.h"
 
 namespace {
 
@@ -293,13 +296,10 @@ extern "C" int pn2_sa_mlp_max_fused_bf16(int b, int n, int m, int nsample, int c
     SaBf16Params p{};
     p.n = n; p.m = m; p.c = c; p.groups = b * m; p.nsample = nsample;
     p.xyz = xyz; p.new_xyz = new_xyz; p.points = static_cast<const __bf16*>(points_bf16); p.idx = idx; p.out = out;
-    int nt[3] = {0, 0, 0};
-    for (int l = 0; l < nlayers; ++l) {
-        if (widths[l] <= 0 || widths[l] % 32 != 0 || widths[l] > 128) return PN2_EUNSUP;
-        if (!w[l] || !bias[l]) return PN2_ENULL;
-        p.w[l] = widths[l]; p.W[l] = w[l]; p.bias[l] = bias[l];
-        nt[l] = widths[l] / 32;
-    }
+    // the layer stack (pn2_layer_stack.h): weights are staged float by float while they are rounded to bf16, no alignment asked
+    constexpr Pn2LayerRule kBf16Layers = {3, kPn2WidthsChain, kPn2AlignNone, false};
+    int nt[3];
+    if (int rc = pn2_read_layers(p, kBf16Layers, nlayers, widths, w, bias, nt)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int key = nlayers * 1000 + nt[0] * 100 + nt[1] * 10 + nt[2];
 #define PN2_BF_CASE(L_, A_, B_, C_)                                                              \

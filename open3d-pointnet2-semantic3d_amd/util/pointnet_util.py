@@ -22,6 +22,23 @@ from ..tf_ops.tf_interpolate import three_interpolate, three_nn
 from ..tf_ops.tf_sampling import (farthest_point_sample, farthest_point_sample_and_gather, farthest_point_sample_with_ties,
                                   gather_point, tag_fps_output)
 
+# ---- A/B and parity switches of this module (tests, bench.py and tools/ set them; every default is the fast path) -----------------
+# set False to force the unfused HIP path (group_concat + pn2_linear); used by tests/bench
+USE_FUSED_SA = True
+USE_HOISTED_SA = True  # A/B: feature part of the first SA layer computed on the source points (linearity)
+# A/B and parity switch: the pooled K = 32 SA kernels skip the rows the ball query padded (csrc/pn2_sa_fused.hip, PACK).  Same
+# bits either way.  The library's switch is process-wide and on by default: it is told only when this flag differs from what it
+# was last told.  A captured graph keeps the choice it was captured with.
+USE_SA_ROW_PACKING = True
+_sa_row_packing_told = True
+USE_HOISTED_FP = True  # A/B: first FP layer's product with the interpolated channels computed on the known points (linearity)
+USE_FUSED_TRAIN_FRONT = True  # set False: the training path's SA / FP front ends as separate ops (tests / A-B)
+USE_MLP_CHAIN = True  # set False to force one pn2_linear launch per layer (tests/bench)
+USE_MLP_WIDE = True   # set False: coarse-level MLPs as one pn2_linear launch per layer (tests / A-B)
+WIDE_MIN_ROWS = 4096  # FP2 (128 tiles) still wins with its front end fused in (28 us vs 8 + 25); FP1 (1024 rows = 32 tiles) does not
+USE_FUSED_FP = True    # set False to force pn2_fp_interp_concat + separate MLP launches (tests/bench)
+_WIDE_WIDTHS = (128, 256, 512)  # what the pn2_*_mlp_wide entry points take
+
 
 def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=True, geometry=None):
     """-> new_xyz (B,npoint,3), new_points (B,npoint,nsample,3+C), idx, grouped_xyz.
@@ -99,11 +116,8 @@ def _sa_fused_inference(xyz, new_xyz, points, idx, mlp, bn, conv_scope_fmt, pool
         ws.append(w2)
         bs.append(b2)
         cin = cout
-    L = len(mlp)
     _sync_sa_row_packing(xyz)
-    widths, bptrs = int_array(mlp), ptr_table(bs)
     oshape = (b, m, mlp[-1]) if pool else (b, m, nsample, mlp[-1])
-    out = torch.empty(oshape, dtype=torch.float32, device=xyz.device)
     if (USE_HOISTED_SA and not bf16 and nsample == 32 and c >= 32 and c % 4 == 0
             and ((pool and tuple(mlp) in ((64, 64, 128), (128, 128, 128))) or (not pool and tuple(mlp) == (128, 128)))):
         # feature part of the first layer hoisted by linearity: zf = points @ W1[3:] on the n source points (8x fewer rows
@@ -111,23 +125,21 @@ def _sa_fused_inference(xyz, new_xyz, points, idx, mlp, bn, conv_scope_fmt, pool
         w1x, w1f = tf_util.split_first_layer(ws[0], 3, c, "sa_pre")   # rows [0,3) = xyz, [3, 3+c) = features
         xyz, points = xyz.contiguous(), points.contiguous()
         zf = tf_util.hoist_gemm(points.reshape(b * n, c), w1f)
-        if launch("pn2_sa_mlp_fused_pre", xyz, b, n, m, nsample, ptr(xyz), ptr(new_xyz), ptr(zf), ptr(idx), L, widths,
-                  ptr_table([w1x] + ws[1:]), bptrs, int(bool(pool)), ptr(out), may_refuse=True):
+        out = tf_util._launch_stack("pn2_sa_mlp_fused_pre", xyz, (b, n, m, nsample, xyz, new_xyz, zf, idx), ws, bs,
+                                    (int(bool(pool)),), oshape, w0=w1x)
+        if out is not None:
             return out
-    wptrs = ptr_table(ws)
     xyz_v, ldx = rows_in_place(xyz)
     pts, ldp = (None, 0) if points is None else rows_in_place(points)
     if pool and not bf16 and (ldx != 3 or (points is not None and ldp != c)):
         # column blocks of a wider batch (model.get_sa_fp_features: the xyz / rgb halves of point_cloud (b,n,6)) gathered in place
-        if launch("pn2_sa_mlp_max_fused_ld", xyz, b, n, m, nsample, c, ptr(xyz_v), ldx, ptr(new_xyz), ptr(pts), ldp, ptr(idx), L,
-                  widths, wptrs, bptrs, ptr(out), may_refuse=True):
+        out = tf_util._launch_stack("pn2_sa_mlp_max_fused_ld", xyz, (b, n, m, nsample, c, xyz_v, ldx, new_xyz, pts, ldp, idx), ws, bs,
+                                    (), oshape)
+        if out is not None:
             return out
-    xyz_v = xyz_v.contiguous()
-    pts = None if pts is None else pts.contiguous()
     name = "pn2_sa_mlp_max_fused_bf16" if bf16 else ("pn2_sa_mlp_max_fused" if pool else "pn2_sa_mlp_rows_fused")
-    ok = launch(name, xyz, b, n, m, nsample, c, ptr(xyz_v), ptr(new_xyz), ptr(pts), ptr(idx), L, widths, wptrs, bptrs, ptr(out),
-                may_refuse=True)
-    return out if ok else None
+    pts = None if pts is None else pts.contiguous()
+    return tf_util._launch_stack(name, xyz, (b, n, m, nsample, c, xyz_v.contiguous(), new_xyz, pts, idx), ws, bs, (), oshape)
 
 
 def _sa_group_concat(xyz, new_xyz, points, idx):
@@ -260,18 +272,6 @@ class _FPInterpConcat(torch.autograd.Function):
         return None, None, g1, g2, None
 
 
-# set False to force the unfused HIP path (group_concat + pn2_linear); used by tests/bench
-USE_FUSED_SA = True
-
-
-USE_HOISTED_SA = True  # A/B: feature part of the first SA layer computed on the source points (linearity)
-# A/B and parity switch: the pooled K = 32 SA kernels skip the rows the ball query padded (csrc/pn2_sa_fused.hip, PACK).  Same
-# bits either way.  The library's switch is process-wide and on by default: it is told only when this flag differs from what it
-# was last told.  A captured graph keeps the choice it was captured with.
-USE_SA_ROW_PACKING = True
-_sa_row_packing_told = True
-
-
 def _sync_sa_row_packing(where):
     global _sa_row_packing_told
     want = bool(USE_SA_ROW_PACKING)
@@ -280,7 +280,6 @@ def _sync_sa_row_packing(where):
         _sa_row_packing_told = want
 
 
-USE_HOISTED_FP = True  # A/B: first FP layer's product with the interpolated channels computed on the known points (linearity)
 def sa_geometry(xyz, npoint, radius, nsample):
     """The feature-independent half of an SA layer: FPS -> gather -> ball query.
     -> new_xyz (B,npoint,3), idx (B,npoint,nsample).  Depends only on coordinates, so a model can
@@ -352,58 +351,118 @@ def coarse_geometry(xyz0, npoints, radii, nsamples, want_nn=True, fps_arith_mode
     return out
 
 
+def _first_taken(routes, *args):
+    """the result of the first route of an ordered tuple that takes the configuration (the last one of each tuple takes all)"""
+    for route in routes:
+        got = route(*args)
+        if got is not None:
+            return got
+    raise AssertionError("unreachable: the last route takes every configuration")
+
+
+class _SaCall:
+    """what the routes of sa_features_inference read: the module's inputs as they were given (xyz / points may be column blocks
+    of a wider batch, points may be bfloat16) until _sa_step_dense_float32 has run"""
+
+    def __init__(self, xyz, new_xyz, points, idx, mlp, bn, bn_decay):
+        self.xyz, self.new_xyz, self.points, self.idx = xyz, new_xyz, points, idx
+        self.mlp, self.bn, self.bn_decay, self.nsample = mlp, bn, bn_decay, idx.shape[2]
+        self.was_bf16 = False
+
+
+# A route of sa_features_inference holds its whole predicate and its launch, is named for the entry point it reaches and returns
+# the module's (B, npoint, mlp[-1]) features, or None: not its configuration, or the library refused.  SA_ROUTES is the order.
+def _sa_route_mlp_max_fused(a):
+    """pn2_sa_mlp_max_fused (_ld: column blocks in place; _bf16: bf16 features; pn2_sa_mlp_fused_pre: first layer hoisted)"""
+    if not USE_FUSED_SA:
+        return None
+    return _sa_fused_inference(a.xyz, a.new_xyz, a.points, a.idx, a.mlp, a.bn, "conv%d")
+
+
+def _sa_step_dense_float32(a):
+    """not a kernel: every route below reads dense rows (the fused kernel above takes column blocks in place), and float32"""
+    a.xyz = a.xyz.contiguous()
+    a.points = None if a.points is None else a.points.contiguous()
+    if a.points is not None and a.points.dtype == torch.bfloat16:
+        a.points, a.was_bf16 = a.points.float(), True  # configuration outside the bf16 kernel: the fp32 kernels on the exact values
+    return None
+
+
+def _sa_route_mlp_max_fused_float32(a):
+    """pn2_sa_mlp_max_fused on bf16 features the bf16 kernel did not take"""
+    return _sa_route_mlp_max_fused(a) if a.was_bf16 else None
+
+
+def _sa_route_mlp_rows_fused(a):
+    """[128,128,wide]: gather + first two layers fused (pn2_sa_mlp_rows_fused / pn2_sa_mlp_fused_pre: activations stay in
+    registers), the wide last layer + max over K on pn2_linear"""
+    mlp = a.mlp
+    if not (USE_FUSED_SA and len(mlp) == 3 and mlp[0] == mlp[1] == 128 and mlp[2] % 32 == 0):
+        return None
+    h = _sa_fused_inference(a.xyz, a.new_xyz, a.points, a.idx, mlp[:2], a.bn, "conv%d", pool=False)
+    if h is None:
+        return None
+    h = tf_util.conv2d(h, mlp[2], [1, 1], padding="VALID", stride=[1, 1], bn=a.bn, is_training=False,
+                       scope="conv2", bn_decay=a.bn_decay, pool=a.nsample)
+    return h.squeeze(2)
+
+
+def _sa_wide_layers(a):
+    """-> (ws, bs) of an all-wide stack (SA4) for pn2_sa_mlp_wide*: gather + centre + concat + the whole MLP + max over K in one
+    launch; None when the stack is not one"""
+    mlp, points = a.mlp, a.points
+    if not (USE_MLP_WIDE and USE_FUSED_SA and a.nsample == 32 and points is not None
+            and points.dtype == torch.float32 and points.shape[2] % 4 == 0 and 1 <= len(mlp) <= 3
+            and all(w in _WIDE_WIDTHS for w in mlp) and a.idx.shape[0] * a.idx.shape[1] * 32 >= WIDE_MIN_ROWS):
+        return None
+    folded, cprev = [], 3 + points.shape[2]
+    for i, cout in enumerate(mlp):
+        with tf_util.variable_scope("conv%d" % i):
+            if i == 0:  # the kernel's first-layer row order: [features | xyz | zero pad to a multiple of 8]
+                folded.append(tf_util.folded_dense(cprev, cout, a.bn, (1, 1, cprev, cout), pad_to=32,
+                                                   pad_in=-(-cprev // 8) * 8, rotate_rows=cprev - 3))
+            else:
+                folded.append(tf_util.folded_dense(cprev, cout, a.bn, (1, 1, cprev, cout), pad_to=32))
+        cprev = cout
+    _sync_sa_row_packing(a.xyz)  # the pooled wide kernel packs rows too (csrc/pn2_mlp_wide.hip, PACK)
+    return [f[0] for f in folded], [f[1] for f in folded]
+
+
+def _sa_route_mlp_wide_pre(a):
+    """pn2_sa_mlp_wide_pre: the all-wide stack with the feature part of its first layer hoisted"""
+    layers = _sa_wide_layers(a) if USE_HOISTED_SA else None
+    return None if layers is None else tf_util.hip_sa_mlp_wide_pre(a.xyz, a.new_xyz, a.points, a.idx, *layers)
+
+
+def _sa_route_mlp_wide(a):
+    """pn2_sa_mlp_wide"""
+    layers = _sa_wide_layers(a)
+    return None if layers is None else tf_util.hip_sa_mlp_wide(a.xyz, a.new_xyz, a.points, a.idx, *layers)
+
+
+def _sa_route_group_concat(a):
+    """pn2_sa_group_concat + one pn2_linear per layer: takes everything"""
+    h = _sa_group_concat(a.xyz, a.new_xyz, a.points, a.idx)  # (B,M,K,3+C)
+    pool_ok = a.nsample == 16 or a.nsample % 32 == 0
+    for i, cout in enumerate(a.mlp):
+        last = i == len(a.mlp) - 1
+        h = tf_util.conv2d(h, cout, [1, 1], padding="VALID", stride=[1, 1], bn=a.bn, is_training=False,
+                           scope="conv%d" % i, bn_decay=a.bn_decay, pool=a.nsample if (last and pool_ok) else 0)
+    if not pool_ok:
+        h = h.amax(dim=2, keepdim=True)
+    return h.squeeze(2)
+
+
+SA_ROUTES = (_sa_route_mlp_max_fused, _sa_step_dense_float32, _sa_route_mlp_max_fused_float32, _sa_route_mlp_rows_fused,
+             _sa_route_mlp_wide_pre, _sa_route_mlp_wide, _sa_route_group_concat)
+
+
 def sa_features_inference(xyz, new_xyz, points, idx, mlp, bn=True, bn_decay=None):
     """The feature half of an SA layer (inference, max pooling): gather + MLP + max over K,
-    fused when the widths allow it.  Must be called inside the layer's variable scope.
+    fused when the widths allow it: the first of SA_ROUTES that takes the configuration.  Must be called inside the layer's
+    variable scope.
     -> (B,npoint,mlp[-1])"""
-    nsample = idx.shape[2]
-    new_points = None
-    if USE_FUSED_SA:
-        new_points = _sa_fused_inference(xyz, new_xyz, points, idx, mlp, bn, "conv%d")
-    if new_points is None:  # every other kernel reads dense rows (the fused kernel above takes column blocks in place)
-        xyz = xyz.contiguous()
-        points = None if points is None else points.contiguous()
-    if new_points is None and points is not None and points.dtype == torch.bfloat16:
-        points = points.float()  # configuration outside the bf16 kernel: run the fp32 kernels on the exact values
-        if USE_FUSED_SA:
-            new_points = _sa_fused_inference(xyz, new_xyz, points, idx, mlp, bn, "conv%d")
-    if new_points is None and USE_FUSED_SA and len(mlp) == 3 and mlp[0] == mlp[1] == 128 and mlp[2] % 32 == 0:
-        # [128,128,wide]: gather + first two layers fused (activations stay in registers), the wide
-        # last layer + max over K on pn2_linear
-        h = _sa_fused_inference(xyz, new_xyz, points, idx, mlp[:2], bn, "conv%d", pool=False)
-        if h is not None:
-            h = tf_util.conv2d(h, mlp[2], [1, 1], padding="VALID", stride=[1, 1], bn=bn, is_training=False,
-                               scope="conv2", bn_decay=bn_decay, pool=nsample)
-            new_points = h.squeeze(2)
-    if (new_points is None and USE_MLP_WIDE and USE_FUSED_SA and nsample == 32 and points is not None
-            and points.dtype == torch.float32 and points.shape[2] % 4 == 0 and 1 <= len(mlp) <= 3
-            and all(w in (128, 256, 512) for w in mlp) and idx.shape[0] * idx.shape[1] * 32 >= WIDE_MIN_ROWS):
-        # all layers wide (SA4): gather + centre + concat + the whole MLP + max over K in one launch
-        folded, cprev = [], 3 + points.shape[2]
-        for i, cout in enumerate(mlp):
-            with tf_util.variable_scope("conv%d" % i):
-                if i == 0:  # the kernel's first-layer row order: [features | xyz | zero pad to a multiple of 8]
-                    folded.append(tf_util.folded_dense(cprev, cout, bn, (1, 1, cprev, cout), pad_to=32,
-                                                       pad_in=-(-cprev // 8) * 8, rotate_rows=cprev - 3))
-                else:
-                    folded.append(tf_util.folded_dense(cprev, cout, bn, (1, 1, cprev, cout), pad_to=32))
-            cprev = cout
-        _sync_sa_row_packing(xyz)  # the pooled wide kernel packs rows too (csrc/pn2_mlp_wide.hip, PACK)
-        if USE_HOISTED_SA:
-            new_points = tf_util.hip_sa_mlp_wide_pre(xyz, new_xyz, points, idx, [f[0] for f in folded], [f[1] for f in folded])
-        if new_points is None:
-            new_points = tf_util.hip_sa_mlp_wide(xyz, new_xyz, points, idx, [f[0] for f in folded], [f[1] for f in folded])
-    if new_points is None:
-        h = _sa_group_concat(xyz, new_xyz, points, idx)  # (B,M,K,3+C)
-        pool_ok = nsample == 16 or nsample % 32 == 0
-        for i, cout in enumerate(mlp):
-            last = i == len(mlp) - 1
-            h = tf_util.conv2d(h, cout, [1, 1], padding="VALID", stride=[1, 1], bn=bn, is_training=False,
-                               scope="conv%d" % i, bn_decay=bn_decay, pool=nsample if (last and pool_ok) else 0)
-        if not pool_ok:
-            h = h.amax(dim=2, keepdim=True)
-        new_points = h.squeeze(2)
-    return new_points
+    return _first_taken(SA_ROUTES, _SaCall(xyz, new_xyz, points, idx, mlp, bn, bn_decay))
 
 
 _POOL_MODES = {"max": 0, "avg": 1, "weighted_avg": 2, "max_and_avg": 3}
@@ -642,31 +701,142 @@ def _fp_interp_concat(dist, idx, points1, points2, pad_to=1):
     return out
 
 
-USE_FUSED_TRAIN_FRONT = True  # set False: the training path's SA / FP front ends as separate ops (tests / A-B)
+class _DenseStack:
+    """what the routes of dense_mlp_inference read: the layer widths, their folded (weight, bias) pairs, and for the FP front
+    end its inputs and the row count"""
+
+    def __init__(self, mlp, folded, rows, fp_front):
+        self.mlp, self.folded, self.rows = mlp, folded, rows
+        if fp_front is not None:
+            self.dist, self.idx, self.points1, self.points2, self.pad_to = fp_front
+
+    def layers(self, i, take):
+        """-> (ws, bs) of layers i .. i + take - 1"""
+        part = self.folded[i:i + take]
+        return [f[0] for f in part], [f[1] for f in part]
+
+    def front(self):
+        return self.dist, self.idx, self.points1, self.points2
 
 
-USE_MLP_CHAIN = True  # set False to force one pn2_linear launch per layer (tests/bench)
+def _chain_widths(widths):
+    return all(w <= 128 and w % 32 == 0 for w in widths)
 
 
-USE_MLP_WIDE = True   # set False: coarse-level MLPs as one pn2_linear launch per layer (tests / A-B)
-WIDE_MIN_ROWS = 4096  # FP2 (128 tiles) still wins with its front end fused in (28 us vs 8 + 25); FP1 (1024 rows = 32 tiles) does not
+def _wide_widths(widths):
+    return all(w in _WIDE_WIDTHS for w in widths)
 
 
-USE_FUSED_FP = True    # set False to force pn2_fp_interp_concat + separate MLP launches (tests/bench)
+# A route holds its whole predicate and its launch, is named for the entry point it reaches and returns (rows after its layers,
+# number of layers it consumed), or None: not its configuration, or the library refused.  FP_FRONT_ROUTES produce the first rows
+# from the FP front end (s.rows of them); DENSE_TAIL_ROUTES(s, h, i) run layers i.. on the rows h.  The tuples are the order.
+# 65536 rows: the LDS-resident chains pay off from there on (enough 32-row tiles to fill the chip) and the wide kernels take up
+# to there, so exactly 65536 rows satisfy both and the order decides.
+def _fp_route_mlp_fused_pre(s):
+    """pn2_fp_mlp_fused_pre: first layer hoisted by linearity (interp(points2) @ W == interp(points2 @ W)): points2 @ W1a on the
+    m known rows, then front end + up to three LDS-resident layers in one kernel"""
+    mlp = s.mlp
+    if not (USE_FUSED_FP and USE_MLP_CHAIN and USE_HOISTED_FP and s.rows >= 65536 and len(mlp) >= 2
+            and _chain_widths(mlp[:3])):
+        return None
+    take = min(3, len(mlp))
+    y = tf_util.hip_fp_mlp_fused_pre(*s.front(), *s.layers(0, take))
+    return None if y is None else (y, take)
+
+
+def _fp_step_dense_points1(s):
+    """not a kernel: only the hoisted chain above reads a column block in place"""
+    if s.points1 is not None:
+        s.points1 = s.points1.contiguous()
+    return None
+
+
+def _fp_route_mlp_fused(take):
+    def route(s):
+        """pn2_fp_mlp_fused: front end + `take` LDS-resident layers"""
+        mlp = s.mlp
+        if not (USE_FUSED_FP and USE_MLP_CHAIN and s.rows >= 65536 and s.points2.shape[2] % 8 == 0
+                and take <= len(mlp) and _chain_widths(mlp[:1]) and _chain_widths(mlp[:take])):
+            return None
+        y = tf_util.hip_fp_mlp_fused(*s.front(), *s.layers(0, take))
+        return None if y is None else (y, take)
+    return route
+
+
+def _fp_wide(s, entry):
+    """coarse FP levels: front end + the whole MLP (up to three layers) in one launch"""
+    mlp = s.mlp
+    if not (USE_FUSED_FP and USE_MLP_WIDE and WIDE_MIN_ROWS <= s.rows <= 65536 and s.dist.shape[1] % 32 == 0
+            and s.points2.shape[2] % 4 == 0 and (s.points1 is None or s.points1.shape[2] % 4 == 0) and _wide_widths(mlp[:3])):
+        return None
+    take = min(3, len(mlp))
+    y = entry(*s.front(), *s.layers(0, take))
+    return None if y is None else (y, take)
+
+
+def _fp_route_mlp_wide_pre(s):
+    """pn2_fp_mlp_wide_pre: pn2_fp_mlp_wide with the first layer hoisted; needs a skip link"""
+    return _fp_wide(s, tf_util.hip_fp_mlp_wide_pre) if USE_HOISTED_FP and s.points1 is not None else None
+
+
+def _fp_route_mlp_wide(s):
+    """pn2_fp_mlp_wide"""
+    return _fp_wide(s, tf_util.hip_fp_mlp_wide)
+
+
+def _fp_route_interp_concat(s):
+    """pn2_fp_interp_concat: the front end materialised, no layer consumed; takes everything"""
+    x = _fp_interp_concat(s.dist, s.idx, s.points1, s.points2, pad_to=s.pad_to)
+    return x.reshape(s.rows, x.shape[2]), 0
+
+
+def _tail_route_mlp_wide(s, h, i):
+    """pn2_mlp_wide: coarse levels (4096 .. 65536 rows, widths 128 / 256 / 512), up to three remaining layers in one launch"""
+    mlp = s.mlp
+    if not (USE_MLP_WIDE and WIDE_MIN_ROWS <= h.shape[0] <= 65536 and _wide_widths(mlp[i:i + 3])):
+        return None
+    take = min(3, len(mlp) - i)
+    y = tf_util.hip_mlp_wide(h, *s.layers(i, take))
+    return None if y is None else (y, take)
+
+
+def _tail_route_mlp_chain(take):
+    def route(s, h, i):
+        """pn2_mlp_chain: `take` LDS-resident layers"""
+        mlp = s.mlp
+        if not (USE_MLP_CHAIN and h.shape[0] >= 65536 and _chain_widths(mlp[i:i + 2])
+                and i + take <= len(mlp) and _chain_widths(mlp[i:i + take])):
+            return None
+        y = tf_util.hip_mlp_chain(h, *s.layers(i, take))
+        return None if y is None else (y, take)
+    return route
+
+
+def _tail_route_linear(s, h, i):
+    """pn2_linear: one layer; takes everything"""
+    w2, b2 = s.folded[i]
+    h = tf_util.hip_linear(h, w2, b2, relu=True)
+    if h.shape[1] != s.mlp[i]:
+        h = h[:, :s.mlp[i]].contiguous()
+    return h, 1
+
+
+FP_FRONT_ROUTES = (_fp_route_mlp_fused_pre, _fp_step_dense_points1, _fp_route_mlp_fused(2), _fp_route_mlp_fused(1),
+                   _fp_route_mlp_wide_pre, _fp_route_mlp_wide, _fp_route_interp_concat)
+DENSE_TAIL_ROUTES = (_tail_route_mlp_wide, _tail_route_mlp_chain(2), _tail_route_mlp_chain(1), _tail_route_linear)
 
 
 def dense_mlp_inference(x2d, cin, mlp, scope_fmt, bn=True, fp_front=None):
     """Run a stack of 1x1-conv layers on (rows, cin_padded) rows.  Consecutive layers whose widths are
-    <= 128 run as LDS-resident chains (pn2_mlp_chain, up to 2 layers per launch); anything else runs
-    one pn2_linear per layer.  `cin` is the true input width (x2d may carry zero pad columns).
+    <= 128 run as LDS-resident chains (pn2_mlp_chain, up to 2 layers per launch), wide ones on pn2_mlp_wide, anything else
+    runs one pn2_linear per layer: DENSE_TAIL_ROUTES, in order.  `cin` is the true input width (x2d may carry zero pad columns).
     fp_front = (dist, idx, points1, points2, pad_to): the rows are the FP front end; when the first layers
-    qualify they are produced inside the first chain kernel (pn2_fp_mlp_fused) and x2d may be None,
+    qualify they are produced inside the first kernel (FP_FRONT_ROUTES, in order) and x2d may be None,
     otherwise they are materialised with pn2_fp_interp_concat.
     Must be called inside the module's variable scope."""
     if x2d is None:
-        dist, idx, points1, points2, pad_to = fp_front
-        rows = dist.shape[0] * dist.shape[1]
-        cw = -(-cin // pad_to) * pad_to
+        rows = fp_front[0].shape[0] * fp_front[0].shape[1]
+        cw = -(-cin // fp_front[4]) * fp_front[4]
     else:
         rows, cw = x2d.shape
     folded = []
@@ -676,71 +846,11 @@ def dense_mlp_inference(x2d, cin, mlp, scope_fmt, bn=True, fp_front=None):
             pad_in = cw if i == 0 else None
             folded.append(tf_util.folded_dense(c, cout, bn, (1, 1, c, cout), pad_to=32, pad_in=pad_in))
         c = cout
-    i, h = 0, x2d
-    if h is None:
-        if (USE_FUSED_FP and USE_MLP_CHAIN and USE_HOISTED_FP and rows >= 65536 and len(mlp) >= 2
-                and all(w <= 128 and w % 32 == 0 for w in mlp[:3])):
-            # first layer hoisted by linearity (interp(points2) @ W == interp(points2 @ W)): points2 @ W1a on the m known
-            # rows, then front end + up to three LDS-resident layers in one kernel
-            take = min(3, len(mlp))
-            y = tf_util.hip_fp_mlp_fused_pre(dist, idx, points1, points2, [folded[k][0] for k in range(take)],
-                                             [folded[k][1] for k in range(take)])
-            if y is not None:
-                h, i = y, take
-        if h is None and points1 is not None:
-            points1 = points1.contiguous()  # (only the hoisted chain above reads a column block in place)
-        if (h is None and USE_FUSED_FP and USE_MLP_CHAIN and rows >= 65536 and points2.shape[2] % 8 == 0
-                and mlp[0] <= 128 and mlp[0] % 32 == 0):
-            for take in (2, 1):
-                if take > len(mlp) or any(w > 128 or w % 32 for w in mlp[:take]):
-                    continue
-                y = tf_util.hip_fp_mlp_fused(dist, idx, points1, points2, [folded[k][0] for k in range(take)],
-                                             [folded[k][1] for k in range(take)])
-                if y is not None:
-                    h, i = y, take
-                    break
-        if (h is None and USE_FUSED_FP and USE_MLP_WIDE and WIDE_MIN_ROWS <= rows <= 65536 and dist.shape[1] % 32 == 0
-                and points2.shape[2] % 4 == 0 and (points1 is None or points1.shape[2] % 4 == 0)
-                and all(w in (128, 256, 512) for w in mlp[:3])):
-            # coarse FP levels: front end + the whole MLP in one launch (pn2_fp_mlp_wide)
-            take = min(3, len(mlp))
-            y = None
-            if USE_HOISTED_FP and points1 is not None:
-                y = tf_util.hip_fp_mlp_wide_pre(dist, idx, points1, points2, [folded[k][0] for k in range(take)],
-                                                [folded[k][1] for k in range(take)])
-            if y is None:
-                y = tf_util.hip_fp_mlp_wide(dist, idx, points1, points2, [folded[k][0] for k in range(take)],
-                                            [folded[k][1] for k in range(take)])
-            if y is not None:
-                h, i = y, take
-        if h is None:
-            x = _fp_interp_concat(dist, idx, points1, points2, pad_to=pad_to)
-            h = x.reshape(rows, x.shape[2])
+    stack = _DenseStack(mlp, folded, rows, fp_front if x2d is None else None)
+    h, i = (x2d, 0) if x2d is not None else _first_taken(FP_FRONT_ROUTES, stack)
     while i < len(mlp):
-        done = False
-        # coarse levels (4096 .. 32768 rows, widths 128 / 256 / 512): the remaining layers in one launch (pn2_mlp_wide)
-        if USE_MLP_WIDE and WIDE_MIN_ROWS <= h.shape[0] <= 65536 and all(w in (128, 256, 512) for w in mlp[i:i + 3]):
-            take = min(3, len(mlp) - i)
-            y = tf_util.hip_mlp_wide(h, [folded[k][0] for k in range(i, i + take)], [folded[k][1] for k in range(i, i + take)])
-            if y is not None:
-                h, i = y, i + take
-                continue
-        # the LDS-resident chain pays off when there are enough 32-row tiles to fill the chip
-        if USE_MLP_CHAIN and h.shape[0] >= 65536 and all(w <= 128 and w % 32 == 0 for w in mlp[i:i + 2]):
-            for take in (2, 1):
-                if i + take > len(mlp) or any(w > 128 or w % 32 for w in mlp[i:i + take]):
-                    continue
-                y = tf_util.hip_mlp_chain(h, [folded[k][0] for k in range(i, i + take)],
-                                          [folded[k][1] for k in range(i, i + take)])
-                if y is not None:
-                    h, i, done = y, i + take, True
-                    break
-        if not done:
-            w2, b2 = folded[i]
-            h = tf_util.hip_linear(h, w2, b2, relu=True)
-            if h.shape[1] != mlp[i]:
-                h = h[:, :mlp[i]].contiguous()
-            i += 1
+        h, took = _first_taken(DENSE_TAIL_ROUTES, stack, h, i)
+        i += took
     return h
 
 

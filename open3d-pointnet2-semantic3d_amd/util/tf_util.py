@@ -254,16 +254,38 @@ def hip_linear(x2d, w, b, relu=True, pool=0):
     return y
 
 
+_SAME = object()
+
+
+def _launch_stack(name, where, lead, ws, bs, trail, oshape, w0=_SAME, after=()):
+    """One launch of a fused-MLP entry point: name(*lead, nlayers, widths[], w[], bias[], *trail, y, *after, stream) with y a new
+    float32 tensor of `oshape` on the device of `where`.  lead / trail / after hold the scalars and the tensors (None -> NULL)
+    in the prototype's order; the tensors are dense already and are held until the call has returned.  ws, bs: the layers'
+    (cin_i, cout_i) weights and biases; w0 replaces the pointer of the first layer's weight where the entry point reads other
+    rows than ws[0]'s (a padded or split first layer; None -> NULL).
+    -> y, or None when the library reports the configuration as unsupported.  Every other failure raises Pn2Error."""
+    L, widths, wptrs, bptrs = layer_arrays(ws, bs)
+    if w0 is not _SAME:
+        wptrs = ptr_table([w0] + list(ws[1:]))
+    y = torch.empty(oshape, dtype=torch.float32, device=where.device)
+    dev = lambda args: [ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args]  # noqa: E731
+    ok = launch(name, where, *dev(lead), L, widths, wptrs, bptrs, *dev(trail), ptr(y), *dev(after), may_refuse=True)
+    return y if ok else None
+
+
+def pad_first_layer_rows(w0, cin):
+    """W0 zero-padded to cin rounded up to a multiple of 8 rows: the wide kernels read W0 in groups of 8 rows"""
+    need = -(-cin // 8) * 8
+    return w0 if w0.shape[0] >= need else F.pad(w0, (0, 0, 0, need - w0.shape[0])).contiguous()
+
+
 def hip_mlp_chain(x2d, ws, bs, pool=0):
     """relu(relu(x @ W0 + b0) @ W1 + b1) with LDS-resident weights (pn2_mlp_chain).  Returns None
     when the library reports the configuration as unsupported (caller falls back to hip_linear)."""
     require_cuda(x2d)
     rows, cin = x2d.shape
-    x2d = x2d.contiguous()
-    L, widths, wptrs, bptrs = layer_arrays(ws, bs)
-    orows = rows // pool if pool else rows
-    y = torch.empty((orows, ws[-1].shape[1]), dtype=torch.float32, device=x2d.device)
-    return y if launch("pn2_mlp_chain", x2d, rows, cin, ptr(x2d), L, widths, wptrs, bptrs, int(pool), ptr(y), may_refuse=True) else None
+    return _launch_stack("pn2_mlp_chain", x2d, (rows, cin, x2d.contiguous()), ws, bs, (int(pool),),
+                         (rows // pool if pool else rows, ws[-1].shape[1]))
 
 
 def multi_copy_(dsts, srcs, fills=()):
@@ -311,41 +333,36 @@ def hip_mlp_wide(x2d, ws, bs, relu_last=True, pool=0):
     through all layers); pool = 32 adds the max over each group of 32 rows.  None when the library reports the
     configuration as unsupported (caller falls back to hip_linear per layer)."""
     require_cuda(x2d)
-    x2d = x2d.contiguous()
     rows, cin = x2d.shape
-    if ws[0].shape[0] < -(-cin // 8) * 8:  # the kernel reads W0 in groups of 8 rows
-        ws = [F.pad(ws[0], (0, 0, 0, -(-cin // 8) * 8 - ws[0].shape[0])).contiguous()] + list(ws[1:])
-    L, widths, wptrs, bptrs = layer_arrays(ws, bs)
-    y = torch.empty((rows // pool if pool else rows, ws[-1].shape[1]), dtype=torch.float32, device=x2d.device)
-    ok = launch("pn2_mlp_wide", x2d, rows, cin, cin, ptr(x2d), L, widths, wptrs, bptrs, int(bool(relu_last)), int(pool), ptr(y),
-                may_refuse=True)
-    return y if ok else None
+    return _launch_stack("pn2_mlp_wide", x2d, (rows, cin, cin, x2d.contiguous()), ws, bs, (int(bool(relu_last)), int(pool)),
+                         (rows // pool if pool else rows, ws[-1].shape[1]), w0=pad_first_layer_rows(ws[0], cin))
+
+
+def _fp_shapes(dist, points1, points2):
+    b, n, _ = dist.shape
+    return b, n, points2.shape[1], (0 if points1 is None else points1.shape[2]), points2.shape[2]
 
 
 def hip_fp_mlp_wide(dist, idx, points1, points2, ws, bs):
     """[three_interpolate(points2) | points1] -> up to three wide dense layers in ONE launch (pn2_fp_mlp_wide);
     -> (b*n, w_last) or None when the library reports the configuration as unsupported."""
     require_cuda(dist, idx, points1, points2)
-    b, n, _ = dist.shape
-    m, c2 = points2.shape[1], points2.shape[2]
-    c1 = 0 if points1 is None else points1.shape[2]
-    need = -(-(c1 + c2) // 8) * 8
-    if ws[0].shape[0] < need:
-        ws = [F.pad(ws[0], (0, 0, 0, need - ws[0].shape[0])).contiguous()] + list(ws[1:])
-    L, widths, wptrs, bptrs = layer_arrays(ws, bs)
-    y = torch.empty((b * n, ws[-1].shape[1]), dtype=torch.float32, device=dist.device)
+    b, n, m, c1, c2 = _fp_shapes(dist, points1, points2)
     p1 = None if points1 is None else points1.contiguous()
-    ok = launch("pn2_fp_mlp_wide", dist, b, n, m, c1, c2, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(p1),
-                ptr(points2.contiguous()), L, widths, wptrs, bptrs, ptr(y), may_refuse=True)
-    return y if ok else None
+    return _launch_stack("pn2_fp_mlp_wide", dist, (b, n, m, c1, c2, dist.contiguous(), idx.contiguous(), p1, points2.contiguous()),
+                         ws, bs, (), (b * n, ws[-1].shape[1]), w0=pad_first_layer_rows(ws[0], c1 + c2))
 
 
 def sa_wide_first_layer(w0):
     """W0 (3 + c, cout) in the reference's [xyz | features] row order (pointnet_util.py:52-54) -> the row order
     pn2_sa_mlp_wide reads: [features | xyz | zero rows up to a multiple of 8]"""
     w = torch.cat([w0[3:], w0[:3]], dim=0)
-    pad = -w.shape[0] % 8
-    return F.pad(w, (0, 0, 0, pad)).contiguous() if pad else w.contiguous()
+    return pad_first_layer_rows(w, w.shape[0]).contiguous()
+
+
+def _sa_out_shape(idx, wl, pool):
+    b, m, ns = idx.shape
+    return (b, m, wl) if pool else (b, m, ns, wl)
 
 
 def hip_sa_mlp_wide(xyz, new_xyz, points, idx, ws, bs, pool=True):
@@ -355,13 +372,8 @@ def hip_sa_mlp_wide(xyz, new_xyz, points, idx, ws, bs, pool=True):
     require_cuda(xyz, new_xyz, points, idx)
     b, n, _ = xyz.shape
     m, ns = idx.shape[1], idx.shape[2]
-    c = points.shape[2]
-    L, widths, wptrs, bptrs = layer_arrays(ws, bs)
-    wl = ws[-1].shape[1]
-    y = torch.empty((b, m, wl) if pool else (b, m, ns, wl), dtype=torch.float32, device=xyz.device)
-    ok = launch("pn2_sa_mlp_wide", xyz, b, n, m, ns, c, ptr(xyz.contiguous()), ptr(new_xyz.contiguous()), ptr(points.contiguous()),
-                ptr(idx.contiguous()), L, widths, wptrs, bptrs, int(bool(pool)), ptr(y), may_refuse=True)
-    return y if ok else None
+    lead = (b, n, m, ns, points.shape[2], xyz.contiguous(), new_xyz.contiguous(), points.contiguous(), idx.contiguous())
+    return _launch_stack("pn2_sa_mlp_wide", xyz, lead, ws, bs, (int(bool(pool)),), _sa_out_shape(idx, ws[-1].shape[1], pool))
 
 
 def hip_fp_mlp_wide_pre(dist, idx, points1, points2, ws, bs):
@@ -370,16 +382,11 @@ def hip_fp_mlp_wide_pre(dist, idx, points1, points2, ws, bs):
     require_cuda(dist, idx, points1, points2)
     if points1 is None:
         return None
-    b, n, _ = dist.shape
-    m, c2 = points2.shape[1], points2.shape[2]
-    c1 = points1.shape[2]
+    b, n, m, c1, c2 = _fp_shapes(dist, points1, points2)
     w0a, w0b = split_first_layer(ws[0], c2, c1, "fp_wide_pre", pad_b_rows=8)
     z = hoist_gemm(points2.reshape(b * m, c2), w0a)
-    L, widths, wptrs, bptrs = layer_arrays([w0b] + list(ws[1:]), bs)
-    y = torch.empty((b * n, ws[-1].shape[1]), dtype=torch.float32, device=dist.device)
-    ok = launch("pn2_fp_mlp_wide_pre", dist, b, n, m, c1, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(points1.contiguous()),
-                ptr(z), L, widths, wptrs, bptrs, ptr(y), may_refuse=True)
-    return y if ok else None
+    return _launch_stack("pn2_fp_mlp_wide_pre", dist, (b, n, m, c1, dist.contiguous(), idx.contiguous(), points1.contiguous(), z),
+                         ws, bs, (), (b * n, ws[-1].shape[1]), w0=w0b)
 
 
 def hip_sa_mlp_wide_pre(xyz, new_xyz, points, idx, ws, bs, pool=True):
@@ -391,28 +398,18 @@ def hip_sa_mlp_wide_pre(xyz, new_xyz, points, idx, ws, bs, pool=True):
     c = points.shape[2]
     w0f, w0x = split_first_layer(ws[0], c, 3, "sa_wide_pre", pad_b_rows=8)
     zf = hoist_gemm(points.reshape(b * n, c), w0f)
-    L, widths, wptrs, bptrs = layer_arrays([w0x] + list(ws[1:]), bs)
-    wl = ws[-1].shape[1]
-    y = torch.empty((b, m, wl) if pool else (b, m, ns, wl), dtype=torch.float32, device=xyz.device)
-    ok = launch("pn2_sa_mlp_wide_pre", xyz, b, n, m, ns, ptr(xyz.contiguous()), ptr(new_xyz.contiguous()), ptr(zf),
-                ptr(idx.contiguous()), L, widths, wptrs, bptrs, int(bool(pool)), ptr(y), may_refuse=True)
-    return y if ok else None
+    return _launch_stack("pn2_sa_mlp_wide_pre", xyz, (b, n, m, ns, xyz.contiguous(), new_xyz.contiguous(), zf, idx.contiguous()),
+                         ws, bs, (int(bool(pool)),), _sa_out_shape(idx, ws[-1].shape[1], pool), w0=w0x)
 
 
 def hip_fp_mlp_fused(dist, idx, points1, points2, ws, bs):
     """[three_interpolate(points2) | points1] -> up to two dense layers in ONE kernel (pn2_fp_mlp_fused);
     returns (b*n, w_last) or None when the library reports the configuration as unsupported."""
     require_cuda(dist, idx, points1, points2)
-    b, n, _ = dist.shape
-    m, c2 = points2.shape[1], points2.shape[2]
-    c1 = 0 if points1 is None else points1.shape[2]
+    b, n, m, c1, c2 = _fp_shapes(dist, points1, points2)
     p1 = None if points1 is None else points1.contiguous()
-    p2 = points2.contiguous()
-    L, widths, wptrs, bptrs = layer_arrays(ws, bs)
-    y = torch.empty((b * n, ws[-1].shape[1]), dtype=torch.float32, device=dist.device)
-    ok = launch("pn2_fp_mlp_fused", dist, b, n, m, c1, c2, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(p1), ptr(p2), L, widths,
-                wptrs, bptrs, ptr(y), may_refuse=True)
-    return y if ok else None
+    return _launch_stack("pn2_fp_mlp_fused", dist, (b, n, m, c1, c2, dist.contiguous(), idx.contiguous(), p1, points2.contiguous()),
+                         ws, bs, (), (b * n, ws[-1].shape[1]))
 
 
 _zero_bias = {}
@@ -459,9 +456,7 @@ def hip_fp_mlp_fused_pre(dist, idx, points1, points2, ws, bs, schedule=None):
     library's choice.  Same bits either way.
     Returns (b*n, w_last), or None when the library reports the configuration as unsupported."""
     require_cuda(dist, idx, points1, points2)
-    b, n, _ = dist.shape
-    m, c2 = points2.shape[1], points2.shape[2]
-    c1 = 0 if points1 is None else points1.shape[2]
+    b, n, m, c1, c2 = _fp_shapes(dist, points1, points2)
     L = len(ws)
     if L < 2 or L > 3 or any(w.shape[1] % 32 or w.shape[1] > 128 for w in ws):
         return None
@@ -471,16 +466,13 @@ def hip_fp_mlp_fused_pre(dist, idx, points1, points2, ws, bs, schedule=None):
     p1, ld1 = (None, 0) if points1 is None else rows_in_place(points1)
     if schedule is not None and p1 is not None:
         p1, ld1 = p1.contiguous(), c1
-    widths, wptrs, bptrs = int_array([w.shape[1] for w in ws]), ptr_table([w1b] + list(ws[1:])), ptr_table(bs)  # w1b: None when c1 == 0
-    y = torch.empty((b * n, ws[-1].shape[1]), dtype=torch.float32, device=dist.device)
-    common = (b, n, m, c1, ptr(dist.contiguous()), ptr(idx.contiguous()), ptr(p1), ptr(z), L, widths, wptrs, bptrs, ptr(y))
-    if schedule is None and p1 is not None and ld1 != c1:
-        ok = launch("pn2_fp_mlp_fused_pre_ld", dist, *common[:7], ld1, *common[7:], may_refuse=True)
-    elif schedule is None:
-        ok = launch("pn2_fp_mlp_fused_pre", dist, *common, may_refuse=True)
-    else:
-        ok = launch("pn2_fp_mlp_fused_pre_schedule", dist, *common, int(schedule), may_refuse=True)
-    return y if ok else None
+    lead = (b, n, m, c1, dist.contiguous(), idx.contiguous(), p1)
+    name, after = "pn2_fp_mlp_fused_pre", ()
+    if schedule is not None:
+        name, after = "pn2_fp_mlp_fused_pre_schedule", (int(schedule),)
+    elif p1 is not None and ld1 != c1:
+        name, lead = "pn2_fp_mlp_fused_pre_ld", lead + (ld1,)
+    return _launch_stack(name, dist, lead + (z,), ws, bs, (), (b * n, ws[-1].shape[1]), w0=w1b, after=after)  # w1b: None when c1 == 0
 
 
 def hip_linear_narrow(x2d, w, b=None):

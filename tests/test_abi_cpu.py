@@ -294,6 +294,176 @@ def test_argument_validation_needs_no_gpu(pn2):
     assert L.pn2_relu_grad(16, nul, fake, fake, nul) == -2
 
 
+# ---- refusals of the fused-MLP entry points (csrc/pn2_sa_fused.hip, pn2_sa_fused_bf16.hip, pn2_mlp_wide.hip) -------------------
+# One reader (csrc/pn2_layer_stack.h) validates nlayers / widths[] / w[] / bias[] for all fifteen; what a refused call returns,
+# and which fault wins where two are present, is part of the ABI.  REFUSAL_TABLE was printed by `python tests/test_abi_cpu.py`
+# on the commit before the shared reader: one row per fault, one column per entry point of REFUSAL_ENTRIES.
+#   I = PN2_EINVAL, N = PN2_ENULL, R = PN2_ERANGE, U = PN2_EUNSUP;  . = not called: the entry point has no such argument, or it
+#   accepts the combination (a misaligned bias on the chains, a NULL w[0] with c1 == 0) and would go on to launch.
+# A fault is a list of changes to a call that would be accepted, joined by " + ":
+#   nlayers=0 / nlayers=max+1      widths=NULL / w=NULL / bias=NULL (the host tables)
+#   widths[0]=48, widths[last]=0   a width at the first / last layer
+#   w[0]=NULL, bias[last]=NULL     a device pointer of a layer;  =odd: 4 bytes past a 16-byte boundary
+#   c1=0, pool=7                   a scalar argument of that name
+#   range                          the row count pushed past what an int holds (b = m = n = 2^20; rows = 2^31 - 8)
+# Device pointers are placeholders that are never dereferenced; the host arrays are real.  Every call of pn2_sa_mlp_max_fused*
+# keeps nsample = 32, so no zero-fill is queued even on the commit that queued it ahead of the kernel choice.
+REFUSAL_CODES = {"I": -1, "N": -2, "R": -3, "U": -4}
+_CHAIN3, _CHAIN2, _CHAIN128, _WIDE = [64, 64, 128], [128, 128], [128, 128, 128], [128, 256, 512]
+REFUSAL_ENTRIES = [  # entry point, widths of a call it accepts (its most layers), scalar arguments that differ from _SCALARS
+    ("pn2_sa_mlp_max_fused", _CHAIN3, {}), ("pn2_sa_mlp_max_fused_ld", _CHAIN3, {}), ("pn2_sa_mlp_rows_fused", _CHAIN2, {}),
+    ("pn2_sa_mlp_fused_pre", _CHAIN3, {"pool": 1}), ("pn2_sa_mlp_max_fused_bf16", _CHAIN3, {}), ("pn2_mlp_chain", _CHAIN2, {}),
+    ("pn2_fp_mlp_fused", _CHAIN2, {}), ("pn2_fp_mlp_fused_pre", _CHAIN128, {}), ("pn2_fp_mlp_fused_pre_ld", _CHAIN128, {}),
+    ("pn2_fp_mlp_fused_pre_schedule", _CHAIN128, {}), ("pn2_mlp_wide", _WIDE, {}), ("pn2_sa_mlp_wide", _WIDE, {"pool": 1}),
+    ("pn2_fp_mlp_wide", _WIDE, {}), ("pn2_fp_mlp_wide_pre", _WIDE, {}), ("pn2_sa_mlp_wide_pre", _WIDE, {"pool": 1})]
+_SCALARS = dict(b=1, n=64, m=8, nsample=32, c=16, c1=4, c2=8, rows=64, cin=8, x_stride=8, relu_last=1, pool=0, schedule=0,
+                ld_xyz=3, ld_points=16, ld_points1=4)
+_RANGE = dict(b=1 << 20, n=1 << 20, m=1 << 20, rows=(1 << 31) - 8)
+REFUSAL_FAULTS = [
+    "nlayers=0", "nlayers=max+1", "widths=NULL", "w=NULL", "bias=NULL",
+    "widths[0]=0", "widths[0]=48", "widths[0]=160", "widths[0]=64", "widths[0]=384",
+    "widths[last]=0", "widths[last]=48", "widths[last]=160", "widths[last]=64", "widths[last]=384",
+    "w[0]=NULL", "w[last]=NULL", "bias[0]=NULL", "bias[last]=NULL",
+    "w[0]=odd", "w[last]=odd", "bias[0]=odd", "bias[last]=odd",
+    "c1=0 + w[0]=NULL", "c1=0 + w[0]=NULL + w[last]=NULL", "c1=0 + w[0]=NULL + bias[0]=NULL", "c1=0 + w[0]=odd",
+    "range", "pool=7",
+    # two faults at once: the precedence
+    "nlayers=0 + widths=NULL", "nlayers=max+1 + w=NULL", "nlayers=max+1 + widths[0]=48", "nlayers=max+1 + widths[0]=64",
+    "nlayers=max+1 + range", "widths=NULL + range",
+    "widths[0]=48 + w[0]=NULL", "widths[0]=64 + w[0]=NULL", "w[0]=odd + bias[0]=NULL", "bias[0]=odd + w[0]=NULL",
+    "widths[last]=0 + bias[0]=NULL", "w[0]=NULL + w[last]=odd", "w[0]=odd + bias[last]=NULL", "bias[last]=odd + w[last]=NULL",
+    "widths[0]=48 + range", "widths[0]=64 + range", "w[last]=NULL + range", "w[last]=odd + range",
+    "pool=7 + w[0]=NULL", "pool=7 + widths[last]=64", "pool=7 + range",
+]
+REFUSAL_TABLE = [
+    ("nlayers=0",                                 "I I I I I I I I I I U U U U U"),
+    ("nlayers=max+1",                             "U U U U U U U U U U U U U U U"),
+    ("widths=NULL",                               "N N N N N N N N N N N N N N N"),
+    ("w=NULL",                                    "N N N N N N N N N N N N N N N"),
+    ("bias=NULL",                                 "N N N N N N N N N N N N N N N"),
+    ("widths[0]=0",                               "U U U U U U U U U U U U U U U"),
+    ("widths[0]=48",                              "U U U U U U U U U U U U U U U"),
+    ("widths[0]=160",                             "U U U U U U U U U U U U U U U"),
+    ("widths[0]=64",                              ". . U . . . . U U U U U U U U"),
+    ("widths[0]=384",                             "U U U U U U U U U U U U U U U"),
+    ("widths[last]=0",                            "U U U U U U U U U U U U U U U"),
+    ("widths[last]=48",                           "U U U U U U U U U U U U U U U"),
+    ("widths[last]=160",                          "U U U U U U U U U U U U U U U"),
+    ("widths[last]=64",                           ". . U U U U U U U U U U U U U"),
+    ("widths[last]=384",                          "U U U U U U U U U U U U U U U"),
+    ("w[0]=NULL",                                 "N N N N N N N N N N N N N N N"),
+    ("w[last]=NULL",                              "N N N N N N N N N N N N N N N"),
+    ("bias[0]=NULL",                              "N N N N N N N N N N N N N N N"),
+    ("bias[last]=NULL",                           "N N N N N N N N N N N N N N N"),
+    ("w[0]=odd",                                  "U U U U . U U U U U U U U U U"),
+    ("w[last]=odd",                               "U U U U . U U U U U U U U U U"),
+    ("bias[0]=odd",                               ". . . . . . . . . . U U U U U"),
+    ("bias[last]=odd",                            ". . . . . . . . . . U U U U U"),
+    ("c1=0 + w[0]=NULL",                          ". . . . . . N . . . . . N I ."),
+    ("c1=0 + w[0]=NULL + w[last]=NULL",           ". . . . . . N N N N . . N I ."),
+    ("c1=0 + w[0]=NULL + bias[0]=NULL",           ". . . . . . N N N N . . N I ."),
+    ("c1=0 + w[0]=odd",                           ". . . . . . U U U U . . U I ."),
+    ("range",                                     "R R R R R . R R R R R R R R R"),
+    ("pool=7",                                    ". . . . . U . . . . U . . . ."),
+    ("nlayers=0 + widths=NULL",                   "I I I I I I I I I I U U U U U"),
+    ("nlayers=max+1 + w=NULL",                    "N N N N N N N N N N U U U U U"),
+    ("nlayers=max+1 + widths[0]=48",              "U U U U U U U U U U U U U U U"),
+    ("nlayers=max+1 + widths[0]=64",              "U U U U U U U U U U U U U U U"),
+    ("nlayers=max+1 + range",                     "U U R U U U R R R R U U U U U"),
+    ("widths=NULL + range",                       "N N N N N N N N N N N N N N N"),
+    ("widths[0]=48 + w[0]=NULL",                  "U U U U U U U N N N U U U U U"),
+    ("widths[0]=64 + w[0]=NULL",                  "N N N N N N N N N N U U U U U"),
+    ("w[0]=odd + bias[0]=NULL",                   "N N N N N N N N N N N N N N N"),
+    ("bias[0]=odd + w[0]=NULL",                   "N N N N N N N N N N N N N N N"),
+    ("widths[last]=0 + bias[0]=NULL",             "N N N N N N N N N N N N N N N"),
+    ("w[0]=NULL + w[last]=odd",                   "N N N N N N N N N N N N N N N"),
+    ("w[0]=odd + bias[last]=NULL",                "U U U U N U U U U U U U U U U"),
+    ("bias[last]=odd + w[last]=NULL",             "N N N N N N N N N N N N N N N"),
+    ("widths[0]=48 + range",                      "R R R R R U R R R R U U U U U"),
+    ("widths[0]=64 + range",                      "R R R R R . R R R R U U U U U"),
+    ("w[last]=NULL + range",                      "R R R R R N R R R R N N N N N"),
+    ("w[last]=odd + range",                       "R R R R R U R R R R U U U U U"),
+    ("pool=7 + w[0]=NULL",                        ". . . N . U . . . . N N . . N"),
+    ("pool=7 + widths[last]=64",                  ". . . U . U . . . . U U . . U"),
+    ("pool=7 + range",                            ". . . R . U . . . . U R . . R"),
+]
+
+
+def _refusal_call(pn2, entry, widths, own, fault):
+    """-> the code `entry` returns for an acceptable call with `fault` applied, or None when the entry point lacks an argument
+    the fault names"""
+    f = _header().functions[entry]
+    nmax = len(widths)
+    scal = dict(_SCALARS, **own)
+    lay = dict(nlayers=nmax, widths=list(widths) + [128], w=[4096] * (nmax + 1), bias=[8192] * (nmax + 1))
+    tables = dict(widths=True, w=True, bias=True)
+    for atom in fault.split(" + "):
+        if atom == "range":
+            scal.update(_RANGE)
+            continue
+        key, value = atom.split("=", 1)
+        if "[" in key:
+            name, at = key[:-1].split("[")
+            at = 0 if at == "0" else nmax - 1
+            if name == "widths":
+                lay[name][at] = int(value)
+            elif value == "NULL":
+                lay[name][at] = None
+            else:  # odd
+                lay[name][at] += 4
+        elif value == "NULL":
+            tables[key] = False
+        elif key == "nlayers":
+            lay["nlayers"] = nmax + 1 if value == "max+1" else int(value)
+        else:
+            if key not in f.argnames:
+                return None
+            scal[key] = int(value)
+    fake = ctypes.c_void_p(4096)  # never dereferenced: every call of the table is refused before a launch
+    host = dict(widths=(ctypes.c_int * (nmax + 1))(*lay["widths"]), w=(ctypes.c_void_p * (nmax + 1))(*lay["w"]),
+                bias=(ctypes.c_void_p * (nmax + 1))(*lay["bias"]))
+    args = []
+    for name, t in zip(f.argnames, f.argtypes):
+        if name == "nlayers":
+            args.append(lay["nlayers"])
+        elif name in host:
+            args.append(host[name] if tables[name] else None)
+        elif name == "stream":
+            args.append(None)
+        elif t is ctypes.c_void_p:
+            args.append(fake)
+        else:
+            args.append(scal[name])
+    return getattr(pn2._lib.lib, entry)(*args)
+
+
+def test_refusal_table_is_well_formed():
+    assert len(REFUSAL_ENTRIES) == 15 and len({e[0] for e in REFUSAL_ENTRIES}) == 15
+    assert [f for f, _ in REFUSAL_TABLE] == REFUSAL_FAULTS
+    for fault, cells in REFUSAL_TABLE:
+        assert len(cells.split()) == 15 and set(cells.split()) <= set(REFUSAL_CODES) | {"."}, fault
+    for col, (entry, _, _) in enumerate(REFUSAL_ENTRIES):  # every entry point is refused for each kind of fault the issue names
+        rows = {f for f, cells in REFUSAL_TABLE if cells.split()[col] != "."}
+        assert {"nlayers=0", "nlayers=max+1", "widths=NULL", "w=NULL", "bias=NULL", "widths[0]=0", "w[last]=NULL", "bias[0]=NULL",
+                "bias[last]=NULL", "widths[0]=48 + w[0]=NULL", "w[0]=odd + bias[0]=NULL"} <= rows, entry
+
+
+@pytest.mark.parametrize("col", range(15), ids=[e[0] for e in REFUSAL_ENTRIES])
+def test_fused_mlp_refusals_are_unchanged(pn2, col):
+    """every refused layer stack returns what the commit before the shared reader returned, precedence included"""
+    entry, widths, own = REFUSAL_ENTRIES[col]
+    called = 0
+    for fault, cells in REFUSAL_TABLE:
+        cell = cells.split()[col]
+        if cell == ".":
+            continue
+        rc = _refusal_call(pn2, entry, widths, own, fault)
+        assert rc in REFUSAL_CODES.values(), (entry, fault, rc)
+        assert rc == REFUSAL_CODES[cell], (entry, fault, rc)
+        called += 1
+    assert called >= 25, entry
+
+
 def test_rows_in_place_recognises_column_blocks():
     """_lib.rows_in_place: a dense (b,n,c) tensor or a column block of a wider dense one is read where it lies (row stride in
     floats); anything else is copied.  Host logic only."""
@@ -334,3 +504,13 @@ def test_product_package_never_imports_the_oracle():
             if f.endswith((".py", ".hip", ".h")):
                 txt = open(os.path.join(dp, f)).read()
                 assert "import oracle" not in txt and "from oracle" not in txt and "pn2_oracle" not in txt, f
+
+
+if __name__ == "__main__":  # prints REFUSAL_TABLE's rows from the library in the tree (see the comment above the table)
+    import sys
+    sys.path.insert(0, ROOT)
+    import pn2_amd
+    letter = {v: k for k, v in REFUSAL_CODES.items()}
+    for fault in REFUSAL_FAULTS:
+        cells = [letter.get(_refusal_call(pn2_amd, e, wd, own, fault), ".") for e, wd, own in REFUSAL_ENTRIES]
+        print("    (%-44s %r)," % ('"%s",' % fault, " ".join(cells)))
