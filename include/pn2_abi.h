@@ -829,6 +829,49 @@ int pn2_sa_hoist_rows_multi_bn(int nscales, int b, int n, int m, int z_stride, c
                                float *const *running_mean, float *const *running_var, float *const *save_mean,
                                float *const *save_invstd, float *const *scale, float *const *shift, void *stream);
 
+/* ---- raw ASCII scans: the step in front of the down-sampling (reference preprocess.py:23-55, util/point_cloud_util.py:53-57) ----
+ * Semantic3D ships <scene>.txt (`x y z intensity r g b` per line) and <scene>.labels (one integer per line).  Both are parsed
+ * from a device buffer of text in two stages: a line index, then one line per lane.  One call takes one chunk of at most
+ * PN2_TEXT_MAX_BYTES bytes (int offsets), 16-byte aligned, holding whole lines; lines end in '\n', a last line without one
+ * is a line, nothing follows a final '\n'.  Tokens are separated by runs of space, tab and '\r'.
+ *
+ * Number rule (the oracle is Python's float(token) / int(token) on the grammar below):
+ *   float token  [+-]? digits* ('.' digits*)? ([eE][+-]?digits+)?  with at least one mantissa digit.  With leading zeros
+ *                stripped, w = the integer of ALL mantissa digits and e10 = exponent - number of fraction digits:
+ *                w <= 2^53 and |e10| <= 22 is FAST: the value is (double)w * 10^e10 or (double)w / 10^-e10 -- one correctly
+ *                rounded IEEE operation on two exact operands (Clinger's fast path), equal to float(token); -0.0 keeps its
+ *                sign.  Every other valid token, and nan / inf / infinity in any case with an optional sign, is SLOW: the
+ *                column's bit (1 << column) is set in the line's flags and nothing is written for it (the caller parses it).
+ *   int token    [+-]?digits+ with the value in int32; anything else makes the line malformed.
+ * Column kinds: PN2_TEXT_F64 -> the next column of out_f64 (nlines, nF); PN2_TEXT_I32 (int token) and PN2_TEXT_TRUNC_I32
+ * (float token truncated toward zero, the reference's int(float(tok)); |v| >= 2^31 makes the line malformed) -> the next
+ * column of out_i32 (nlines, nI); PN2_TEXT_SKIP: any token, not read.  A line with another number of tokens than ncols, a
+ * bad token or nothing but whitespace is malformed: PN2_TEXT_MALFORMED in its flags, its outputs unspecified. */
+#define PN2_TEXT_TILE_BYTES 4096     /* bytes of text per workgroup of the line index: 256 lanes x one 16-byte load */
+#define PN2_TEXT_MAX_BYTES 1073741824
+#define PN2_TEXT_MAX_COLS 8
+#define PN2_TEXT_F64 0
+#define PN2_TEXT_I32 1
+#define PN2_TEXT_TRUNC_I32 2
+#define PN2_TEXT_SKIP 3
+#define PN2_TEXT_MALFORMED 128       /* the flags' top bit; column 7, where there is one, is therefore I32 or SKIP (PN2_EUNSUP) */
+
+/* Line index.  line_start (line_cap) int32: entry i = offset of the first byte of line i, entry nlines = one past the '\n'
+ * that ends the last line (nbytes + 1 when it has none), so line i is [line_start[i], line_start[i + 1] - 1).  *out_count
+ * (device int) = nlines, whatever line_cap is; entries at or past line_cap are not written, so a caller that finds
+ * *out_count + 1 > line_cap calls again with more room.  workspace: 256-byte aligned, *bytes of
+ * pn2_text_index_workspace_bytes(nbytes) -- per tile of PN2_TEXT_TILE_BYTES a count and its exclusive scan. */
+int pn2_text_index_workspace_bytes(int nbytes, unsigned long long *bytes);
+int pn2_text_index_lines(const unsigned char *text, int nbytes, int *line_start, int line_cap, int *out_count,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* Field parse of lines [0, nlines) of the index above.  kinds (ncols) is a HOST array of PN2_TEXT_* read at call time.
+ * out_f64 / out_i32 may be NULL when no column writes there.  flags (nlines) bytes.  status (3) device ints, set by the
+ * call: the smallest malformed line index (0x7fffffff: none), the number of malformed lines, the number of slow tokens
+ * in well-formed lines.  Needs no workspace. */
+int pn2_text_parse(const unsigned char *text, int nbytes, const int *line_start, int nlines, const int *kinds, int ncols,
+                   double *out_f64, int *out_i32, unsigned char *flags, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
