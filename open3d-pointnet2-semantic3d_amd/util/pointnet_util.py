@@ -501,6 +501,57 @@ def group_pool(new_points, grouped_xyz, pooling):
     return _GroupPool.apply(new_points, grouped_xyz if mode == 2 else None, mode)
 
 
+# ---- training: which form a module's first layer takes, and which layers of a stack defer their batch norm ---------------------
+def _sa_first_layer_fusable(is_training, points, mlp, nsample, group_all, knn, use_xyz, bn, pooling):
+    """what both fused first-layer forms of pointnet_sa_module need: training; plain ball-query grouping with xyz (no group_all, no
+    knn); batch norm and max pooling; float32 points; a first layer of width % 4 == 0; nsample <= 1024"""
+    return (bool(is_training) and not group_all and not knn and use_xyz and bn and pooling == "max" and points is not None
+            and points.dtype == torch.float32 and len(mlp) > 0 and mlp[0] % 4 == 0 and nsample <= 1024)
+
+
+def _sa_train_hoisted(fusable, points, mlp, geometry):
+    """first layer on the n SOURCE points instead of the m * nsample grouped rows (tf_util._TrainHoistedBnRelu):
+    _sa_first_layer_fusable; tf_util.USE_HOISTED_TRAIN; features of >= 16 channels; geometry AND its scatter plan computed ahead,
+    the plan usable at the first layer's width"""
+    return bool(fusable and tf_util.USE_HOISTED_TRAIN and points.shape[2] >= 16 and geometry is not None and len(geometry) > 2
+                and _plan_usable(geometry[2], mlp[0]))
+
+
+def _sa_train_small_first(fusable, hoisted, points, mlp):
+    """few point channels (the level-0 module: xyz + rgb): front end + first conv + its statistics in ONE launch
+    (tf_util.conv2d_sa_first_small): _sa_first_layer_fusable and not hoisted; tf_util.USE_SA_FIRST_LAYER_FUSED and
+    USE_BN_FINISH_IN_PRODUCER; at most 5 point channels that carry no gradient; first layer at most 1024 wide"""
+    return bool(fusable and not hoisted and tf_util.USE_SA_FIRST_LAYER_FUSED and tf_util.USE_BN_FINISH_IN_PRODUCER
+                and points.shape[2] <= 5 and not points.requires_grad and mlp[0] <= 1024)
+
+
+def _msg_train_hoisted(is_training, points, mlp_list, nsample_list, geometry, plans, use_xyz, bn):
+    """all scales' first layers hoisted together (tf_util._TrainHoistedMsgBnRelu): training with geometry computed ahead;
+    tf_util.USE_HOISTED_MSG_TRAIN; batch norm, xyz used; float32 points of >= 16 channels; at most MSG_HOIST_MAX_SCALES scales, each
+    with a first layer of width % 4 == 0, a plan usable at that width and nsample <= 1024"""
+    return bool(geometry is not None and bool(is_training) and tf_util.USE_HOISTED_MSG_TRAIN and bn and use_xyz and points is not None
+                and points.dtype == torch.float32 and points.shape[2] >= 16 and len(mlp_list) <= tf_util.MSG_HOIST_MAX_SCALES
+                and all(len(mlp) > 0 and mlp[0] % 4 == 0 and _plan_usable(pl, mlp[0]) for mlp, pl in zip(mlp_list, plans))
+                and all(k <= 1024 for k in nsample_list))
+
+
+def _fp_train_hoisted(points1, points2, mlp, plan, bn):
+    """the interpolated half of the first conv on the n2 KNOWN points instead of the n1 dense ones (tf_util._TrainHoistedBnRelu):
+    tf_util.USE_HOISTED_TRAIN; batch norm; a skip link of 1..8 float32 channels that carry no gradient (the level-0 module's
+    colours); float32 points2; a first layer of width % 32 == 0; the interpolation's scatter plan, usable at that width"""
+    return bool(tf_util.USE_HOISTED_TRAIN and bn and points1 is not None and 1 <= points1.shape[2] <= 8
+                and not points1.requires_grad and points1.dtype == torch.float32 and points2.dtype == torch.float32
+                and len(mlp) > 0 and mlp[0] % 32 == 0 and _plan_usable(plan, mlp[0]))
+
+
+def _defer_after(is_training, bn, rows, widths, i):
+    """may layer i of a stack over `rows` rows hand its UN-normalised output to layer i + 1 (tf_util.USE_BN_ON_LOAD: that layer
+    applies the batch norm + ReLU while loading it)?  Only a layer whose output feeds nothing but the next conv2d may.  widths: the
+    stack's widths -- followed, where the caller knows it, by the width of what consumes the last layer (0: unknown -> materialise)"""
+    return bool(is_training and bn and i + 1 < len(widths) and widths[i + 1] > 0
+                and tf_util.can_defer_bn(rows, widths[i], widths[i + 1]))
+
+
 def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_all, is_training, bn_decay, scope,
                        bn=True, pooling="max", knn=False, use_xyz=True, use_nchw=False, geometry=None):
     """PointNet Set Abstraction module -> new_xyz (B,npoint,3), new_points (B,npoint,mlp[-1] or mlp2[-1]), idx.
@@ -531,34 +582,22 @@ def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_al
             if geometry is not None and geometry[1] is None:
                 raise ValueError("geometry=(new_xyz, None) (samples drawn ahead, ball query here) is the inference fast path's "
                                  "hand-over: pass the idx too for training / group_all / knn / non-max pooling")
-            # training, features of >= 16 channels, geometry + scatter plan computed ahead: the feature half of the first
-            # conv runs on the n SOURCE points instead of the m * nsample grouped rows (tf_util._TrainHoistedBnRelu)
-            hoist = (bool(is_training) and tf_util.USE_HOISTED_TRAIN and not group_all and not knn and use_xyz and bn
-                     and pooling == "max" and points is not None and points.dtype == torch.float32 and points.shape[2] >= 16
-                     and len(mlp) > 0 and mlp[0] % 4 == 0 and nsample <= 1024 and geometry is not None and len(geometry) > 2
-                     and _plan_usable(geometry[2], mlp[0]))
+            # pick the first-layer form ...
+            fusable = _sa_first_layer_fusable(is_training, points, mlp, nsample, group_all, knn, use_xyz, bn, pooling)
+            hoist = _sa_train_hoisted(fusable, points, mlp, geometry)
             first = 0
-            # a layer whose output feeds only the next conv2d of this loop may hand over its UN-normalised output
-            # (tf_util.USE_BN_ON_LOAD): the next layer applies the batch norm + ReLU while loading it
-            defer = lambda i, rows: (bool(is_training) and bn and i + 1 < len(mlp)  # noqa: E731
-                                     and tf_util.can_defer_bn(rows, mlp[i], mlp[i + 1]))
-            small_first = (bool(is_training) and tf_util.USE_SA_FIRST_LAYER_FUSED and tf_util.USE_BN_FINISH_IN_PRODUCER
-                           and not hoist and not group_all and not knn and use_xyz and bn and pooling == "max"
-                           and points is not None and points.dtype == torch.float32 and points.shape[2] <= 5
-                           and not points.requires_grad and len(mlp) > 0 and mlp[0] % 4 == 0 and mlp[0] <= 1024
-                           and nsample <= 1024)
-            if small_first:
-                # few point channels (the level-0 module: xyz + rgb): front end + first conv + its statistics in ONE launch
+            if _sa_train_small_first(fusable, hoist, points, mlp):
                 new_xyz, idx = geometry[:2] if geometry is not None else sa_geometry(xyz, npoint, radius, nsample)
                 grouped_xyz = None
                 new_points = tf_util.conv2d_sa_first_small(xyz, new_xyz, points, idx, mlp[0], "conv0", bn_decay,
-                                                           pool=nsample if len(mlp) == 1 else 0, defer_bn=defer(0, idx.numel()))
+                                                           pool=nsample if len(mlp) == 1 else 0,
+                                                           defer_bn=_defer_after(is_training, bn, idx.numel(), mlp, 0))
                 first = 1
             elif hoist:
                 new_xyz, idx, grouped_xyz = geometry[0], geometry[1], None
                 new_points = tf_util.conv2d_hoisted_first("sa", points, (xyz, new_xyz, idx), geometry[2], 3 + points.shape[2],
                                                           mlp[0], "conv0", bn_decay, pool=nsample if len(mlp) == 1 else 0,
-                                                          defer_bn=defer(0, idx.numel()))
+                                                          defer_bn=_defer_after(is_training, bn, idx.numel(), mlp, 0))
                 first = 1
             elif group_all:
                 nsample = xyz.shape[1]
@@ -566,15 +605,14 @@ def pointnet_sa_module(xyz, points, npoint, radius, nsample, mlp, mlp2, group_al
             else:
                 new_xyz, new_points, idx, grouped_xyz = sample_and_group(npoint, radius, nsample, xyz, points, knn,
                                                                          use_xyz, geometry=geometry)
-            # training: the max over K rides in the last layer's batch-norm kernels (tf_util._TrainDenseBnRelu)
+            # ... then loop.  Training: the max over K rides in the last layer's batch-norm kernels (tf_util._TrainDenseBnRelu)
             fuse_pool = bool(is_training) and bn and pooling == "max" and len(mlp) > 0 and nsample <= 1024
-            for i, cout in enumerate(mlp):
-                if i < first:
-                    continue
-                new_points = tf_util.conv2d(new_points, cout, [1, 1], padding="VALID", stride=[1, 1], bn=bn,
+            for i in range(first, len(mlp)):
+                rows = new_points.numel() // new_points.shape[-1]
+                new_points = tf_util.conv2d(new_points, mlp[i], [1, 1], padding="VALID", stride=[1, 1], bn=bn,
                                             is_training=is_training, scope="conv%d" % i, bn_decay=bn_decay,
                                             pool=nsample if (fuse_pool and i == len(mlp) - 1) else 0,
-                                            defer_bn=defer(i, new_points.numel() // new_points.shape[-1]))
+                                            defer_bn=_defer_after(is_training, bn, rows, mlp, i))
             if pooling not in _POOL_MODES:
                 raise ValueError("unknown pooling %r" % pooling)
             if not (pooling == "max" and fuse_pool):
@@ -618,7 +656,7 @@ def pointnet_sa_module_msg(xyz, points, npoint, radius_list, nsample_list, mlp_l
     require_cuda(xyz, points)
     with tf_util.variable_scope(scope):
         xyz = xyz.contiguous()
-        queries = None
+        queries = g_idx = g_plans = None
         if geometry is not None:
             if new_xyz is not None:
                 raise ValueError("pass the samples either as new_xyz or inside geometry, not both")
@@ -636,14 +674,9 @@ def pointnet_sa_module_msg(xyz, points, npoint, radius_list, nsample_list, mlp_l
         elif tuple(new_xyz.shape) != (xyz.shape[0], int(npoint), 3):
             raise ValueError("new_xyz: (batch_size, npoint, 3) samples of xyz expected")
         outs = []
-        if (geometry is not None and bool(is_training) and tf_util.USE_HOISTED_MSG_TRAIN and bn and use_xyz and points is not None
-                and points.dtype == torch.float32 and points.shape[2] >= 16 and len(mlp_list) <= tf_util.MSG_HOIST_MAX_SCALES
-                and all(len(mlp) > 0 and mlp[0] % 4 == 0 and _plan_usable(pl, mlp[0]) for mlp, pl in zip(mlp_list, g_plans))
-                and all(k <= 1024 for k in nsample_list)):
-            # ---- training, geometry + plans computed ahead: all scales' first layers hoisted together ----
-            rows = [g_idx[i].numel() for i in range(len(mlp_list))]
-            defer = lambda i, j: (j + 1 < len(mlp_list[i])  # noqa: E731
-                                  and tf_util.can_defer_bn(rows[i], mlp_list[i][j], mlp_list[i][j + 1]))
+        if _msg_train_hoisted(is_training, points, mlp_list, nsample_list, geometry, g_plans, use_xyz, bn):
+            # ---- training, geometry + plans computed ahead: all scales' first layers hoisted together, then loop ----
+            defer = lambda i, j: _defer_after(True, True, g_idx[i].numel(), mlp_list[i], j)  # noqa: E731
             firsts = tf_util.conv2d_hoisted_first_msg(
                 points, xyz, new_xyz, g_idx, g_plans, [mlp[0] for mlp in mlp_list], ["conv%d_0" % i for i in range(len(mlp_list))],
                 bn_decay, pools=[nsample_list[i] if len(mlp) == 1 else 0 for i, mlp in enumerate(mlp_list)],
@@ -878,24 +911,15 @@ def pointnet_fp_module(xyz1, xyz2, points1, points2, mlp, is_training, bn_decay,
         if not is_training:
             # weights + interpolate + concat fused, then LDS-resident MLP chains / MFMA layers
             return fp_features_inference(dist, idx, points1, points2, mlp, bn, bn_decay)
-        # the interpolated half of the first conv runs on the n2 known points instead of the n1 dense ones
-        # (tf_util._TrainHoistedBnRelu); points1 = a few input channels (the level-0 module) or SA features
-        c1 = 0 if points1 is None else points1.shape[2]
-        if (tf_util.USE_HOISTED_TRAIN and bn and points1 is not None
-                and 1 <= c1 <= 8 and not points1.requires_grad
-                and points1.dtype == torch.float32 and points2.dtype == torch.float32 and len(mlp) > 0 and mlp[0] % 32 == 0
-                and _plan_usable(plan, mlp[0])):
-            rows = points1.shape[0] * points1.shape[1]
-            nxt = list(mlp[1:]) + [int(defer_last_bn)]  # width of the layer that consumes layer i (0: unknown -> materialise)
-            defer = lambda i: bn and nxt[i] > 0 and tf_util.can_defer_bn(rows, mlp[i], nxt[i])  # noqa: E731
-            h = tf_util.conv2d_hoisted_first("fp", points2, (dist, idx, points1), plan, points2.shape[2] + points1.shape[2],
-                                             mlp[0], "conv_0", bn_decay, defer_bn=defer(0))
-            for i, cout in enumerate(mlp):
-                if i > 0:
-                    h = tf_util.conv2d(h, cout, [1, 1], padding="VALID", stride=[1, 1], bn=bn, is_training=is_training,
-                                       scope="conv_%d" % i, bn_decay=bn_decay, defer_bn=defer(i))
-            return h.squeeze(2)
-        if USE_FUSED_TRAIN_FRONT and points2.dtype == torch.float32:
+        # pick the first-layer form (points1 = a few input channels -- the level-0 module -- or SA features), then loop
+        rows = dist.shape[0] * dist.shape[1]
+        widths = list(mlp) + [int(defer_last_bn)]  # ... + the width of what consumes the last layer (0: unknown -> materialise)
+        first = 0
+        if _fp_train_hoisted(points1, points2, mlp, plan, bn):
+            new_points1 = tf_util.conv2d_hoisted_first("fp", points2, (dist, idx, points1), plan, points2.shape[2] + points1.shape[2],
+                                                       mlp[0], "conv_0", bn_decay, defer_bn=_defer_after(True, bn, rows, widths, 0))
+            first = 1
+        elif USE_FUSED_TRAIN_FRONT and points2.dtype == torch.float32:
             new_points1 = _FPInterpConcat.apply(dist, idx, None if points1 is None else points1.contiguous(),
                                                 points2.contiguous(), plan)
         else:
@@ -904,12 +928,10 @@ def pointnet_fp_module(xyz1, xyz2, points1, points2, mlp, is_training, bn_decay,
             weight = (1.0 / dist) / norm
             interpolated = three_interpolate(points2, idx, weight)
             new_points1 = torch.cat([interpolated, points1], dim=2) if points1 is not None else interpolated
-        new_points1 = new_points1.unsqueeze(2)
-        rows = new_points1.shape[0] * new_points1.shape[1]
-        nxt = list(mlp[1:]) + [int(defer_last_bn)]
-        for i, cout in enumerate(mlp):
-            # un-normalised hand-over to the next layer of the stack (tf_util.USE_BN_ON_LOAD)
-            dfr = bool(is_training) and bn and nxt[i] > 0 and tf_util.can_defer_bn(rows, cout, nxt[i])
-            new_points1 = tf_util.conv2d(new_points1, cout, [1, 1], padding="VALID", stride=[1, 1], bn=bn,
-                                         is_training=is_training, scope="conv_%d" % i, bn_decay=bn_decay, defer_bn=dfr)
+        if not first:
+            new_points1 = new_points1.unsqueeze(2)
+        for i in range(first, len(mlp)):
+            new_points1 = tf_util.conv2d(new_points1, mlp[i], [1, 1], padding="VALID", stride=[1, 1], bn=bn,
+                                         is_training=is_training, scope="conv_%d" % i, bn_decay=bn_decay,
+                                         defer_bn=_defer_after(True, bn, rows, widths, i))
         return new_points1.squeeze(2)

@@ -15,7 +15,7 @@ Two execution paths per layer:
 """
 import contextlib
 import math
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import weakref
 
@@ -505,26 +505,101 @@ def hip_matmul(x2d, w):
     return hip_linear(x2d, w.contiguous(), None, relu=False)
 
 
-def hip_matmul_bn_stats(x2d, w, ws):
-    """y = x2d @ w on pn2_linear_bn_stats: the GEMM also leaves the column sums of y and y^2 in the ZEROED batch-norm
-    workspace `ws` (pn2_bn_workspace_bytes(cout) bytes), which is then BN_WS_SUMMED.  cout % 32 == 0."""
+# ---- the training layer path: its A/B switches and thresholds (tests and tools set them as attributes of this module; no path is
+# retired -- the off paths are the witnesses the tests compare against).  DESIGN.md section 5 names the parts below. ------------
+USE_GEMM_BN_STATS = True  # batch statistics from the forward GEMM's epilogue (set False: separate pass over y; tests / A-B)
+# The one-block launches that used to follow every producer of batch-norm sums (fold the slot copies; derive scale / shift resp. the
+# gradient constants) are done by the producer's LAST WORKGROUP (csrc/pn2_common.h pn2_bn_finish): a layer inside a stack is one
+# launch forward (GEMM + statistics + constants) and two backward (data gradient + finish of the layer below; weight gradient).
+# False: the separate launches (A/B, tests).
+USE_BN_FINISH_IN_PRODUCER = True
+# cross-layer link: the first batch-norm reduction of layer i rides in the data-gradient GEMM of layer i+1.
+# When the output z of a dense+BN(+ReLU) layer is consumed by exactly one other such layer, the gradient dz reaching the
+# batch norm is the dX of that consumer's data-gradient GEMM.  pn2_linear_dgrad_bn_grad_stats forms the two per-channel
+# sums of the batch-norm gradient (sum g, sum g * xhat) from its accumulator tiles, so the producer's backward skips the
+# reduction pass over (dz, y) (pn2_bn_relu_backward_mode, BN_WS_SUMMED).  The link is keyed by the storage address of z and checked
+# again in the backward: only when the tensor arriving as dz IS the linked GEMM's output (a second consumer makes autograd
+# hand over a sum in a new tensor) is the shortcut taken.
+USE_DGRAD_BN_STATS = True
+# deferred normalisation: layer i publishes (scale, shift) and hands its PRE-normalisation output y to layer i+1
+# (pn2_bn_relu_forward_deferred); layer i+1's forward GEMM and weight gradient apply relu(fma(y, scale, shift)) while they
+# load y (pn2_linear_bn_stats_xf, pn2_linear_wgrad_accumulate_xf): the normalised activation is never written or re-read.
+# Decided by the module code (conv2d(..., defer_bn=True)) for layers whose output feeds exactly the next conv2d of the stack.
+USE_BN_ON_LOAD = True
+# batch-norm gradient applied on load (round 6): the gradient dy LEAVING a layer's batch norm is only ever read by that
+# layer's own data and weight gradient GEMMs, so it is not written: pn2_bn_grad_constants folds the two reduction sums into six
+# per-channel constants (+ dgamma, dbeta) and pn2_linear_dgrad_gx / pn2_linear_wgrad_gx form dy from (y, dz) while they load
+# their operand -- bn_grad_apply_kernel's pass (read dz, y; write dy) and the two re-reads of dy are gone, and behind the fused
+# max pool the (rows, c) gradient never exists at all.  Same float expressions as the materialised form: both hand the GEMMs the
+# same bits (tests/test_train_gpu.py::test_bn_grad_on_load_equals_the_materialised_form).
+USE_BN_GRAD_ON_LOAD = True
+# behind the fused max pool the first backward reduction is taken from the pooled tensors (rows / 32 entries per channel: the
+# gradient is non-zero only on the rows attaining a maximum) instead of a pass over y (A/B, tests)
+USE_POOLED_BN_REDUCE = True
+USE_FUSED_BWD_NARROW = True  # 32 / 64-channel layers: data and weight gradient in one launch, (y, dz) read once (A/B, tests)
+USE_SA_FIRST_LAYER_FUSED = True  # SA module, few point channels: front end + first conv + statistics in one launch (A/B, tests)
+USE_HOISTED_TRAIN = True  # first layer of SA2-SA4 / FP4 with its feature half applied to the source rows (A/B, tests)
+# (FP1-FP3, whose skip link is a wide SA feature tensor that needs a GEMM of its own, keep the concatenated form: the hoisted
+# variant was built and measured slower -- 4.13 vs 4.05 ms per step, DESIGN.md section 9 -- and removed in round 4.)
+USE_HOIST_BN_STATS = True  # ... and its batch statistics (+ fold + constants) taken by the launch that writes it (A/B, tests)
+# (from 32768 rows on: below, the epilogue's tail -- 2 * cout fp64 atomics per workgroup, the ticket, the fold of 64 slot copies
+#  by one workgroup -- costs more than the statistics pass it replaces: 8192 x 256: 19 vs 15 us, tools/hoist_stats_ab.py)
+HOIST_BN_STATS_MIN_ROWS = 32768
+USE_HOISTED_MSG_TRAIN = True  # pointnet_sa_module_msg(geometry=...) in training: all scales' first layers hoisted together (A/B, tests)
+MSG_HOIST_MAX_SCALES = 4      # scales one pn2_sa_hoist_rows_multi_bn / pn2_scatter_plan_apply_multi launch takes
+
+
+def _bn_scratch(c, device, zeroed=False):
+    """batch-norm accumulators (pn2_bn_workspace_bytes(c) bytes) and their state (BN_WS_*): a slice of the step's zero arena when
+    there is one; else a fresh zero fill (zeroed: for a launch that adds to them) or uncleared memory"""
+    nbytes = lib.pn2_bn_workspace_bytes(c)
+    arena = get_default_store().zero_arena
+    v = arena.take(nbytes) if arena is not None else None
+    if v is not None:
+        return v, BN_WS_ZEROED
+    if zeroed:
+        return torch.zeros(nbytes // 8, dtype=torch.float64, device=device), BN_WS_ZEROED
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device), BN_WS_UNCLEARED
+
+
+def _bn_consts_out(c, device):
+    """uninitialised (save_mean, save_invstd, scale, shift) for a launch that publishes a deferred batch norm's constants"""
+    save_mean = torch.empty(c, dtype=torch.float32, device=device)
+    return save_mean, torch.empty_like(save_mean), torch.empty_like(save_mean), torch.empty_like(save_mean)
+
+
+def _matmul_bn_stats(entry, x2d, w, ws, *tail):
+    """y = x2d @ w on one of the pn2_linear_bn_stats* entry points: they share the argument head (rows, cin, cout, x, w, y, ws,
+    bytes of ws) and differ in `tail`"""
     require_cuda(x2d, w)
     rows, cin = x2d.shape
     cout = w.shape[1]
     y = torch.empty((rows, cout), dtype=torch.float32, device=x2d.device)
-    launch("pn2_linear_bn_stats", x2d, rows, cin, cout, ptr(x2d.contiguous()), ptr(w.contiguous()), ptr(y), ptr(ws), nbytes(ws))
+    launch(entry, x2d, rows, cin, cout, ptr(x2d.contiguous()), ptr(w.contiguous()), ptr(y), ptr(ws), nbytes(ws), *tail)
     return y
+
+
+def hip_matmul_bn_stats(x2d, w, ws):
+    """y = x2d @ w on pn2_linear_bn_stats: the GEMM also leaves the column sums of y and y^2 in the ZEROED batch-norm
+    workspace `ws` (pn2_bn_workspace_bytes(cout) bytes), which is then BN_WS_SUMMED.  cout % 32 == 0."""
+    return _matmul_bn_stats("pn2_linear_bn_stats", x2d, w, ws)
 
 
 def hip_matmul_bn_stats_xf(x_raw, w, ws, sc, sh, relu):
     """hip_matmul_bn_stats on relu?(fma(x_raw, sc, sh)) formed while the operand is staged (pn2_linear_bn_stats_xf)"""
-    require_cuda(x_raw, w)
-    rows, cin = x_raw.shape
-    cout = w.shape[1]
-    y = torch.empty((rows, cout), dtype=torch.float32, device=x_raw.device)
-    launch("pn2_linear_bn_stats_xf", x_raw, rows, cin, cout, ptr(x_raw.contiguous()), ptr(w.contiguous()), ptr(y), ptr(ws), nbytes(ws),
-           ptr(sc), ptr(sh), int(relu))
-    return y
+    return _matmul_bn_stats("pn2_linear_bn_stats_xf", x_raw, w, ws, ptr(sc), ptr(sh), int(relu))
+
+
+def hip_matmul_bn_stats_fin(x2d, w, ws, xf, finish, gamma=None, beta=None, b=None, decay=0.0, running_mean=None, running_var=None):
+    """hip_matmul_bn_stats (xf None) / hip_matmul_bn_stats_xf (xf = (scale, shift, relu)) whose last workgroup also folds the
+    statistics (finish 1) or folds them and publishes the deferred batch norm's constants (finish 2, pn2_linear_bn_stats_fin).
+    -> y, (save_mean, save_invstd, scale, shift) or None"""
+    consts = _bn_consts_out(w.shape[1], x2d.device) if finish == 2 else None
+    sc, sh, xrelu = xf if xf is not None else (None, None, 0)
+    y = _matmul_bn_stats("pn2_linear_bn_stats_fin", x2d, w, ws, ptr(sc), ptr(sh), int(xrelu), int(finish), ptr(gamma), ptr(beta),
+                         ptr(b), BN_EPSILON, float(decay), ptr(running_mean), ptr(running_var),
+                         *map(ptr, consts or (None, None, None, None)))
+    return y, consts
 
 
 def hip_linear_dgrad(dy, w):
@@ -536,55 +611,6 @@ def hip_linear_dgrad(dy, w):
     dx = torch.empty((rows, cin), dtype=torch.float32, device=dy.device)
     launch("pn2_linear_dgrad", dy, rows, cin, cout, ptr(dy), ptr(w.contiguous()), ptr(dx))
     return dx
-
-
-def _bn_scratch(c, device):
-    """batch-norm accumulators and their state (BN_WS_*): a slice of the step's zero arena when there is one, else uncleared memory"""
-    nbytes = lib.pn2_bn_workspace_bytes(c)
-    arena = get_default_store().zero_arena
-    v = arena.take(nbytes) if arena is not None else None
-    if v is not None:
-        return v, BN_WS_ZEROED
-    return torch.empty(nbytes // 8, dtype=torch.float64, device=device), BN_WS_UNCLEARED
-
-
-USE_GEMM_BN_STATS = True  # batch statistics from the forward GEMM's epilogue (set False: separate pass over y; tests / A-B)
-# The one-block launches that used to follow every producer of batch-norm sums (fold the slot copies; derive scale / shift resp. the
-# gradient constants) are done by the producer's LAST WORKGROUP (csrc/pn2_common.h pn2_bn_finish): a layer inside a stack is one
-# launch forward (GEMM + statistics + constants) and two backward (data gradient + finish of the layer below; weight gradient).
-# False: the separate launches (A/B, tests).
-USE_BN_FINISH_IN_PRODUCER = True
-
-
-def _bn_consts_out(c, device):
-    """uninitialised (save_mean, save_invstd, scale, shift) for a launch that publishes a deferred batch norm's constants"""
-    save_mean = torch.empty(c, dtype=torch.float32, device=device)
-    return save_mean, torch.empty_like(save_mean), torch.empty_like(save_mean), torch.empty_like(save_mean)
-
-
-def hip_matmul_bn_stats_fin(x2d, w, ws, xf, finish, gamma=None, beta=None, b=None, decay=0.0, running_mean=None, running_var=None):
-    """hip_matmul_bn_stats (xf None) / hip_matmul_bn_stats_xf (xf = (scale, shift, relu)) whose last workgroup also folds the
-    statistics (finish 1) or folds them and publishes the deferred batch norm's constants (finish 2, pn2_linear_bn_stats_fin).
-    -> y, (save_mean, save_invstd, scale, shift) or None"""
-    require_cuda(x2d, w)
-    rows, cin = x2d.shape
-    cout = w.shape[1]
-    y = torch.empty((rows, cout), dtype=torch.float32, device=x2d.device)
-    consts = _bn_consts_out(cout, x2d.device) if finish == 2 else None
-    sc, sh, xrelu = xf if xf is not None else (None, None, 0)
-    cs = consts if consts is not None else (None, None, None, None)
-    launch("pn2_linear_bn_stats_fin", x2d, rows, cin, cout, ptr(x2d.contiguous()), ptr(w.contiguous()), ptr(y), ptr(ws), nbytes(ws),
-           ptr(sc), ptr(sh), int(xrelu), int(finish), ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, float(decay), ptr(running_mean),
-           ptr(running_var), ptr(cs[0]), ptr(cs[1]), ptr(cs[2]), ptr(cs[3]))
-    return y, consts
-
-
-def _bn_zeroed_scratch(c, device):
-    """zero-filled batch-norm accumulators for pn2_linear_bn_stats: a slice of the step's zero arena, else a fresh fill"""
-    nbytes = lib.pn2_bn_workspace_bytes(c)
-    arena = get_default_store().zero_arena
-    v = arena.take(nbytes) if arena is not None else None
-    return v if v is not None else torch.zeros(nbytes // 8, dtype=torch.float64, device=device)
 
 
 def _wgrad_out(w, fresh=True):
@@ -630,6 +656,19 @@ def _ones_column(rows, device):
     return t
 
 
+def _dense_grads(ctx, x2d, w, dy, b_like):
+    """(dx, dw, db) of y = x2d @ w (+ b) from dy, as far as ctx.needs_input_grad asks: dX on pn2_linear_dgrad, dW = x2d^T @ dY and
+    db = 1^T @ dY (a column sum) on pn2_linear_wgrad.  b_like: (1, cout), what the bias gradient is shaped (and, for a
+    parameter's own storage, placed) like; None: a fresh tile."""
+    dx = hip_linear_dgrad(dy, w) if ctx.needs_input_grad[0] else None
+    dw = _hip_wgrad(x2d, dy, w) if ctx.needs_input_grad[1] else None
+    db = None
+    if ctx.has_bias and ctx.needs_input_grad[2]:
+        b_like = b_like if b_like is not None else dy.new_empty((1, dy.shape[1]))
+        db = _hip_wgrad(_ones_column(dy.shape[0], dy.device), dy, b_like).reshape(-1)
+    return dx, dw, db
+
+
 class _TrainMatmul(torch.autograd.Function):
     """y = x2d @ w (+ b) for the training path's un-normalised layers (the class head); backward: dX on
     pn2_linear_dgrad, dW = x2d^T @ dY on pn2_linear_wgrad (the reduction over all rows, ~8x faster than the library
@@ -649,17 +688,7 @@ class _TrainMatmul(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2d, w = ctx.saved_tensors[:2]
-        dy = dy.contiguous()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = hip_linear_dgrad(dy, w)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = _hip_wgrad(x2d, dy, w)
-        db = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = _hip_wgrad(_ones_column(dy.shape[0], dy.device), dy, ctx.saved_tensors[2].view(1, -1)).reshape(-1)
-        return dx, dw, db
+        return _dense_grads(ctx, x2d, w, dy.contiguous(), ctx.saved_tensors[2].view(1, -1) if ctx.has_bias else None)
 
 
 class _TrainDenseRelu(torch.autograd.Function):
@@ -686,12 +715,7 @@ class _TrainDenseRelu(torch.autograd.Function):
         dz = dz.contiguous()
         dy = torch.empty_like(dz)
         launch("pn2_relu_grad", dz, dz.numel(), ptr(z), ptr(dz), ptr(dy))
-        dx = hip_linear_dgrad(dy, w) if ctx.needs_input_grad[0] else None
-        dw = _hip_wgrad(x2d, dy, w) if ctx.needs_input_grad[1] else None
-        db = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = _hip_wgrad(_ones_column(dy.shape[0], dy.device), dy, dy.new_empty((1, dy.shape[1]))).reshape(-1)
-        return dx, dw, db
+        return _dense_grads(ctx, x2d, w, dy, None)
 
 
 def _train_dense(inputs, w2d, b, relu=False):
@@ -705,14 +729,7 @@ def _train_dense(inputs, w2d, b, relu=False):
     return y.reshape(list(inputs.shape[:-1]) + [cout])
 
 
-# ---- cross-layer link: the first batch-norm reduction of layer i rides in the data-gradient GEMM of layer i+1 -----------
-# When the output z of a dense+BN(+ReLU) layer is consumed by exactly one other such layer, the gradient dz reaching the
-# batch norm is the dX of that consumer's data-gradient GEMM.  pn2_linear_dgrad_bn_grad_stats forms the two per-channel
-# sums of the batch-norm gradient (sum g, sum g * xhat) from its accumulator tiles, so the producer's backward skips the
-# reduction pass over (dz, y) (pn2_bn_relu_backward_mode, BN_WS_SUMMED).  The link is keyed by the storage address of z and checked
-# again in the backward: only when the tensor arriving as dz IS the linked GEMM's output (a second consumer makes autograd
-# hand over a sum in a new tensor) is the shortcut taken.
-USE_DGRAD_BN_STATS = True
+# ---- cross-layer link (USE_DGRAD_BN_STATS, USE_BN_ON_LOAD) ---------------------------------------------------------------
 # Registry of the producer records, keyed by the storage address of the producer's output.  WEAK values: the record is owned by
 # the producer's autograd context (ctx.link), so it lives exactly as long as that node of the tape -- a forward pass whose tape
 # is dropped (or never built) leaves nothing behind, and an address reused by a later tensor finds no stale record.
@@ -720,15 +737,33 @@ _bn_links = weakref.WeakValueDictionary()
 
 
 class _BnLink:
-    __slots__ = ("shape", "y", "gamma", "beta", "mean", "invstd", "relu", "ws", "dz_ptr", "dz_keep", "sc", "sh", "consumed",
-                 "gx", "ws_state", "coef", "dgamma", "dbeta", "__weakref__")
+    """What an un-pooled dense+BN layer leaves for the layer that consumes its output, in three stages."""
+    __slots__ = ("shape", "y", "gamma", "beta", "mean", "invstd", "relu", "sc", "sh", "gx",  # the forward record
+                 "consumed",                                   # a following layer's forward has applied (sc, sh) on load
+                 "ws", "ws_state", "dz_ptr", "dz_keep",        # notes of the consumer's data-gradient GEMM: this layer's two sums
+                 "coef", "dgamma", "dbeta",                    # ... and, finish kind 3, the gradient constants it published
+                 "__weakref__")
 
+    def __init__(self, shape, y, gamma, beta, mean, invstd, relu, sc=None, sh=None, gx=False):
+        """sc / sh: the layer deferred its normalisation, its output IS y.  gx: its backward forms the batch-norm gradient on load --
+        the consumer's data-gradient GEMM may then publish the gradient constants itself"""
+        self.shape, self.y, self.gamma, self.beta, self.mean, self.invstd = tuple(shape), y, gamma, beta, mean, invstd
+        self.relu, self.sc, self.sh, self.gx, self.consumed = bool(relu), sc, sh, bool(gx), False
+        self.ws = self.ws_state = self.dz_ptr = self.dz_keep = self.coef = self.dgamma = self.dbeta = None
 
-# ---- deferred normalisation: layer i publishes (scale, shift) and hands its PRE-normalisation output y to layer i+1 -------
-# (pn2_bn_relu_forward_deferred); layer i+1's forward GEMM and weight gradient apply relu(fma(y, scale, shift)) while they
-# load y (pn2_linear_bn_stats_xf, pn2_linear_wgrad_accumulate_xf): the normalised activation is never written or re-read.
-# Decided by the module code (conv2d(..., defer_bn=True)) for layers whose output feeds exactly the next conv2d of the stack.
-USE_BN_ON_LOAD = True
+    def note(self, **left):
+        """what a consumer's launch has left for this layer's backward, written once the launch has been accepted"""
+        for k, v in left.items():
+            setattr(self, k, v)
+
+    def spend(self):
+        """this layer's backward runs once: refuse a deferred output that no following conv2d consumed, then drop what the record
+        kept alive"""
+        if self.sc is not None and not self.consumed:
+            # the un-normalised output went somewhere else than into the next dense layer: whatever read it saw wrong values
+            raise RuntimeError("a deferred batch-norm output (conv2d(..., defer_bn=True)) was not consumed by a following conv2d")
+        self.y = self.gamma = self.beta = self.mean = self.invstd = self.sc = self.sh = None
+        self.ws = self.ws_state = self.dz_ptr = self.dz_keep = self.coef = self.dgamma = self.dbeta = None
 
 
 def can_defer_bn(rows, c, c_next):
@@ -765,11 +800,10 @@ def hip_linear_dgrad_linked(dy, w, link):
     if USE_BN_FINISH_IN_PRODUCER and w.shape[1] > 16:
         return _hip_dgrad_fin(dy.contiguous(), None, w, link)
     rows, cin = dy.shape[0], w.shape[0]
-    pws = _bn_zeroed_scratch(cin, dy.device)
     dx = torch.empty((rows, cin), dtype=torch.float32, device=dy.device)
-    launch("pn2_linear_dgrad_bn_grad_stats", dy, rows, cin, w.shape[1], ptr(dy), ptr(w.contiguous()), ptr(dx), ptr(link.y),
-           ptr(link.gamma), ptr(link.beta), ptr(link.mean), ptr(link.invstd), int(link.relu), ptr(pws), nbytes(pws))
-    link.ws, link.ws_state, link.dz_ptr, link.dz_keep = pws, BN_WS_SUMMED, dx.data_ptr(), dx
+    below, _, notes = _below_args(link, rows, cin, dx, fin=False)
+    launch("pn2_linear_dgrad_bn_grad_stats", dy, rows, cin, w.shape[1], ptr(dy), ptr(w.contiguous()), ptr(dx), *below)
+    link.note(**notes)
     return dx
 
 
@@ -804,27 +838,44 @@ def _stats_done(state):
 def _bn_train_forward_deferred(y, b, gamma, beta, running_mean, running_var, decay, stats=None):
     """the statistics half of _bn_train_forward only (pn2_bn_relu_forward_deferred) -> save_mean, save_invstd, scale, shift"""
     rows, c = y.shape
-    ws, state = stats if stats is not None else (_bn_zeroed_scratch(c, y.device), BN_WS_ZEROED)
+    ws, state = stats if stats is not None else _bn_scratch(c, y.device, zeroed=True)
     consts = _bn_consts_out(c, y.device)
     launch("pn2_bn_relu_forward_deferred", y, rows, c, ptr(y), ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, decay,
            _stats_done(state), ptr(running_mean), ptr(running_var), ptr(ws), nbytes(ws), *map(ptr, consts))
     return consts
 
 
-def _bn_register_producer(z, y, gamma, beta, save_mean, save_invstd, relu, pooled, sc=None, sh=None, gx=False):
-    """record an un-pooled dense+BN layer as the possible producer of the next layer's input (see _BnLink) -> link or None;
-    sc / sh: the layer deferred its normalisation, z IS y"""
-    if not USE_DGRAD_BN_STATS or pooled:
-        return None
-    lk = _BnLink()
-    lk.shape, lk.y, lk.gamma, lk.beta, lk.mean, lk.invstd, lk.relu = tuple(z.shape), y, gamma, beta, save_mean, save_invstd, bool(relu)
-    lk.ws = lk.ws_state = lk.dz_ptr = lk.dz_keep = None
-    lk.sc, lk.sh, lk.consumed = sc, sh, False
-    # gx: this layer's backward forms its batch-norm gradient on load -- the consumer's data-gradient GEMM may then publish the
-    # gradient constants itself (finish kind 3); coef / dgamma / dbeta: what that GEMM's last workgroup has left
-    lk.gx, lk.coef, lk.dgamma, lk.dbeta = bool(gx), None, None, None
-    _bn_links[z.data_ptr()] = lk
-    return lk
+def _bn_tail(y, bn, relu, pool, defer, stats=None, consts=None, gx=False):
+    """The batch-norm tail of a training forward, shared by the three Functions below.  y (rows, c): the layer's GEMM output;
+    bn = (b, gamma, beta, running_mean, running_var, decay); stats: (workspace, BN_WS_* state) when the producer of y has left
+    the column sums; consts: (save_mean, save_invstd, scale, shift) when it has published a deferred batch norm's constants too.
+    defer: publish (scale, shift) and hand y over UN-normalised -- only the next dense layer of the stack may consume it, and the
+    record is what tells that layer what it reads; else normalise (+ ReLU, + max over groups of `pool` rows).  An un-pooled layer
+    is recorded as the possible producer of the next layer's input (_BnLink).
+    -> output, record or None, what backward needs: always the _BN_SAVED entries (y, gamma, beta, save_mean, save_invstd, zmax,
+    ties) -- zmax / ties None unless pooled -- to be saved in this order (_bn_saved reads them back)."""
+    gamma, beta = bn[1], bn[2]
+    if defer:
+        save_mean, save_invstd, sc, sh = consts if consts is not None else _bn_train_forward_deferred(y, *bn, stats)
+        out, ties = y, None
+    else:
+        out, ties, save_mean, save_invstd = _bn_train_forward(y, *bn, relu, pool, stats)
+        sc = sh = None
+    link = None
+    if USE_DGRAD_BN_STATS and not pool > 1:
+        link = _bn_links[out.data_ptr()] = _BnLink(out.shape, y, gamma, beta, save_mean, save_invstd, relu, sc, sh, gx)
+    if defer and link is None:
+        raise RuntimeError("deferred batch norm needs the producer links (USE_DGRAD_BN_STATS)")
+    return out, link, (y, gamma, beta, save_mean, save_invstd, out if pool > 1 else None, ties)
+
+
+_BN_SAVED = 7
+
+
+def _bn_saved(saved, at):
+    """the _BN_SAVED entries of ctx.saved_tensors from position `at` on, where a forward saved _bn_tail's third result
+    -> (y, gamma, beta, save_mean, save_invstd, zmax, ties)"""
+    return saved[at:at + _BN_SAVED]
 
 
 def _param_grad_out(p):
@@ -833,52 +884,45 @@ def _param_grad_out(p):
     return gv if gv is not None else torch.empty_like(p)
 
 
-def _bn_link_spend(lk):
-    """a layer's backward runs once: refuse a deferred output that no following conv2d consumed, then drop what its producer
-    record (lk, may be None) kept alive"""
-    if lk is None:
-        return
-    if lk.sc is not None and not lk.consumed:
-        # the un-normalised output went somewhere else than into the next dense layer: whatever read it saw wrong values
-        raise RuntimeError("a deferred batch-norm output (conv2d(..., defer_bn=True)) was not consumed by a following conv2d")
-    lk.ws = lk.ws_state = lk.dz_keep = lk.dz_ptr = lk.y = lk.gamma = lk.beta = lk.mean = lk.invstd = lk.sc = lk.sh = None
-    lk.coef = lk.dgamma = lk.dbeta = None
+def _link_sums(lk, dz, y):
+    """(workspace, BN_WS_* state) holding the two gradient sums of the batch norm recorded in lk -- SUMMED, or FOLDED by the
+    consumer's data-gradient GEMM (pn2_linear_dgrad_fin) -- when that GEMM has left them AND dz is its output (a second consumer
+    makes autograd hand over a sum in a new tensor); else None: the backward reduces (dz, y) itself"""
+    if lk is not None and lk.ws is not None and lk.dz_ptr == dz.data_ptr() and dz.shape == y.shape:
+        return lk.ws, lk.ws_state
+    return None
+
+
+def _split_ties(ties, zmax):
+    """what the pooled forward saved as `ties` -> (tie counts, ysel or None): _bn_train_forward stacks [tie counts | ysel]"""
+    if ties is not None and ties.dim() == zmax.dim() + 1:
+        return ties[0], ties[1]
+    return ties, None
 
 
 def _bn_train_backward(dz, y, gamma, beta, save_mean, save_invstd, relu, pool, zmax, ties, lk):
     """gradient of _bn_train_forward on pn2_bn_relu_backward_mode -> dy (rows, c), dgamma, dbeta.  lk: this layer's producer
-    record; when the consumer's data-gradient GEMM has already left the two reduction sums there (and dz is that GEMM's
-    output), the reduction pass is skipped."""
+    record (or None); with _link_sums the reduction pass is skipped."""
     rows, c = y.shape
     dz = dz.contiguous()
     dy = torch.empty_like(y)
     dgamma, dbeta = _param_grad_out(gamma), _param_grad_out(beta)
-    if lk is not None and lk.ws is not None and lk.dz_ptr == dz.data_ptr() and dz.shape == y.shape:
-        ws, state = lk.ws, lk.ws_state  # SUMMED, or FOLDED by the consumer's data-gradient GEMM (pn2_linear_dgrad_fin)
-    else:
-        ws, state = _bn_scratch(c, y.device)
-    _bn_link_spend(lk)
-    if ties is not None and ties.dim() == zmax.dim() + 1:
-        ties = ties[0]  # [tie counts | ysel] of _bn_train_forward
+    ws, state = _link_sums(lk, dz, y) or _bn_scratch(c, y.device)
+    if lk is not None:
+        lk.spend()
     launch("pn2_bn_relu_backward_mode", y, rows, c, ptr(dz), ptr(y), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), int(relu),
-           int(pool), ptr(zmax), ptr(ties), ptr(ws), nbytes(ws), state, ptr(dy), ptr(dgamma), ptr(dbeta))
+           int(pool), ptr(zmax), ptr(_split_ties(ties, zmax)[0]), ptr(ws), nbytes(ws), state, ptr(dy), ptr(dgamma), ptr(dbeta))
     return dy, dgamma, dbeta
 
 
-# ---- batch-norm gradient applied on load (round 6): the gradient dy LEAVING a layer's batch norm is only ever read by that
-# layer's own data and weight gradient GEMMs, so it is not written: pn2_bn_grad_constants folds the two reduction sums into six
-# per-channel constants (+ dgamma, dbeta) and pn2_linear_dgrad_gx / pn2_linear_wgrad_gx form dy from (y, dz) while they load
-# their operand -- bn_grad_apply_kernel's pass (read dz, y; write dy) and the two re-reads of dy are gone, and behind the fused
-# max pool the (rows, c) gradient never exists at all.  Same float expressions as the materialised form: both hand the GEMMs the
-# same bits (tests/test_train_gpu.py::test_bn_grad_on_load_equals_the_materialised_form).
-USE_BN_GRAD_ON_LOAD = True
-# behind the fused max pool the first backward reduction is taken from the pooled tensors (rows / 32 entries per channel: the
-# gradient is non-zero only on the rows attaining a maximum) instead of a pass over y (A/B, tests)
-USE_POOLED_BN_REDUCE = True
+def _gx_shape_ok(c, pool):
+    """can the batch-norm gradient of a layer of width c, pooled over groups of `pool` rows (0: not pooled), be formed on load
+    (USE_BN_GRAD_ON_LOAD)?  The part known in the forward; _gx_usable adds what only the backward sees."""
+    return bool(USE_BN_GRAD_ON_LOAD and c % 4 == 0 and 16 < c <= 512 and pool in (0, 32))
 
 
 def _gx_usable(rows, c, pool, dz, y):
-    return bool(USE_BN_GRAD_ON_LOAD and c % 4 == 0 and 16 < c <= 512 and pool in (0, 32) and (not pool or rows % 32 == 0)
+    return bool(_gx_shape_ok(c, pool) and (not pool or rows % 32 == 0)
                 and dz.dtype == torch.float32 and dz.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0)
 
 
@@ -886,23 +930,20 @@ def _bn_grad_constants(dz, y, gamma, beta, save_mean, save_invstd, relu, pool, z
     """first half of the on-load batch-norm gradient (pn2_bn_grad_constants) -> coef (6, c), dgamma, dbeta.  lk as in
     _bn_train_backward: the reduction pass is skipped when the consumer's data-gradient GEMM has already left the sums."""
     rows, c = y.shape
-    ready = None
-    if lk is not None and lk.ws is not None and lk.dz_ptr == dz.data_ptr() and dz.shape == y.shape:
-        ws, state = lk.ws, lk.ws_state
-        if lk.coef is not None:  # the consumer's data-gradient GEMM has published them already (finish kind 3)
-            ready = (lk.coef, lk.dgamma, lk.dbeta)
-    else:
-        ws, state = _bn_zeroed_scratch(c, y.device), BN_WS_ZEROED
-    _bn_link_spend(lk)
+    sums = _link_sums(lk, dz, y)
+    # ... or even published the constants (finish kind 3)
+    ready = (lk.coef, lk.dgamma, lk.dbeta) if (sums is not None and lk.coef is not None) else None
+    ws, state = sums or _bn_scratch(c, y.device, zeroed=True)
+    if lk is not None:
+        lk.spend()
     if ready is not None:
         return ready
     coef = torch.empty((6, c), dtype=torch.float32, device=y.device)
     dgamma, dbeta = _param_grad_out(gamma), _param_grad_out(beta)
-    ysel = None
-    if ties is not None and ties.dim() == zmax.dim() + 1:
-        ties, ysel = ties[0], (ties[1] if USE_POOLED_BN_REDUCE else None)
+    ties, ysel = _split_ties(ties, zmax)
     launch("pn2_bn_grad_constants", y, rows, c, ptr(dz), ptr(y), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), int(relu),
-           int(pool), ptr(zmax), ptr(ties), ptr(ysel), _stats_done(state), ptr(ws), nbytes(ws), ptr(coef), ptr(dgamma), ptr(dbeta))
+           int(pool), ptr(zmax), ptr(ties), ptr(ysel if USE_POOLED_BN_REDUCE else None), _stats_done(state), ptr(ws), nbytes(ws),
+           ptr(coef), ptr(dgamma), ptr(dbeta))
     return coef, dgamma, dbeta
 
 
@@ -910,25 +951,19 @@ def _below_args(link, rows, cin, dx, fin):
     """What a data-gradient GEMM with output dx (rows, cin) is handed to serve the layer below (link: its producer record, or
     None): -> below (8 arguments: that layer's batch norm + a zeroed workspace for its two gradient sums), fin_out (4 arguments,
     fin only: what the GEMM's last workgroup does with the sums -- 1 fold them, 3 publish the gradient constants, dgamma and
-    dbeta (link.gx) --), notes: what _note_on_link writes on the record once the launch has been accepted."""
+    dbeta (link.gx) --), notes: what link.note() writes on the record once the launch has been accepted (None without a link)."""
     if link is None:
-        return (None, None, None, None, None, 0, None, 0), (0, None, None, None), {}
-    pws = _bn_zeroed_scratch(cin, dx.device)
+        return (None, None, None, None, None, 0, None, 0), (0, None, None, None), None
+    pws = _bn_scratch(cin, dx.device, zeroed=True)[0]
     below = (ptr(link.y), ptr(link.gamma), ptr(link.beta), ptr(link.mean), ptr(link.invstd), int(link.relu), ptr(pws), nbytes(pws))
     notes = dict(ws=pws, ws_state=BN_WS_FOLDED if fin else BN_WS_SUMMED, dz_ptr=dx.data_ptr(), dz_keep=dx)
     fin_out = (1, None, None, None)
-    if fin:
-        if link.gx and _gx_usable(rows, cin, 0, dx, link.y):
-            coef = torch.empty((6, cin), dtype=torch.float32, device=dx.device)
-            dgamma, dbeta = _param_grad_out(link.gamma), _param_grad_out(link.beta)
-            notes.update(coef=coef, dgamma=dgamma, dbeta=dbeta)
-            fin_out = (3, ptr(coef), ptr(dgamma), ptr(dbeta))
+    if fin and link.gx and _gx_usable(rows, cin, 0, dx, link.y):
+        coef = torch.empty((6, cin), dtype=torch.float32, device=dx.device)
+        dgamma, dbeta = _param_grad_out(link.gamma), _param_grad_out(link.beta)
+        notes.update(coef=coef, dgamma=dgamma, dbeta=dbeta)
+        fin_out = (3, ptr(coef), ptr(dgamma), ptr(dbeta))
     return below, fin_out, notes
-
-
-def _note_on_link(link, notes):
-    for k, v in notes.items():
-        setattr(link, k, v)
 
 
 def _hip_dgrad_fin(dy, gx, w, link):
@@ -946,11 +981,9 @@ def _hip_dgrad_fin(dy, gx, w, link):
     else:
         up = (ptr(dy), None, None, None, 0, 0, None, None)
     launch("pn2_linear_dgrad_fin", ref, rows, cin, w.shape[1], *up, ptr(w.contiguous()), ptr(dx), *below, *fin_out)
-    _note_on_link(link, notes)
+    if link is not None:
+        link.note(**notes)
     return dx
-
-
-USE_FUSED_BWD_NARROW = True  # 32 / 64-channel layers: data and weight gradient in one launch, (y, dz) read once (A/B, tests)
 
 
 def _hip_bwd_fused(x2d, xf, y, dz, coef, relu, pool, zmax, ties, w, link):
@@ -968,7 +1001,8 @@ def _hip_bwd_fused(x2d, xf, y, dz, coef, relu, pool, zmax, ties, w, link):
                 int(relu), int(pool), ptr(zmax), ptr(ties), ptr(w.contiguous()), ptr(dx), ptr(dw), *below, *fin_out, may_refuse=True)
     if not ok:
         return None
-    _note_on_link(link, notes)
+    if link is not None:
+        link.note(**notes)
     return dx, dw
 
 
@@ -982,7 +1016,8 @@ def _hip_dgrad_gx(y, dz, coef, relu, pool, zmax, ties, w, link):
     below, _, notes = _below_args(link, rows, cin, dx, fin=False)
     launch("pn2_linear_dgrad_gx", y, rows, cin, w.shape[1], ptr(y), ptr(dz), ptr(coef), int(relu), int(pool), ptr(zmax), ptr(ties),
            ptr(w.contiguous()), ptr(dx), *below)
-    _note_on_link(link, notes)
+    if link is not None:
+        link.note(**notes)
     return dx
 
 
@@ -995,12 +1030,70 @@ def _hip_wgrad_gx(x2d, xf, y, dz, coef, relu, pool, zmax, ties, w):
     return dw
 
 
+def _backward_grads(ctx, names, **grads):
+    """a backward's return value: one entry per forward argument, None except the gradients given by argument name (names: the
+    forward's leading argument names, in order)"""
+    out = [None] * len(ctx.needs_input_grad)
+    for k, g in grads.items():
+        out[names.index(k)] = g
+    return tuple(out)
+
+
+def _sa_first_layer_bn(front, w, bn, defer):
+    """_dense_bn_gemm's first arm: the first layer of an SA module with few point channels -- gather + centre + concat + product +
+    statistics + their fold / constants in ONE launch (pn2_sa_first_layer_bn); the x2d returned = the grouped input it leaves for
+    the weight gradient"""
+    xyz, new_xyz, points, idx = front
+    b, gamma, beta, running_mean, running_var, decay = bn
+    c = w.shape[1]
+    bsz, n = xyz.shape[0], xyz.shape[1]
+    m, ns = idx.shape[1], idx.shape[2]
+    cpts = points.shape[2]
+    ws = _bn_scratch(c, xyz.device, zeroed=True)[0]
+    y = torch.empty((bsz * m * ns, c), dtype=torch.float32, device=xyz.device)
+    x2d = torch.empty((bsz * m * ns, 3 + cpts), dtype=torch.float32, device=xyz.device)
+    consts = _bn_consts_out(c, xyz.device) if defer else None
+    launch("pn2_sa_first_layer_bn", xyz, bsz, n, m, ns, cpts, c, ptr(xyz), ptr(new_xyz), ptr(points), ptr(idx),
+           ptr(w.contiguous()), ptr(y), ptr(x2d), ptr(ws), nbytes(ws), 2 if defer else 1, ptr(gamma), ptr(beta), ptr(b),
+           BN_EPSILON, float(decay), ptr(running_mean), ptr(running_var), *map(ptr, consts or (None, None, None, None)))
+    return y, x2d, (ws, BN_WS_FOLDED), consts
+
+
+def _dense_bn_gemm(x2d, w, prev, defer, front, bn):
+    """The forward GEMM of a dense+BN layer (_TrainDenseBnRelu).  prev: the producer record of x2d, or None; when that layer
+    deferred its batch norm, x2d is its UN-normalised output and the GEMM applies (scale, shift, relu) while loading it.  defer: this
+    layer defers its own.  front: _sa_first_layer_bn's operands instead of x2d.  bn as in _bn_tail.
+    -> y, x2d, stats = (workspace, BN_WS_* state) once the launch has left the column sums of y there (else None), consts = the
+    deferred batch norm's constants when the launch has published them too (else None)"""
+    if front is not None:
+        return _sa_first_layer_bn(front, w, bn, defer)
+    b, gamma, beta, running_mean, running_var, decay = bn
+    c = w.shape[1]
+    xf = (prev.sc, prev.sh, prev.relu) if (prev is not None and prev.sc is not None) else None
+    gemm_stats = xf is not None or (USE_GEMM_BN_STATS and c % 32 == 0)
+    if gemm_stats and USE_BN_FINISH_IN_PRODUCER:
+        # ONE launch: GEMM (batch norm of the layer below applied on load when it was deferred) + column sums of y + -- in the
+        # launch's last workgroup -- their fold and, for a layer that defers its own batch norm, its constants
+        ws = _bn_scratch(c, x2d.device, zeroed=True)[0]
+        y, consts = hip_matmul_bn_stats_fin(x2d, w, ws, xf, 2 if defer else 1, gamma, beta, b, decay, running_mean, running_var)
+        return y, x2d, (ws, BN_WS_FOLDED), consts
+    if xf is not None:
+        ws = _bn_scratch(c, x2d.device, zeroed=True)[0]
+        return hip_matmul_bn_stats_xf(x2d, w, ws, *xf), x2d, (ws, BN_WS_SUMMED), None
+    if gemm_stats:
+        # the GEMM's epilogue leaves the column sums of y in the batch-norm workspace: no statistics pass over y
+        ws = _bn_scratch(c, x2d.device, zeroed=True)[0]
+        return hip_matmul_bn_stats(x2d, w, ws), x2d, (ws, BN_WS_SUMMED), None
+    return hip_matmul(x2d, w), x2d, None, None
+
+
 class _TrainDenseBnRelu(torch.autograd.Function):
     """relu?(batch_norm(x2d @ w + b)) [-> max over groups of `pool` rows] for the training path, with the
-    normalisation on the HIP library: forward = GEMM -> pn2_bn_relu_forward (fp64 batch moments, normalise + ReLU
+    normalisation on the HIP library: forward = GEMM (_dense_bn_gemm) -> batch norm (_bn_tail: fp64 batch moments, normalise + ReLU
     [+ max pool: the un-pooled activation is never written]; the pre-BN bias only moves the mean, so it is folded into
     the moving average instead of being added); backward = pn2_bn_relu_backward (pool / ReLU masks, dgamma, dbeta, dy)
     -> dX = dY @ w^T, dW on pn2_linear_wgrad.  Replaces nine elementwise / reduction kernels per layer."""
+    _ARGS = ("x2d", "w", "b", "gamma", "beta")
 
     @staticmethod
     def forward(ctx, x2d, w, b, gamma, beta, running_mean, running_var, decay, relu, pool, defer, front=None):
@@ -1014,70 +1107,25 @@ class _TrainDenseBnRelu(torch.autograd.Function):
         #                                    (the callers also drop the request when no tape is being recorded at all)
         if xf and c % 32 != 0:
             raise RuntimeError("a deferred batch-norm output reached a layer that cannot apply it")
-        consts, stats = None, None  # stats: (workspace, BN_WS_* state) once the GEMM has left the column sums of y there
-        if front is not None:
-            # the first layer of an SA module with few point channels: gather + centre + concat + product + statistics + their
-            # fold / constants in ONE launch (pn2_sa_first_layer_bn); x2d = the grouped input it leaves for the weight gradient
-            xyz, new_xyz, points, idx = front
-            bsz, n = xyz.shape[0], xyz.shape[1]
-            m, ns = idx.shape[1], idx.shape[2]
-            cpts = points.shape[2]
-            ws = _bn_zeroed_scratch(c, xyz.device)
-            y = torch.empty((bsz * m * ns, c), dtype=torch.float32, device=xyz.device)
-            x2d = torch.empty((bsz * m * ns, 3 + cpts), dtype=torch.float32, device=xyz.device)
-            if defer:
-                consts = _bn_consts_out(c, xyz.device)
-            cs = consts if consts is not None else (None, None, None, None)
-            launch("pn2_sa_first_layer_bn", xyz, bsz, n, m, ns, cpts, c, ptr(xyz), ptr(new_xyz), ptr(points), ptr(idx),
-                   ptr(w.contiguous()), ptr(y), ptr(x2d), ptr(ws), nbytes(ws), 2 if defer else 1, ptr(gamma), ptr(beta), ptr(b),
-                   BN_EPSILON, float(decay), ptr(running_mean), ptr(running_var), ptr(cs[0]), ptr(cs[1]), ptr(cs[2]), ptr(cs[3]))
-            stats = (ws, BN_WS_FOLDED)
-        elif (xf or (USE_GEMM_BN_STATS and c % 32 == 0)) and USE_BN_FINISH_IN_PRODUCER:
-            # ONE launch: GEMM (batch norm of the layer below applied on load when it was deferred) + column sums of y + -- in the
-            # launch's last workgroup -- their fold and, for a layer that defers its own batch norm, its constants
-            ws = _bn_zeroed_scratch(c, x2d.device)
-            y, consts = hip_matmul_bn_stats_fin(x2d, w, ws, (prev.sc, prev.sh, prev.relu) if xf else None, 2 if defer else 1,
-                                                gamma, beta, b, decay, running_mean, running_var)
-            stats = (ws, BN_WS_FOLDED)
-        elif xf:
-            ws = _bn_zeroed_scratch(c, x2d.device)
-            y = hip_matmul_bn_stats_xf(x2d, w, ws, prev.sc, prev.sh, prev.relu)
-            stats = (ws, BN_WS_SUMMED)
-        elif USE_GEMM_BN_STATS and c % 32 == 0:
-            # the GEMM's epilogue leaves the column sums of y in the batch-norm workspace: no statistics pass over y
-            ws = _bn_zeroed_scratch(c, x2d.device)
-            y = hip_matmul_bn_stats(x2d, w, ws)
-            stats = (ws, BN_WS_SUMMED)
-        else:
-            y = hip_matmul(x2d, w)
+        bn = (b, gamma, beta, running_mean, running_var, decay)
+        y, x2d, stats, consts = _dense_bn_gemm(x2d, w, prev, defer, front, bn)
         if xf:
             prev.consumed = True
         ctx.xf = (prev.sc, prev.sh, bool(prev.relu)) if xf else None
         ctx.relu, ctx.pool = bool(relu), int(pool)
         ctx.prev = prev if (prev is not None and w.shape[1] > 16) else None
-        gx = bool(USE_BN_GRAD_ON_LOAD and c % 4 == 0 and 16 < c <= 512 and not pooled)  # what backward will do (see _gx_usable)
-        if defer:
-            if consts is not None:
-                save_mean, save_invstd, sc, sh = consts
-            else:
-                save_mean, save_invstd, sc, sh = _bn_train_forward_deferred(y, b, gamma, beta, running_mean, running_var, decay, stats)
-            ctx.save_for_backward(x2d, w, y, gamma, beta, save_mean, save_invstd)
-            ctx.link = _bn_register_producer(y, y, gamma, beta, save_mean, save_invstd, relu, False, sc, sh, gx=gx)
-            if ctx.link is None:
-                raise RuntimeError("deferred batch norm needs the producer links (USE_DGRAD_BN_STATS)")
-            return y  # un-normalised: only the next dense layer of the stack may consume it
-        z, ties, save_mean, save_invstd = _bn_train_forward(y, b, gamma, beta, running_mean, running_var, decay, relu, pool, stats)
-        if pooled:
-            ctx.save_for_backward(x2d, w, y, gamma, beta, save_mean, save_invstd, z, ties)
-        else:
-            ctx.save_for_backward(x2d, w, y, gamma, beta, save_mean, save_invstd)
-        ctx.link = _bn_register_producer(z, y, gamma, beta, save_mean, save_invstd, relu, pooled, gx=gx)
-        return z
+        # gx: what backward will do with an un-pooled layer's gradient -- the consumer of this layer's record needs to know
+        out, ctx.link, saved = _bn_tail(y, bn, relu, pool, defer, stats, consts, gx=not pooled and _gx_shape_ok(c, 0))
+        ctx.save_for_backward(x2d, w, *saved)
+        return out
 
     @staticmethod
     def backward(ctx, dz):
-        x2d, w, y, gamma, beta, save_mean, save_invstd = ctx.saved_tensors[:7]
-        zmax, ties = ctx.saved_tensors[7:] if ctx.pool > 1 else (None, None)
+        x2d, w = ctx.saved_tensors[:2]
+        y, gamma, beta, save_mean, save_invstd, zmax, ties = _bn_saved(ctx.saved_tensors, 2)
+        grads = lambda **g: _backward_grads(ctx, _TrainDenseBnRelu._ARGS, **g)  # noqa: E731
+        # (b: a constant in front of batch norm has no effect on the output: its gradient is exactly zero -- None, which the
+        # trainer's gradient buffer treats as (and keeps at) zero without a fill per layer)
         dz = dz.contiguous()
         if _gx_usable(y.shape[0], y.shape[1], ctx.pool, dz, y):
             # the gradient leaving the batch norm is formed by the two GEMMs while they load (y, dz): never written
@@ -1088,25 +1136,29 @@ class _TrainDenseBnRelu(torch.autograd.Function):
             if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
                 both = _hip_bwd_fused(x2d, ctx.xf, y, dz, coef, ctx.relu, ctx.pool, zmax, ties, w, pv)  # narrow layers: one launch
                 if both is not None:
-                    return both[0], both[1], None, dgamma, dbeta, None, None, None, None, None, None, None
+                    return grads(x2d=both[0], w=both[1], gamma=dgamma, beta=dbeta)
             if ctx.needs_input_grad[0]:
                 dx = _hip_dgrad_gx(y, dz, coef, ctx.relu, ctx.pool, zmax, ties, w, pv)
             dw = _hip_wgrad_gx(x2d, ctx.xf, y, dz, coef, ctx.relu, ctx.pool, zmax, ties, w) if ctx.needs_input_grad[1] else None
-            return dx, dw, None, dgamma, dbeta, None, None, None, None, None, None, None
+            return grads(x2d=dx, w=dw, gamma=dgamma, beta=dbeta)
         dy, dgamma, dbeta = _bn_train_backward(dz, y, gamma, beta, save_mean, save_invstd, ctx.relu, ctx.pool, zmax, ties, ctx.link)
         dx = None
         if ctx.needs_input_grad[0]:
             pv = ctx.prev
             dx = hip_linear_dgrad_linked(dy, w, pv) if (pv is not None and pv.y is not None) else hip_linear_dgrad(dy, w)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = _hip_wgrad(x2d, dy, w, ctx.xf)
-        # a constant in front of batch norm has no effect on the output: its gradient is exactly zero -- None, which the
-        # trainer's gradient buffer treats as (and keeps at) zero without a fill per layer
-        return dx, dw, None, dgamma, dbeta, None, None, None, None, None, None, None
+        dw = _hip_wgrad(x2d, dy, w, ctx.xf) if ctx.needs_input_grad[1] else None
+        return grads(x2d=dx, w=dw, gamma=dgamma, beta=dbeta)
 
 
-USE_SA_FIRST_LAYER_FUSED = True  # SA module, few point channels: front end + first conv + statistics in one launch (A/B, tests)
+def _train_variables(scope, cin, cout, bn_decay, pool=0):
+    """The variables of a dense+BN layer called in training under `scope` (names, shapes, initialisation as tf_util.conv2d), in
+    the form the Functions take them -> w (cin, cout), bn = (b, gamma, beta, moving mean, moving variance, decay) as in
+    _bn_tail, pool as 0 or > 1"""
+    with variable_scope(scope):
+        st, w, b, (beta, gamma, mean, var) = _dense_variables(cin, cout, True, (1, 1, cin, cout))
+    st.train_epoch += 1
+    decay = 0.9 if bn_decay is None else float(bn_decay)  # tf_util.py:571
+    return w.reshape(cin, cout), (b, gamma, beta, mean, var, decay), int(pool) if pool and pool > 1 else 0
 
 
 def conv2d_sa_first_small(xyz, new_xyz, points, idx, num_output_channels, scope, bn_decay=None, pool=0, defer_bn=False):
@@ -1115,25 +1167,11 @@ def conv2d_sa_first_small(xyz, new_xyz, points, idx, num_output_channels, scope,
     grouped tensor first: _TrainDenseBnRelu(front=...) on pn2_sa_first_layer_bn.  Same variables as tf_util.conv2d under `scope`.
     -> (b, m, nsample or 1, cout)"""
     cout = int(num_output_channels)
-    cin = 3 + points.shape[2]
-    with variable_scope(scope):
-        st, w, b, bnv = _dense_variables(cin, cout, True, (1, 1, cin, cout))
-        st.train_epoch += 1
-        beta, gamma, mean, var = bnv
-        decay = 0.9 if bn_decay is None else float(bn_decay)
-        pool = int(pool) if pool and pool > 1 else 0
-        front = (xyz.detach().contiguous(), new_xyz.detach().contiguous(), points.detach().contiguous(), idx.contiguous())
-        z = _TrainDenseBnRelu.apply(None, w.reshape(cin, cout), b, gamma, beta, mean, var, decay, True, pool,
-                                    bool(defer_bn) and not pool and torch.is_grad_enabled(), front)
+    w, bn, pool = _train_variables(scope, 3 + points.shape[2], cout, bn_decay, pool)
+    front = (xyz.detach().contiguous(), new_xyz.detach().contiguous(), points.detach().contiguous(), idx.contiguous())
+    z = _TrainDenseBnRelu.apply(None, w, *bn, True, pool, bool(defer_bn) and not pool and torch.is_grad_enabled(), front)
     m, ns = idx.shape[1], idx.shape[2]
     return z.reshape(xyz.shape[0], m, ns // pool if pool else ns, cout)
-
-
-HOIST_BN_STATS_MIN_ROWS = 32768
-USE_HOIST_BN_STATS = True  # ... and its batch statistics (+ fold + constants) taken by the launch that writes it (A/B, tests)
-USE_HOISTED_TRAIN = True  # first layer of SA2-SA4 / FP4 with its feature half applied to the source rows (A/B, tests)
-# (FP1-FP3, whose skip link is a wide SA feature tensor that needs a GEMM of its own, keep the concatenated form: the hoisted
-# variant was built and measured slower -- 4.13 vs 4.05 ms per step, DESIGN.md section 9 -- and removed in round 4.)
 
 
 def _hip_wgrad_into(x2d, dy, dw_rows):
@@ -1146,12 +1184,13 @@ class _TrainHoistedBnRelu(torch.autograd.Function):
     (gather / interpolation are linear and commute with it; csrc/pn2_hoist.hip):
         SA: y = (group_point(xyz, idx) - new_xyz) @ W[:3] + (points @ W[3:])[idx]              (pointnet_util.py:39-54,150-156)
         FP: y = three_interpolate(points2 @ W[:c2], idx, w(dist)) + points1 @ W[c2:]             (pointnet_util.py:300-312)
-    then batch norm + ReLU (+ max pool) as in _TrainDenseBnRelu.  The grouped / concatenated tensor is never built, and the
-    GEMM, its data gradient and its weight gradient run on n (resp. m) rows instead of m * nsample (resp. n).  Backward:
+    then batch norm + ReLU (+ max pool) as in _TrainDenseBnRelu (_bn_tail).  The grouped / concatenated tensor is never built, and
+    the GEMM, its data gradient and its weight gradient run on n (resp. m) rows instead of m * nsample (resp. n).  Backward:
     dy from the batch-norm kernels; dz = the scatter of dy through the precomputed plan (the same list the gradient of
     group_point / three_interpolate uses); d(points) = dz @ Wb^T, dWb = points^T dz on the source rows; dWa = a^T dy with
     a = the centred coordinates (SA) resp. points1 (FP: at most 8 skip-link channels that carry no gradient -- the colours
     of the level-0 module)."""
+    _ARGS = ("src", "w", "b", "gamma", "beta")
 
     @staticmethod
     def forward(ctx, src, w, b, gamma, beta, running_mean, running_var, decay, relu, pool, kind, g0, g1, g2, plan, defer):
@@ -1170,18 +1209,16 @@ class _TrainHoistedBnRelu(torch.autograd.Function):
             rows_b = n
         z = hip_matmul(src2d, wb)  # (b * nsrc, cout)
         y = torch.empty((bsz * rows_b, cout), dtype=torch.float32, device=src.device)
-        pooled = pool > 1
-        defer = defer and any(ctx.needs_input_grad)  # as _TrainDenseBnRelu
+        defer = defer and not pool > 1 and any(ctx.needs_input_grad)  # as _TrainDenseBnRelu
         # the deferred batch norm's statistics (+ their fold and the constants) ride in the launch that writes y
-        # (from 32768 rows on: below, the epilogue's tail -- 2 * cout fp64 atomics per workgroup, the ticket, the fold of 64 slot copies
-        #  by one workgroup -- costs more than the statistics pass it replaces: 8192 x 256: 19 vs 15 us, tools/hoist_stats_ab.py)
-        fused_stats = bool(defer and not pooled and USE_HOIST_BN_STATS and USE_BN_FINISH_IN_PRODUCER and bsz * rows_b >= HOIST_BN_STATS_MIN_ROWS)
-        bn_args = ()
+        # (from HOIST_BN_STATS_MIN_ROWS rows on, see there)
+        fused_stats = bool(defer and USE_HOIST_BN_STATS and USE_BN_FINISH_IN_PRODUCER and bsz * rows_b >= HOIST_BN_STATS_MIN_ROWS)
+        consts, bn_args = None, ()
         if fused_stats:
-            ws = _bn_zeroed_scratch(cout, src.device)
-            save_mean, save_invstd, sc, sh = _bn_consts_out(cout, src.device)
+            ws = _bn_scratch(cout, src.device, zeroed=True)[0]
+            consts = _bn_consts_out(cout, src.device)
             bn_args = (ptr(ws), nbytes(ws), 2, ptr(gamma), ptr(beta), ptr(b), BN_EPSILON, float(decay),
-                       ptr(running_mean), ptr(running_var), ptr(save_mean), ptr(save_invstd), ptr(sc), ptr(sh))
+                       ptr(running_mean), ptr(running_var), *map(ptr, consts))
         if kind == "sa":
             a = torch.empty((bsz * rows_b, 3), dtype=torch.float32, device=src.device)
             launch("pn2_sa_hoist_rows_bn" if fused_stats else "pn2_sa_hoist_rows", src, bsz, nsrc, m, ns, cout, ptr(xyz), ptr(new_xyz),
@@ -1193,23 +1230,14 @@ class _TrainHoistedBnRelu(torch.autograd.Function):
             launch("pn2_fp_hoist_rows_bn" if fused_stats else "pn2_fp_hoist_rows", src, bsz, n, nsrc, c1, cout, ptr(dist), ptr(idx),
                    ptr(a), ptr(z), ptr(wa), ptr(y), *bn_args)
         ctx.relu, ctx.pool, ctx.kind, ctx.dims = bool(relu), int(pool), kind, (bsz, nsrc, rows_b, c)
-        if defer and not pooled:
-            if not fused_stats:
-                save_mean, save_invstd, sc, sh = _bn_train_forward_deferred(y, b, gamma, beta, running_mean, running_var, decay)
-            ctx.save_for_backward(src2d, w, y, gamma, beta, save_mean, save_invstd, a, plan)
-            ctx.link = _bn_register_producer(y, y, gamma, beta, save_mean, save_invstd, relu, False, sc, sh)
-            if ctx.link is None:
-                raise RuntimeError("deferred batch norm needs the producer links (USE_DGRAD_BN_STATS)")
-            return y
-        zact, ties, save_mean, save_invstd = _bn_train_forward(y, b, gamma, beta, running_mean, running_var, decay, relu, pool)
-        ctx.save_for_backward(src2d, w, y, gamma, beta, save_mean, save_invstd, a, plan, *((zact, ties) if pooled else ()))
-        ctx.link = _bn_register_producer(zact, y, gamma, beta, save_mean, save_invstd, relu, pooled)
-        return zact
+        out, ctx.link, saved = _bn_tail(y, (b, gamma, beta, running_mean, running_var, decay), relu, pool, defer, consts=consts)
+        ctx.save_for_backward(src2d, w, a, plan, *saved)
+        return out
 
     @staticmethod
     def backward(ctx, dz):
-        src2d, w, y, gamma, beta, save_mean, save_invstd, a, plan = ctx.saved_tensors[:9]
-        zmax, ties = ctx.saved_tensors[9:] if ctx.pool > 1 else (None, None)
+        src2d, w, a, plan = ctx.saved_tensors[:4]
+        y, gamma, beta, save_mean, save_invstd, zmax, ties = _bn_saved(ctx.saved_tensors, 4)
         bsz, nsrc, rows_b, c = ctx.dims
         cout = w.shape[1]
         dy, dgamma, dbeta = _bn_train_backward(dz, y, gamma, beta, save_mean, save_invstd, ctx.relu, ctx.pool, zmax, ties, ctx.link)
@@ -1225,7 +1253,7 @@ class _TrainHoistedBnRelu(torch.autograd.Function):
             dwa, dwb = (dw[:3], dw[3:]) if sa else (dw[c:], dw[:c])
             _hip_wgrad_into(src2d, dzs2d, dwb)
             _hip_wgrad_into(a, dy, dwa)
-        return (dsrc, dw, None, dgamma, dbeta) + (None,) * 11
+        return _backward_grads(ctx, _TrainHoistedBnRelu._ARGS, src=dsrc, w=dw, gamma=dgamma, beta=dbeta)
 
 
 def conv2d_hoisted_first(kind, src, geo, plan, cin, num_output_channels, scope, bn_decay=None, pool=0, defer_bn=False):
@@ -1235,24 +1263,28 @@ def conv2d_hoisted_first(kind, src, geo, plan, cin, num_output_channels, scope, 
     cin = width of the tensor the reference convolves (3 + c resp. c2 + c1).
     -> (b, m, nsample or nsample/pool, cout) resp. (b, n, 1, cout)."""
     cout = int(num_output_channels)
-    with variable_scope(scope):
-        st, w, b, bnv = _dense_variables(cin, cout, True, (1, 1, cin, cout))
-        st.train_epoch += 1
-        beta, gamma, mean, var = bnv
-        decay = 0.9 if bn_decay is None else float(bn_decay)
-        pool = int(pool) if pool and pool > 1 else 0
-        z = _TrainHoistedBnRelu.apply(src.contiguous(), w.reshape(cin, cout), b, gamma, beta, mean, var, decay, True, pool, kind,
-                                      geo[0].contiguous(), geo[1].contiguous(), geo[2].contiguous(), plan,
-                                      bool(defer_bn) and not pool and torch.is_grad_enabled())
+    w, bn, pool = _train_variables(scope, cin, cout, bn_decay, pool)
+    z = _TrainHoistedBnRelu.apply(src.contiguous(), w, *bn, True, pool, kind, geo[0].contiguous(), geo[1].contiguous(),
+                                  geo[2].contiguous(), plan, bool(defer_bn) and not pool and torch.is_grad_enabled())
     if kind == "sa":
         m, ns = geo[2].shape[1], geo[2].shape[2]
         return z.reshape(src.shape[0], m, ns // pool if pool else ns, cout)
     return z.reshape(src.shape[0], geo[2].shape[1], 1, cout)
 
 
-USE_HOISTED_MSG_TRAIN = True  # pointnet_sa_module_msg(geometry=...) in training: all scales' first layers hoisted together (A/B, tests)
-MSG_HOIST_MAX_SCALES = 4      # scales one pn2_sa_hoist_rows_multi_bn / pn2_scatter_plan_apply_multi launch takes
-_MSG_PER = 8                  # tensors per scale in _TrainHoistedMsgBnRelu's argument list
+# _TrainHoistedMsgBnRelu's argument list: _MSG_HEAD, then one _MsgScale record per scale, flattened (autograd takes tensors as
+# arguments of their own); backward returns one gradient per entry in the same layout
+_MSG_HEAD = ("src", "xyz", "new_xyz", "decay", "pools", "defers")
+_MsgScale = namedtuple("_MsgScale", "w b gamma beta running_mean running_var idx plan", defaults=(None,) * 8)
+
+
+def _msg_pack(scales):
+    return [v for sc in scales for v in sc]
+
+
+def _msg_unpack(per):
+    n = len(_MsgScale._fields)
+    return [_MsgScale(*per[i:i + n]) for i in range(0, len(per), n)]
 
 
 class _TrainHoistedMsgBnRelu(torch.autograd.Function):
@@ -1261,19 +1293,21 @@ class _TrainHoistedMsgBnRelu(torch.autograd.Function):
     against the column-concatenated weights,
         z = points @ [Wf_0 | Wf_1 | ...],     y_s = z[idx_s, its columns] + (group_point(xyz, idx_s) - new_xyz) @ Wx_s
     (one pn2_linear, one pn2_sa_hoist_rows_multi_bn that also takes every scale's batch statistics), then per scale batch norm +
-    ReLU (+ max over K, or deferred) as in _TrainHoistedBnRelu.  The variables keep the reference's [features | xyz] row order
-    (:259): Wf_s = w_s[:C], Wx_s = w_s[C:].  Backward: dy_s from the batch-norm kernels; ONE pn2_scatter_plan_apply_multi into the
-    shared dz (b, n, sum cout); d(points) = dz @ Wf_all^T -- the GEMM's reduction adds the scales' contributions --; ONE weight
+    ReLU (+ max over K, or deferred) as in _TrainHoistedBnRelu (_bn_tail).  The variables keep the reference's [features | xyz] row
+    order (:259): Wf_s = w_s[:C], Wx_s = w_s[C:].  Backward: dy_s from the batch-norm kernels; ONE pn2_scatter_plan_apply_multi into
+    the shared dz (b, n, sum cout); d(points) = dz @ Wf_all^T -- the GEMM's reduction adds the scales' contributions --; ONE weight
     gradient points^T dz whose column blocks are the feature rows of the variables' gradients; dWx_s = gxyz_s^T dy_s.
-    Arguments after `defers`: per scale (w (C + 3, cout), b, gamma, beta, running_mean, running_var, idx, plan).
+    Arguments after `defers`: per scale a _MsgScale (w (C + 3, cout), b, gamma, beta, running_mean, running_var, idx, plan).
     -> one tensor per scale: (b * m * K_s, cout_s), or (b * m, cout_s) behind the fused max (pools[s] = K_s > 1)."""
 
     @staticmethod
     def forward(ctx, src, xyz, new_xyz, decay, pools, defers, *per):
-        nsc = len(pools)
+        scales = _msg_unpack(per)
+        nsc = len(scales)
         bsz, nsrc, c = src.shape
         src2d = src.reshape(-1, c)
-        ws_, bs_, gammas, betas, rms, rvs, idxs, plans = (per[k::_MSG_PER] for k in range(_MSG_PER))
+        col = lambda k: [getattr(sc, k) for sc in scales]  # noqa: E731
+        ws_, idxs = col("w"), col("idx")
         m = idxs[0].shape[1]
         ks = [int(i.shape[2]) for i in idxs]
         couts = [int(w.shape[1]) for w in ws_]
@@ -1287,35 +1321,20 @@ class _TrainHoistedMsgBnRelu(torch.autograd.Function):
         left = BN_WS_FOLDED if fin else BN_WS_SUMMED  # state of a scale's workspace after the launch (finish 1 / 0)
         ys = [torch.empty((bsz * m * k, co), dtype=torch.float32, device=src.device) for k, co in zip(ks, couts)]
         gx = [torch.empty((bsz * m * k, 3), dtype=torch.float32, device=src.device) for k in ks]
-        wss = [_bn_zeroed_scratch(co, src.device) for co in couts]
-        consts = [_bn_consts_out(co, src.device) if f == 2 else (None, None, None, None) for co, f in zip(couts, finish)]
+        wss = [_bn_scratch(co, src.device, zeroed=True)[0] for co in couts]
+        consts = [_bn_consts_out(co, src.device) if f == 2 else None for co, f in zip(couts, finish)]
         wxs = [w[c:] for w in ws_]
         launch("pn2_sa_hoist_rows_multi_bn", src, nsc, bsz, nsrc, m, z.shape[1], ptr(xyz), ptr(new_xyz), ptr(z), int_array(ks),
                int_array(couts), int_array(cols), ptr_table(idxs), ptr_table(wxs), ptr_table(ys), ptr_table(gx), ptr_table(wss),
-               u64_array([nbytes(w_) for w_ in wss]), int_array(finish), ptr_table(gammas), ptr_table(betas), ptr_table(bs_),
-               BN_EPSILON, float(decay), ptr_table(rms), ptr_table(rvs), *(ptr_table([cs[k] for cs in consts]) for k in range(4)))
+               u64_array([nbytes(w_) for w_ in wss]), int_array(finish), ptr_table(col("gamma")), ptr_table(col("beta")),
+               ptr_table(col("b")), BN_EPSILON, float(decay), ptr_table(col("running_mean")), ptr_table(col("running_var")),
+               *(ptr_table([cs[k] if cs else None for cs in consts]) for k in range(4)))
         outs, saved, links = [], [src2d, wf_all], []
-        for s in range(nsc):
-            y, pool = ys[s], int(pools[s])
-            if defers[s]:
-                if finish[s] == 2:
-                    save_mean, save_invstd, sc, sh = consts[s]
-                else:
-                    save_mean, save_invstd, sc, sh = _bn_train_forward_deferred(y, bs_[s], gammas[s], betas[s], rms[s], rvs[s], decay,
-                                                                                (wss[s], left))
-                saved += [ws_[s], y, gammas[s], betas[s], save_mean, save_invstd, gx[s], plans[s]]
-                lk = _bn_register_producer(y, y, gammas[s], betas[s], save_mean, save_invstd, True, False, sc, sh)
-                if lk is None:
-                    raise RuntimeError("deferred batch norm needs the producer links (USE_DGRAD_BN_STATS)")
-                outs.append(y)
-            else:
-                zact, ties, save_mean, save_invstd = _bn_train_forward(y, bs_[s], gammas[s], betas[s], rms[s], rvs[s], decay, True,
-                                                                       pool, (wss[s], left))
-                saved += [ws_[s], y, gammas[s], betas[s], save_mean, save_invstd, gx[s], plans[s]]
-                if pool > 1:
-                    saved += [zact, ties]
-                lk = _bn_register_producer(zact, y, gammas[s], betas[s], save_mean, save_invstd, True, pool > 1)
-                outs.append(zact)
+        for s, sc in enumerate(scales):
+            out, lk, kept = _bn_tail(ys[s], (sc.b, sc.gamma, sc.beta, sc.running_mean, sc.running_var, decay), True, int(pools[s]),
+                                     defers[s], (wss[s], left), consts[s])
+            saved += [sc.w, gx[s], sc.plan, *kept]
+            outs.append(out)
             links.append(lk)
         ctx.save_for_backward(*saved)
         ctx.links, ctx.pools, ctx.dims, ctx.cols = links, [int(p) for p in pools], (bsz, nsrc, m, c), cols
@@ -1326,19 +1345,16 @@ class _TrainHoistedMsgBnRelu(torch.autograd.Function):
         saved = ctx.saved_tensors
         src2d, wf_all = saved[:2]
         bsz, nsrc, m, c = ctx.dims
-        nsc, pos = len(ctx.pools), 2
-        ws_, dys, gxs, plans, out_grads = [], [], [], [], []
+        nsc = len(ctx.pools)
+        ws_, dys, gxs, plans, grads = [], [], [], [], []
         for s in range(nsc):
-            w, y, gamma, beta, save_mean, save_invstd, a, plan = saved[pos:pos + 8]
-            pos += 8
-            zmax, ties = None, None
-            if ctx.pools[s] > 1:
-                zmax, ties = saved[pos:pos + 2]
-                pos += 2
+            at = 2 + s * (3 + _BN_SAVED)
+            w, a, plan = saved[at:at + 3]
+            y, gamma, beta, save_mean, save_invstd, zmax, ties = _bn_saved(saved, at + 3)
             dy, dgamma, dbeta = _bn_train_backward(dzs[s], y, gamma, beta, save_mean, save_invstd, True, ctx.pools[s], zmax, ties,
                                                    ctx.links[s])
             ws_.append(w); dys.append(dy); gxs.append(a); plans.append(plan)
-            out_grads.append([None, None, dgamma, dbeta, None, None, None, None])
+            grads.append(dict(gamma=dgamma, beta=dbeta))
         couts = [int(w.shape[1]) for w in ws_]
         total = wf_all.shape[1]
         dzall = torch.empty((bsz, nsrc, total), dtype=torch.float32, device=src2d.device)
@@ -1347,15 +1363,15 @@ class _TrainHoistedMsgBnRelu(torch.autograd.Function):
                u64_array([p.numel() for p in plans]), ptr(dzall))
         dz2d = dzall.view(-1, total)
         dsrc = hip_linear_dgrad(dz2d, wf_all).view(bsz, nsrc, c) if ctx.needs_input_grad[0] else None
-        if any(ctx.needs_input_grad[6 + _MSG_PER * s] for s in range(nsc)):
+        if any(need.w for need in _msg_unpack(ctx.needs_input_grad[len(_MSG_HEAD):])):
             dwf = torch.empty((c, total), dtype=torch.float32, device=src2d.device)
             launch("pn2_linear_wgrad", dz2d, src2d.shape[0], c, total, ptr(src2d), ptr(dz2d), ptr(dwf))
             for s in range(nsc):
                 dw = _wgrad_out(ws_[s])
                 dw[:c].copy_(dwf[:, ctx.cols[s]:ctx.cols[s] + couts[s]])  # the column block -> the feature rows of the variable's gradient
                 _hip_wgrad_into(gxs[s], dys[s], dw[c:])
-                out_grads[s][0] = dw
-        return (dsrc, None, None, None, None, None) + tuple(g for og in out_grads for g in og)
+                grads[s]["w"] = dw
+        return _backward_grads(ctx, _MSG_HEAD, src=dsrc)[:len(_MSG_HEAD)] + tuple(_msg_pack(_MsgScale(**g) for g in grads))
 
 
 def conv2d_hoisted_first_msg(points, xyz, new_xyz, idxs, plans, num_output_channels, scopes, bn_decay=None, pools=None,
@@ -1369,19 +1385,15 @@ def conv2d_hoisted_first_msg(points, xyz, new_xyz, idxs, plans, num_output_chann
     if not 1 <= nsc <= MSG_HOIST_MAX_SCALES:
         raise ValueError("conv2d_hoisted_first_msg takes 1..%d scales" % MSG_HOIST_MAX_SCALES)
     cin = points.shape[2] + 3
-    decay = 0.9 if bn_decay is None else float(bn_decay)
     pools = [int(p) if p and p > 1 else 0 for p in (pools or [0] * nsc)]
     defers = [bool(d) and not pools[s] and torch.is_grad_enabled() for s, d in enumerate(defer_bn or [False] * nsc)]
-    per = []
+    scales = []
     for s in range(nsc):
-        cout = int(num_output_channels[s])
-        with variable_scope(scopes[s]):
-            st, w, b, bnv = _dense_variables(cin, cout, True, (1, 1, cin, cout))
-            st.train_epoch += 1
-            beta, gamma, mean, var = bnv
-        per += [w.reshape(cin, cout), b, gamma, beta, mean, var, idxs[s].contiguous(), plans[s]]
+        w, bn, _ = _train_variables(scopes[s], cin, int(num_output_channels[s]), bn_decay)
+        scales.append(_MsgScale(w, *bn[:5], idxs[s].contiguous(), plans[s]))
+    decay = bn[5]  # the same for every scale
     outs = _TrainHoistedMsgBnRelu.apply(points.contiguous(), xyz.detach().contiguous(), new_xyz.detach().contiguous(), decay,
-                                        tuple(pools), tuple(defers), *per)
+                                        tuple(pools), tuple(defers), *_msg_pack(scales))
     b, m = points.shape[0], idxs[0].shape[1]
     return [o.reshape(b, m, 1 if pools[s] else idxs[s].shape[2], int(num_output_channels[s])) for s, o in enumerate(outs)]
 
