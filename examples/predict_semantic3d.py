@@ -26,7 +26,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pn2_amd as pn2  # noqa: E402
 
 M = pn2.util.metric
-U = pn2.util.point_cloud_util
 
 
 def synthetic_scene(seed, n, ex, ey):
@@ -41,16 +40,17 @@ def synthetic_scene(seed, n, ex, ey):
 
 
 def load_scenes(args, hp, dev):
-    """-> dataset (the down-sampled store), dense {scene name: (points float32 (nd,3) numpy, labels int32 (nd,) or None)}"""
+    """-> dataset (the down-sampled store), dense {scene name: (points float32 (nd,3), labels int32 (nd,) or None)}: device
+    tensors when read from files (pn2.read_point_cloud_pcd / pn2.load_labels), numpy arrays for the synthetic scenes"""
     N = hp["num_point"]
     if args.data:
         ds = pn2.dataset.SemanticDataset(N, args.set, hp["use_color"], hp["box_size_x"], hp["box_size_y"], args.data, device=dev)
         dense = {}
         for name in ds.scene_names:
             prefix = os.path.join(args.raw or args.data, name)
-            pts, _ = U.read_point_cloud_pcd(prefix + ".pcd")
-            labels = U.load_labels(prefix + ".labels") if os.path.exists(prefix + ".labels") else None
-            dense[name] = (pts.astype(np.float32), labels)
+            pts, _ = pn2.read_point_cloud_pcd(prefix + ".pcd", dev, want_colors=False)
+            labels = pn2.load_labels(prefix + ".labels", dev) if os.path.exists(prefix + ".labels") else None
+            dense[name] = (pts.to(torch.float32), labels)
         return ds, dense
     scenes, dense = [], {}
     for k in range(args.scenes):
@@ -111,8 +111,8 @@ def main():
         dataset.check_last()
         torch.cuda.synchronize()
         print("    %d samples of %d points in %.1f ms" % (args.num_samples, hp["num_point"], (time.perf_counter() - t0) * 1e3))
-        U.write_point_cloud_pcd(os.path.join(sparse_dir, name + ".pcd"), points.cpu().numpy())
-        U.write_labels(os.path.join(sparse_dir, name + ".labels"), labels.cpu().numpy())
+        pn2.write_point_cloud_pcd(os.path.join(sparse_dir, name + ".pcd"), points)
+        pn2.write_labels(os.path.join(sparse_dir, name + ".labels"), labels)
         print("    Exported sparse pcd and labels to %s" % os.path.join(sparse_dir, name))
 
         dense_points, dense_gt = dense[name]
@@ -121,9 +121,8 @@ def main():
         dense_labels, dense_colors = pn2.predict.label_dense(points, labels, dense_points, dense_gt, confusion=cm, chunk=args.chunk)
         torch.cuda.synchronize()
         print("    KNN interpolation of %d dense points: %.1f ms" % (len(dense_points), (time.perf_counter() - t0) * 1e3))
-        U.write_labels(os.path.join(dense_dir, name + ".labels"), dense_labels.cpu().numpy())
-        U.write_point_cloud_pcd(os.path.join(dense_dir, name + "_colored.pcd"), dense_points,
-                                dense_colors.cpu().numpy().astype(np.float64) / 255.0)  # (floor(c / 255 * 255) == c for every c)
+        pn2.write_labels(os.path.join(dense_dir, name + ".labels"), dense_labels)
+        pn2.write_point_cloud_pcd(os.path.join(dense_dir, name + "_colored.pcd"), dense_points, dense_colors)  # uint8 as it is
         print("    Dense labels and coloured pcd written to %s" % os.path.join(dense_dir, name))
         if dense_gt is not None:
             cm.print_metrics(dataset.labels_names)

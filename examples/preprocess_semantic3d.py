@@ -87,10 +87,10 @@ def main():
             pn2.point_cloud_txt_to_pcd(raw_dir, name, dev)
         sp, sc, sl = pn2.downsample.down_sample_arrays(points, colors, labels, voxel_size=args.voxel)
         print("Num points after down sampling:", sp.shape[0])
-        U.write_point_cloud_pcd(sparse_pcd, sp.cpu().numpy(), sc.cpu().numpy())
+        pn2.write_point_cloud_pcd(sparse_pcd, sp, sc)
         print("Point cloud written to:", sparse_pcd)
         if sl is not None:
-            U.write_labels(sparse_labels, sl.cpu().numpy())
+            pn2.write_labels(sparse_labels, sl)
             print("Labels written to:", sparse_labels)
     return 0
 

@@ -872,6 +872,42 @@ int pn2_text_index_lines(const unsigned char *text, int nbytes, int *line_start,
 int pn2_text_parse(const unsigned char *text, int nbytes, const int *line_start, int nlines, const int *kinds, int ncols,
                    double *out_f64, int *out_i32, unsigned char *flags, int *status, void *stream);
 
+/* ---- scene files: what the predict flow writes and reads back (reference util/point_cloud_util.py:60-63, Open3D's .pcd) ----
+ * Integer text, the inverse of pn2_text_parse with PN2_TEXT_I32 columns.  values (nrows, ncols) int32, row-major,
+ * 1 <= ncols <= PN2_TEXT_MAX_COLS.  A row becomes its tokens as Python's "%d" prints them (a '-' for negatives, no '+', no
+ * leading zeros; INT32_MIN included), separated by one space, ended by '\n'.  *out_bytes (device u64) = the bytes all rows
+ * need, whatever text_cap is; text[0 : min(need, text_cap)) is exactly that prefix of the full text; no byte at or past
+ * text_cap and no byte past need is written, so a caller whose buffer holds nrows * ncols * PN2_TEXT_I32_CHARS bytes never
+ * calls twice.  text: 16-byte aligned; nrows * ncols * PN2_TEXT_I32_CHARS <= PN2_TEXT_MAX_BYTES (int offsets, PN2_ERANGE).
+ * One row per lane, PN2_TEXT_FORMAT_ROWS rows per workgroup: row lengths and a total per workgroup, an exclusive scan of the
+ * totals, then every workgroup stages its contiguous span in LDS and stores it 16 bytes at a time.  workspace: 256-byte
+ * aligned, *bytes of pn2_text_format_workspace_bytes(nrows) -- per workgroup a total and its scan. */
+#define PN2_TEXT_I32_CHARS 12        /* most bytes of one token with its separator: "-2147483648" and a ' ' or '\n' */
+#define PN2_TEXT_FORMAT_ROWS 256
+int pn2_text_format_workspace_bytes(int nrows, unsigned long long *bytes);
+int pn2_text_format_i32(const int *values, int nrows, int ncols, unsigned char *text, size_t text_cap,
+                        unsigned long long *out_bytes, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The payload of a binary .pcd with 4-byte fields, one row per lane.  n <= PN2_PCD_MAX_ROWS (PN2_ERANGE); rows 16-byte aligned.
+ * pn2_pcd_pack: points (n,3) float32 (PN2_PCD_F32) or float64 (PN2_PCD_F64) -> rows of `x y z` (12 bytes, PN2_PCD_COLOR_NONE)
+ * or `x y z rgb` (16 bytes), what util.point_cloud_util.write_point_cloud_pcd writes: coordinates (float)p, the colour word
+ * (r << 16) | (g << 8) | b with r = clip(floor(c * 255.0), 0, 255) of a float64 colour in [0, 1] (PN2_PCD_COLOR_F64, (n,3)) or
+ * the byte itself (PN2_PCD_COLOR_U8, (n,3)).
+ * pn2_pcd_unpack: rows of nfields (3 .. PN2_PCD_MAX_FIELDS) words, ix / iy / iz / irgb the word index of each field
+ * (irgb = -1: none) -> points (n,3) float64 = the words read as float32, colors (n,3) float64 = byte / 255.0 correctly rounded
+ * (zeros without an rgb field; colors = NULL: not written) -- util.point_cloud_util.read_point_cloud_pcd's arrays. */
+#define PN2_PCD_F32 0
+#define PN2_PCD_F64 1
+#define PN2_PCD_COLOR_NONE 0
+#define PN2_PCD_COLOR_F64 1
+#define PN2_PCD_COLOR_U8 2
+#define PN2_PCD_MAX_ROWS 134217728
+#define PN2_PCD_MAX_FIELDS 64
+int pn2_pcd_pack(const void *points, int point_kind, const void *colors, int color_kind, int n, unsigned int *rows,
+                 void *stream);
+int pn2_pcd_unpack(const unsigned int *rows, int n, int nfields, int ix, int iy, int iz, int irgb, double *points,
+                   double *colors, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

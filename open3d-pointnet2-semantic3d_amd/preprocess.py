@@ -19,7 +19,6 @@ import numpy as np
 import torch
 
 from ._lib import ABI, int_array, launch, ptr, u64_array
-from .util import point_cloud_util
 
 F64, I32, TRUNC_I32, SKIP = (ABI.constants["PN2_TEXT_" + k] for k in ("F64", "I32", "TRUNC_I32", "SKIP"))
 MALFORMED = ABI.constants["PN2_TEXT_MALFORMED"]
@@ -327,4 +326,5 @@ def point_cloud_txt_to_pcd(raw_dir, file_prefix, device="cuda"):
     print("txt: {}".format(txt_file))
     print("pcd: {}".format(pcd_file))
     points, colors, _ = read_semantic3d_txt(txt_file, device, as_pcd=True)
-    point_cloud_util.write_point_cloud_pcd(pcd_file, points.cpu().numpy(), colors.cpu().numpy())
+    from . import scene_io  # it imports this module
+    scene_io.write_point_cloud_pcd(pcd_file, points, colors)
