@@ -10,7 +10,11 @@
     --data PATH   the preprocessed Semantic3D files (<PATH>/<scene>.pcd and .labels, the reference's dataset/semantic_data)
     without it    a synthetic multi-scene store: scenes of different sizes, dense enough for columns of 50k+ points
 
-usage: python examples/train_semantic3d.py [--data PATH] [--epochs E] [--max-steps S] [--val-batches V]"""
+    --jitter SIGMA CLIP, --scale LO HI, --shift RANGE, --dropout MAX_RATIO, --shuffle
+                  the rest of the reference's util/provider.py on the training batches (util.provider.Augmenter, one fused
+                  call behind the sampler on the same side stream; it also takes over the z-rotation).  All off by default.
+
+usage: python examples/train_semantic3d.py [--data PATH] [--epochs E] [--max-steps S] [--val-batches V] [augmentation]"""
 import argparse
 import os
 import sys
@@ -56,6 +60,22 @@ def datasets(args, hp, dev):
     return mk("train", 0), mk("validation", 1)
 
 
+def add_augmentation_arguments(ap):
+    ap.add_argument("--jitter", type=float, nargs=2, metavar=("SIGMA", "CLIP"), default=None)
+    ap.add_argument("--scale", type=float, nargs=2, metavar=("LO", "HI"), default=None)
+    ap.add_argument("--shift", type=float, metavar="RANGE", default=None)
+    ap.add_argument("--dropout", type=float, metavar="MAX_RATIO", default=None)
+    ap.add_argument("--shuffle", action="store_true")
+
+
+def augmenter(args, dev, rotate=None, seed=0):
+    """the Augmenter the command line asks for, or None when it asks for none (the default run is then unchanged)"""
+    if args.jitter is None and args.scale is None and args.shift is None and args.dropout is None and not args.shuffle:
+        return None
+    return pn2.util.provider.Augmenter(seed=seed, device=dev, rotate=rotate, jitter=args.jitter, scale=args.scale,
+                                       shift=args.shift, dropout=args.dropout, shuffle=args.shuffle)
+
+
 def log(title, m):
     print(title)
     for line in M.epoch_log_lines(m["mean_loss"], m["per_class_iou"], m["accuracy"], m["mean_iou"]):
@@ -68,6 +88,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--max-steps", type=int, default=0, help="cap the training steps per epoch (0: get_num_batches)")
     ap.add_argument("--val-batches", type=int, default=0, help="validation batches (0: get_num_batches of validation)")
+    add_augmentation_arguments(ap)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     hp = dict(pn2.model.SEMANTIC_HYPERPARAMS)
@@ -82,6 +103,7 @@ def main():
     tr = pn2.train.Trainer(hp, train.num_classes, store=pn2.util.tf_util.VariableStore(device=dev, seed=0), device=dev,
                            track_metrics=True)
     side = torch.cuda.Stream()
+    aug = augmenter(args, dev, rotate="z") or True  # True: the sampler's own z-rotation, as before
 
     def sample_next(ds, augment):
         side.wait_stream(torch.cuda.current_stream())
@@ -99,9 +121,9 @@ def main():
             steps = min(steps, args.max_steps)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        cur = train.sample_batch_in_all_files(B, augment=True)
+        cur = train.sample_batch_in_all_files(B, augment=aug)
         for _ in range(steps):
-            nxt = sample_next(train, True)
+            nxt = sample_next(train, aug)
             tr.train_step(*cur, sync=False, next_pc=nxt[0], next_labels=nxt[1], next_smpw=nxt[2])
             cur = nxt
         m = tr.train_metrics()

@@ -5,7 +5,10 @@
                            ->  Trainer.train_step (SA/FP stack + head + weighted CE + backward + Adam, N1),
                                the NEXT batch's FPS / ball-query / three_nn chain prefetched on a side stream
 
-No batch ever crosses PCIe.  usage: python examples/train_synthetic.py [steps] [scene_points]"""
+No batch ever crosses PCIe.  --jitter SIGMA CLIP, --scale LO HI, --shift RANGE, --dropout MAX_RATIO, --shuffle: the reference's
+util/provider.py on every batch (util.provider.Augmenter, one fused call behind the sampler on the same stream); all off by default.
+usage: python examples/train_synthetic.py [steps] [scene_points] [augmentation]"""
+import argparse
 import os
 import sys
 import time
@@ -15,11 +18,16 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pn2_amd as pn2  # noqa: E402
+from train_semantic3d import add_augmentation_arguments, augmenter  # noqa: E402
 
 
 def main():
-    steps = int(sys.argv[1]) if len(sys.argv) > 1 else 30
-    n_scene = int(sys.argv[2]) if len(sys.argv) > 2 else 2000000
+    ap = argparse.ArgumentParser()
+    ap.add_argument("steps", type=int, nargs="?", default=30)
+    ap.add_argument("scene_points", type=int, nargs="?", default=2000000)
+    add_augmentation_arguments(ap)
+    args = ap.parse_args()
+    steps, n_scene = args.steps, args.scene_points
     dev = torch.device("cuda:0")
     rs = np.random.RandomState(0)
     # a 60 m x 40 m scene: ground + a few "buildings"; label = height band (something learnable from xyz + rgb)
@@ -36,9 +44,14 @@ def main():
     B, N = hp["batch_size"], hp["num_point"]
     tr = pn2.train.Trainer(hp, 9, store=pn2.util.tf_util.VariableStore(device=dev, seed=0), device=dev)
 
+    aug = augmenter(args, dev)
+
     def batch():
         c, _, l, col = fd.sample_batch(B, N, capacity=400000)
-        return torch.cat([c, col], dim=2), l.long(), label_weights[l.long()]
+        if aug is None:
+            return torch.cat([c, col], dim=2), l.long(), label_weights[l.long()]
+        pc, lab, w = aug(torch.cat([c, col], dim=2), l.int(), label_weights[l.long()])  # labels and weights follow a shuffle
+        return pc, lab.long(), w
 
     prep = torch.cuda.Stream()  # batch k+1 is sampled (and its geometry chain run) while step k trains
     cur = batch()

@@ -908,6 +908,83 @@ int pn2_pcd_pack(const void *points, int point_kind, const void *colors, int col
 int pn2_pcd_unpack(const unsigned int *rows, int n, int nfields, int ix, int iy, int iz, int irgb, double *points,
                    double *colors, void *stream);
 
+/* ---- point-cloud augmentation: util/provider.py of the reference as one pipeline (csrc/pn2_augment.hip) ------------------
+ * in (b,n,c) float32 -> out (b,n,c) float32, c >= 3, xyz in channels 0:3; in_labels (b,n) int32 -> out_labels and in_weights
+ * (b,n) float32 -> out_weights are optional companions (both of a pair or neither) that are only ever permuted.  Stages run
+ * in this fixed order; `flags` turns each on by its bit:
+ *   0 PN2_AUG_SHUFFLE   shuffle_points: out row j is in row perm[j], ONE permutation (n) for the whole batch; labels and
+ *                       weights follow.  Every later stage, and every per-point draw, is indexed by the row after the shuffle.
+ *   1 PN2_AUG_ROTATE | PN2_AUG_PERTURB   p @ R for a (3,3) matrix R per cloud (rotate_point_cloud, rotate_feature_point_cloud,
+ *                       rotate_point_cloud_with_normal, rotate_point_cloud_by_angle*, rotate_perturbation_point_cloud*); with
+ *                       PN2_AUG_ROTATE_NORMALS (needs c >= 6) channels 3:6 are rotated by the same R.
+ *   2 PN2_AUG_SCALE     random_scale_point_cloud: xyz * s, one s per cloud.
+ *   3 PN2_AUG_SHIFT     shift_point_cloud: xyz + t, one t (3) per cloud.
+ *   4 PN2_AUG_JITTER    jitter_point_cloud: x + clip(jitter_sigma * z, -jitter_clip, jitter_clip), one standard normal z per
+ *                       value: xyz only (cj = 3) -- with PN2_AUG_JITTER_ALL all c channels (cj = c), as the reference does to
+ *                       the (B,N,3) arrays it is given.
+ *   5 PN2_AUG_DROPOUT   random_point_dropout: row j of a cloud with u[j] <= ratio becomes row 0 of that cloud as it leaves
+ *                       stage 4 (all c channels).  A dropped row reads nobody's output: it redoes stages 1-4 on the INPUT of row
+ *                       0 with row 0's own jitter draws; row 0, dropped or not, keeps its own value.  Labels and weights are
+ *                       not touched (the reference does not touch them).
+ * Arithmetic rule.  An enabled stage takes float64 and does the reference's one operation in float64: rotation
+ * (x*R[0][j] + y*R[1][j]) + z*R[2][j] in that order (the library is built with -ffp-contract=off), scale x*s, shift x + t,
+ * jitter x + clip(sigma*z).  The float32 input is widened once, values stay float64 between enabled stages and are rounded to
+ * float32 once, at the store.  With ONE stage enabled this is what the numpy function does to a float32 batch (numpy computes
+ * `f32 op= f64` and np.dot of a float32 array with a float64 matrix in float64 and rounds once).  Scale and shift act on xyz,
+ * rotation on xyz (and 3:6 with PN2_AUG_ROTATE_NORMALS); a channel no enabled stage touches is copied unchanged.
+ *
+ * Draws, replay mode (flags & PN2_AUG_REPLAY): the device forms none; per enabled stage its input is required (PN2_ENULL):
+ * draw_perm (n) int32 (an entry outside [0,n) reads row j itself), draw_matrix (b,3,3) float64, draw_scale (b), draw_shift
+ * (b,3), draw_noise (b,n,cj) float64 standard normals (before sigma and the clip), draw_ratio (b) and draw_u (b,n) float64.
+ * counter is not read.
+ * Draws, device mode: counter-based hashes of csrc/pn2_rng.h.  h(s) = sample_stream(seed, *counter, s) for cloud s, draw i of
+ * it U(i) = unit53(draw64(h(s), i)) in [0,1), and
+ *   uniform(lo, hi) = lo + (hi - lo) * U;  angle = (U * 2.0) * pi;
+ *   normal(i) = sqrt(-2.0 * log(1.0 - U(i))) * cos((U(i + 1) * 2.0) * pi)   (Box-Muller, float64)
+ * with these indices (T = 2^41):
+ *   T + 0          rotation angle about rotate_axis (0 x, 1 y, 2 z: the reference's three matrices)      [PN2_AUG_ROTATE]
+ *   T + 2 + 2k     k = 0,1,2: normal -> angle_k = clip(perturb_sigma * normal, -perturb_clip, perturb_clip); R_perturb =
+ *                  Rz . (Ry . Rx) as the reference builds it; with both bits R = R_axis . R_perturb; every 3x3 product in
+ *                  the plain order (a0*b0 + a1*b1) + a2*b2                                               [PN2_AUG_PERTURB]
+ *   T + 8          scale = uniform(scale_lo, scale_hi)
+ *   T + 9 + a      shift[a] = uniform(-shift_range, shift_range), a = 0,1,2
+ *   T + 12         ratio = U * dropout_max
+ *   2T + 2*(j*cj + a)   normal of the jitter of row j, channel a
+ *   4T + j         u[j] of the dropout of row j
+ *   and for the permutation the stream of cloud index -1: key[i] = draw64(h(-1), 8T + i); perm = the indices sorted by
+ *   (key, index), i.e. perm[rank of i] = i.
+ * *counter (device int64) is read once and advanced by one per call, by a one-workgroup prologue launch that snapshots it
+ * into the workspace and forms the per-cloud parameters; the other launches read the snapshot.  No host synchronisation; a
+ * captured call replays into fresh draws.  Launches: prologue, permutation (rank count over LDS tiles of keys, only with
+ * PN2_AUG_SHUFFLE), rows (256 lanes, grid (row tiles, b), one row per lane).
+ * Outputs: out_params (b,PN2_AUG_PARAMS) float64 = R (9, row-major), scale, shift (3), ratio, 0, 0 of this call (identity /
+ * 1 / 0 / 0 for a stage that is off), or NULL; out_perm (n) int32, required with PN2_AUG_SHUFFLE.
+ * in == out is allowed without PN2_AUG_SHUFFLE (PN2_EINVAL with it; PN2_EUNSUP with PN2_AUG_DROPOUT and c >
+ * PN2_AUG_INPLACE_MAX_C: row 0 of every cloud is then kept in the workspace).  Labels / weights may alias their outputs likewise.
+ * PN2_EINVAL: b, n <= 0, c < 3, b > 65535, unknown flag bits or axis, PN2_AUG_ROTATE_NORMALS with c < 6, a stage's parameters
+ * out of order (sigma < 0, clip <= 0, lo > hi, range < 0, dropout_max outside [0,1]), workspace too small or not 256-byte
+ * aligned; PN2_ENULL: in, out, workspace, counter (device mode), a replay input of an enabled stage, out_perm with shuffle. */
+#define PN2_AUG_SHUFFLE 1
+#define PN2_AUG_ROTATE 2
+#define PN2_AUG_PERTURB 4
+#define PN2_AUG_SCALE 8
+#define PN2_AUG_SHIFT 16
+#define PN2_AUG_JITTER 32
+#define PN2_AUG_DROPOUT 64
+#define PN2_AUG_ROTATE_NORMALS 128
+#define PN2_AUG_JITTER_ALL 256
+#define PN2_AUG_REPLAY 512
+#define PN2_AUG_PARAMS 16
+#define PN2_AUG_INPLACE_MAX_C 64
+int pn2_augment_workspace_bytes(int b, unsigned long long *bytes);
+int pn2_augment(int b, int n, int c, int flags, int rotate_axis, double perturb_sigma, double perturb_clip, double scale_lo,
+                double scale_hi, double shift_range, double jitter_sigma, double jitter_clip, double dropout_max,
+                unsigned long long seed, long long *counter, const int *draw_perm, const double *draw_matrix,
+                const double *draw_scale, const double *draw_shift, const double *draw_noise, const double *draw_ratio,
+                const double *draw_u, const float *in, const int *in_labels, const float *in_weights, void *workspace,
+                size_t workspace_bytes, double *out_params, int *out_perm, float *out, int *out_labels, float *out_weights,
+                void *stream);
+
 #ifdef __cplusplus
 }
 #endif

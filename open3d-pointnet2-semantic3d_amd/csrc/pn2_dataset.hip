@@ -20,6 +20,7 @@
 // probability ~cnt^2 / 2^65 per column.  Replay mode takes the reference's draws instead (scene, centre, its shuffled
 // boolean mask, cos / sin computed by numpy) and reproduces its batch bit for bit.
 #include "pn2_common.h"
+#include "pn2_rng.h"
 
 namespace {
 
@@ -84,24 +85,8 @@ struct Draws {  // replay inputs (all NULL: device random numbers from seed and 
     const double* rot;  // (b, 3): angle, cos, sin
 };
 
-__device__ __forceinline__ unsigned long long fmix64(unsigned long long x) {
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
-    x ^= x >> 33;
-    return x;
-}
-// counter-based stream of (seed, batch counter, sample); one more mix per draw index
-__device__ __forceinline__ unsigned long long sample_stream(unsigned long long seed, unsigned long long ctr, int s) {
-    unsigned long long h = fmix64(seed + 0x9E3779B97F4A7C15ull);
-    h = fmix64(h ^ (ctr * 0xD1B54A32D192ED03ull + 0x2545F4914F6CDD1Dull));
-    return fmix64(h ^ ((unsigned long long)(unsigned)s * 0xAEF17502108EF2D9ull + 0x632BE59BD9B4E019ull));
-}
-// subset key of the member at scene-local index i; tags of the per-sample draws live above every point index
-__device__ __forceinline__ unsigned long long draw64(unsigned long long h, unsigned long long i) {
-    return fmix64(h ^ fmix64(i + 0x8CB92BA72F3D8DD7ull));
-}
+// fmix64, sample_stream, draw64, unit53: csrc/pn2_rng.h.  Tags of the per-sample draws live above every point index
 constexpr unsigned long long kTagScene = 1ull << 40, kTagCenter = kTagScene + 1, kTagAngle = kTagScene + 2;
-__device__ __forceinline__ double unit53(unsigned long long k) { return (double)(k >> 11) * 0x1.0p-53; }  // [0, 1)
 
 __device__ __forceinline__ unsigned long long ordered_key(double v) {
     unsigned long long k = (unsigned long long)__double_as_longlong(v);

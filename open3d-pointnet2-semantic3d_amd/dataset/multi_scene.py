@@ -178,8 +178,14 @@ class SemanticDataset:
         center=(B,) (relative to its scene, as np.random.randint(0, len(points)) draws it), masks=(B,cap) uint8 (the
         reference's shuffled mask for columns wider than N), angle=(B,) float64 (np.random.uniform() * 2 * np.pi)): the
         reference's np.random draws, replayed.  Afterwards last_scene, last_center, last_cnt, last_sel (store indices:
-        scene offset + position in the x-sorted scene) and last_angle describe the batch."""
+        scene offset + position in the x-sorted scene) and last_angle describe the batch.
+        augment=util.provider.Augmenter(...): the sampler runs with its own rotation off and the augmenter runs on its batch
+        in the same stream (pn2_augment: two or three more launches; labels and weights follow a shuffle); the augmenter's
+        last_* attributes say what it applied."""
         b, n = int(batch_size), self.num_points_per_sample
+        augmenter = None
+        if callable(augment):
+            augmenter, augment = augment, False
         if b <= 0:
             raise ValueError("batch_size must be positive")
         d = self._upload(b)
@@ -225,6 +231,8 @@ class SemanticDataset:
                ptr(data), ptr(label), ptr(weights))
         self.last_scene, self.last_center, self.last_cnt = info[:, 0], info[:, 1], info[:, 2]
         self.last_status, self.last_sel, self.last_angle = info[:, 7], sel, finfo[:, 0]
+        if augmenter is not None:  # in place unless it shuffles
+            return augmenter(data, label, weights, out=None if augmenter.shuffle else data)
         return data, label, weights
 
     def _scene_view(self, d, scene):

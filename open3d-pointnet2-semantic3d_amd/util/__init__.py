@@ -1,1 +1,1 @@
-from . import tf_util, pointnet_util, metric  # noqa: F401
+from . import tf_util, pointnet_util, metric, provider  # noqa: F401
