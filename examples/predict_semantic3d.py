@@ -44,7 +44,8 @@ def load_scenes(args, hp, dev):
     tensors when read from files (pn2.read_point_cloud_pcd / pn2.load_labels), numpy arrays for the synthetic scenes"""
     N = hp["num_point"]
     if args.data:
-        ds = pn2.dataset.SemanticDataset(N, args.set, hp["use_color"], hp["box_size_x"], hp["box_size_y"], args.data, device=dev)
+        ds = pn2.dataset.SemanticDataset(N, args.set, hp["use_color"], hp["box_size_x"], hp["box_size_y"], args.data, device=dev,
+                                         ingest=args.ingest)
         dense = {}
         for name in ds.scene_names:
             prefix = os.path.join(args.raw or args.data, name)
@@ -60,11 +61,14 @@ def load_scenes(args, hp, dev):
         t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dev, dt)  # noqa: E731
         sp, sc, sl = pn2.downsample.down_sample_arrays(t(pts, torch.float64), t(colors, torch.float64), t(labels, torch.int32),
                                                        voxel_size=args.voxel)
-        scenes.append((sp.cpu().numpy(), sl.cpu().numpy(), sc.cpu().numpy(), name))
+        if args.ingest == "device":  # the down-sampled scene stays where it is
+            scenes.append((sp, sl, sc, name))
+        else:
+            scenes.append((sp.cpu().numpy(), sl.cpu().numpy(), sc.cpu().numpy(), name))
         dense[name] = (pts.astype(np.float32), labels.astype(np.int32))
         print("%s: %d raw points -> %d in the store (voxel %.2f m)" % (name, len(pts), len(scenes[-1][0]), args.voxel))
     ds = pn2.dataset.SemanticDataset(N, args.set, hp["use_color"], hp["box_size_x"], hp["box_size_y"], "", device=dev,
-                                     scenes=scenes)
+                                     scenes=scenes, ingest=args.ingest)
     return ds, dense
 
 
@@ -83,6 +87,8 @@ def main():
     ap.add_argument("--scene-points", type=int, default=2000000, help="raw points per synthetic scene")
     ap.add_argument("--voxel", type=float, default=0.1, help="voxel size of the synthetic store")
     ap.add_argument("--chunk", type=int, default=1 << 24, help="dense points per interpolation call")
+    ap.add_argument("--ingest", choices=("host", "device"), default="host",
+                    help="where the store is sorted and measured: numpy, or pn2_scene_ingest straight into HBM")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     hp = dict(pn2.model.SEMANTIC_HYPERPARAMS)

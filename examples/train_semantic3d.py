@@ -10,6 +10,10 @@
     --data PATH   the preprocessed Semantic3D files (<PATH>/<scene>.pcd and .labels, the reference's dataset/semantic_data)
     without it    a synthetic multi-scene store: scenes of different sizes, dense enough for columns of 50k+ points
 
+    --ingest device
+                  the store is built on the device (SemanticDataset(ingest="device")): same store, same log lines wherever
+                  no two points of a scene share an x (the order of such rows is the one thing the two paths may differ in)
+
     --jitter SIGMA CLIP, --scale LO HI, --shift RANGE, --dropout MAX_RATIO, --shuffle
                   the rest of the reference's util/provider.py on the training batches (util.provider.Augmenter, one fused
                   call behind the sampler on the same side stream; it also takes over the z-rotation).  All off by default.
@@ -47,7 +51,7 @@ SYNTHETIC_SPLITS = {"train": ["syn_a", "syn_b", "syn_c"], "validation": ["syn_d"
 
 
 def datasets(args, hp, dev):
-    kw = dict(device=dev)
+    kw = dict(device=dev, ingest=args.ingest)
     N = hp["num_point"]
     if args.data:
         mk = lambda split, seed: pn2.dataset.SemanticDataset(N, split, hp["use_color"], hp["box_size_x"],  # noqa: E731
@@ -88,6 +92,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--max-steps", type=int, default=0, help="cap the training steps per epoch (0: get_num_batches)")
     ap.add_argument("--val-batches", type=int, default=0, help="validation batches (0: get_num_batches of validation)")
+    ap.add_argument("--ingest", choices=("host", "device"), default="host",
+                    help="where the store is sorted and measured: numpy, or pn2_scene_ingest straight into HBM")
     add_augmentation_arguments(ap)
     args = ap.parse_args()
     dev = torch.device("cuda:0")

@@ -599,6 +599,36 @@ int pn2_dataset_sample(int b, int npts, int num_scenes, int max_chunks, int use_
                        void *workspace, size_t workspace_bytes, int *out_info, double *out_finfo, int *out_sel,
                        float *out_data, int *out_labels, float *out_weights, void *stream);
 
+/* One scene of that store built on the device (csrc/pn2_store.hip): SemanticFileData.__init__ dataset/semantic_dataset.py:84-88
+ * (sort by x, gather) plus what SemanticDataset.__init__ (:214-290) takes from the sorted scene.  Inputs: points (n,3) float64,
+ * colors (n,3) float64 or NULL, labels (n) int32 or NULL.  The rule:
+ *   order      output row i is input row perm[i]; perm sorts by points[:, 0] ascending, ties broken by input index
+ *              (np.argsort(x, kind="stable"); the reference's default argsort leaves the order of ties unspecified).  -0.0 and
+ *              +0.0 compare equal, as in numpy: the key treats them as one value, the stored value keeps its sign.
+ *   out_points (n,3) float64: the rows copied bit for bit.
+ *   out_colors (n,3) float32: float64 -> float32 by one IEEE rounding (numpy astype(np.float32)).  colors == NULL: nothing is
+ *              read or written for colours (out_colors may be NULL).
+ *   out_labels (n) uint8: int32 -> uint8; labels == NULL writes zeros.  A label outside [0, 255] sets status 2.
+ *   out_zrange (2) float64 = [min z, max z] of the scene, exact (scene_z_size is their one subtraction, left to the caller);
+ *              among zeros -0.0 counts as the smaller, so the pair does not depend on the order of the rows.
+ *   out_hist   (9) int64 = np.histogram(labels, range(10))[0]: labels 8 and 9 share the last bin, labels above 9 are valid
+ *              but counted nowhere; labels == NULL: all n in bin 0.
+ *   status     (1) int32: 0 ok; 1 a NaN or +-inf in x, y or z (the host path sorts NaN last and then mis-searches; this one
+ *              refuses); 2 a label outside [0, 255]; both: 1.  With a non-zero status the other outputs are written inside
+ *              their n rows like any others, but what they hold is not specified.
+ *   out_perm   (n) int32 = perm, or NULL.
+ * Every output may point into the middle of a larger store: nothing outside rows [0, n) of each is written.  No output may
+ * overlap an input.  Pointers naturally aligned; workspace 256-byte aligned, pn2_scene_ingest_workspace_size(n) bytes (a
+ * workspace sized for one n serves any n whose own size is not larger), no state kept between calls.
+ * Four launches and a radix sort (hipcub, 64 key bits, stable); every reduction is in integers or ordered keys, so every
+ * result is independent of the order in which workgroups arrive.  No host synchronisation.
+ * PN2_EINVAL: n <= 0, workspace too small, a misaligned pointer; PN2_ENULL: points, out_points, out_labels, out_zrange,
+ * out_hist, status or workspace NULL, or out_colors NULL while colors is not: refused before any launch. */
+int pn2_scene_ingest_workspace_size(int n, unsigned long long *bytes);
+int pn2_scene_ingest(int n, const double *points, const double *colors, const int *labels, double *out_points,
+                     float *out_colors, unsigned char *out_labels, int *out_perm, double *out_zrange, long long *out_hist,
+                     int *status, void *workspace, size_t workspace_bytes, void *stream);
+
 /* pn2_fp_mlp_fused with the first layer's product with the INTERPOLATED channels hoisted out by linearity:
  * three_interpolate(points2) @ W1a == three_interpolate(points2 @ W1a) (pointnet_util.py:300-311 followed by the first conv
  * of :312-325), and z = points2 @ W1a has the m known rows per cloud instead of the n unknown ones.  z (b*m, widths[0])

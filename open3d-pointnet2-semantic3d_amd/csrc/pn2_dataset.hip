@@ -20,6 +20,7 @@
 // probability ~cnt^2 / 2^65 per column.  Replay mode takes the reference's draws instead (scene, centre, its shuffled
 // boolean mask, cos / sin computed by numpy) and reproduces its batch bit for bit.
 #include "pn2_common.h"
+#include "pn2_ordered.h"  // ordered_key, ordered_to_double
 #include "pn2_rng.h"
 
 namespace {
@@ -87,15 +88,6 @@ struct Draws {  // replay inputs (all NULL: device random numbers from seed and 
 
 // fmix64, sample_stream, draw64, unit53: csrc/pn2_rng.h.  Tags of the per-sample draws live above every point index
 constexpr unsigned long long kTagScene = 1ull << 40, kTagCenter = kTagScene + 1, kTagAngle = kTagScene + 2;
-
-__device__ __forceinline__ unsigned long long ordered_key(double v) {
-    unsigned long long k = (unsigned long long)__double_as_longlong(v);
-    return (k >> 63) ? ~k : (k | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ordered_to_double(unsigned long long k) {
-    k = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-    return __longlong_as_double((long long)k);
-}
 
 // first index i in [lo, hi) with x[3*i] >= v (np.searchsorted(points[:, 0], v), side='left', inside one scene segment)
 __device__ __forceinline__ int lower_bound_x(const double* __restrict__ pts, int lo, int hi, double v) {

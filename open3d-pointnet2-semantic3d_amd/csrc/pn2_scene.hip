@@ -9,6 +9,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "pn2_common.h"
+#include "pn2_ordered.h"  // ordered_key, ordered_to_double
 
 namespace {
 
@@ -169,15 +170,10 @@ __global__ void voxel_minmax_kernel(int n, const double* __restrict__ pts, doubl
         double v = sm[a][0];
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w) v = a < 3 ? fmin(v, sm[a][w]) : fmax(v, sm[a][w]);
         // float64 min/max through 64-bit integer atomics on an order-preserving key
-        unsigned long long k = (unsigned long long)__double_as_longlong(v);
-        k = (k >> 63) ? ~k : (k | 0x8000000000000000ull);
+        const unsigned long long k = ordered_key(v);
         if (a < 3) atomicMin(reinterpret_cast<unsigned long long*>(mm) + a, k);
         else atomicMax(reinterpret_cast<unsigned long long*>(mm) + a, k);
     }
-}
-__device__ __forceinline__ double ordered_to_double(unsigned long long k) {
-    k = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-    return __longlong_as_double((long long)k);
 }
 
 __global__ void voxel_key_kernel(int n, const double* __restrict__ pts, const double* __restrict__ mm, double vs,

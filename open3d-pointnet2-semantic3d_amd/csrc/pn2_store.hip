@@ -1,0 +1,194 @@
+// pn2_store.hip -- one scene of the SemanticDataset store built on the device: SemanticFileData.__init__
+// (dataset/semantic_dataset.py:84-88 of the reference: sort by x, gather points / labels / colours) and what
+// SemanticDataset.__init__ (:214-290) takes from the sorted scene (scene_z_size, the label histogram), written straight into
+// the scene's slice of the resident store.  The rule is in include/pn2_abi.h (pn2_scene_ingest).
+//
+//   1 ingest_key_kernel    : one row per lane; key = ordered_key(x) with -0.0 folded onto +0.0, payload = row index; a
+//                            non-finite x, y or z raises bit 0 of the flags (one atomic per wave that saw one);
+//   2 hipcub radix sort    : 64 key bits, pairs, stable: ties in x keep their input order (np.argsort(kind="stable"));
+//   3 ingest_gather_kernel : one OUTPUT row per lane: perm, 24-byte point row, 3 colours float64 -> float32, label -> uint8;
+//                            z min / max as ordered keys (wave, LDS, one atomicMin / atomicMax per workgroup), the label
+//                            histogram (ballots, LDS, one 64-bit atomic per non-zero bin per workgroup), the label range
+//                            (a ballot; bit 1 of the flags);
+//   4 ingest_finish_kernel : keys -> out_zrange, flags -> status.
+// Every reduction is in integers or ordered keys: no result depends on the order in which workgroups arrive.
+//
+// What bounds the gather: its writes are coalesced (24 + 12 + 1 + 4 bytes per row, consecutive lanes consecutive rows), its
+// reads are not: each lane reads a 24-byte point row, a 24-byte colour row and a 4-byte label at a random row of the input, so
+// each wave-instruction touches up to 64 different 128-byte lines of which it uses 8 bytes (a row straddles two lines one time
+// in 16 * 3).  The input of a scene (tens of MB) sits in the Infinity Cache after the key kernel's pass, so the kernel runs at
+// the rate the memory system turns random 64-byte requests around, not at the HBM byte rate; nine independent loads per lane
+// and eight waves per SIMD are what hides their latency.
+#include <hipcub/hipcub.hpp>
+
+#include "pn2_common.h"
+#include "pn2_ordered.h"  // ordered_key, ordered_to_double
+
+namespace {
+
+constexpr int kT = 256;  // threads per workgroup: one row per lane
+constexpr int kWaves = kT / 64;
+constexpr int kHistBins = 9;
+enum { FLAG_NONFINITE = 1, FLAG_LABEL = 2 };
+
+struct Scal {  // the scalars the kernels reduce into (workspace)
+    unsigned long long zmin, zmax;  // ordered keys
+    unsigned flags;
+};
+
+struct Layout {
+    size_t keys_in, keys_out, vals_in, vals_out, scal, cub, total;
+    size_t cub_bytes;
+};
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+// the part in front of the sort's own temporary storage: known without asking the sort
+inline size_t fixed_layout(int n, Layout* L) {
+    size_t o = 0;
+    L->keys_in = o; o += al256((size_t)n * 8);
+    L->keys_out = o; o += al256((size_t)n * 8);
+    L->vals_in = o; o += al256((size_t)n * 4);
+    L->vals_out = o; o += al256((size_t)n * 4);
+    L->scal = o; o += 256;
+    return o;
+}
+inline hipError_t layout(int n, Layout* L) {
+    size_t o = fixed_layout(n, L);
+    size_t cub = 0;
+    const hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, cub, (const unsigned long long*)nullptr,
+                                                            (unsigned long long*)nullptr, (const int*)nullptr, (int*)nullptr, n, 0, 64);
+    L->cub_bytes = cub;
+    L->cub = o; o += al256(cub);
+    L->total = o;
+    return e;
+}
+
+__device__ __forceinline__ bool finite64(double v) {
+    return ((unsigned long long)__double_as_longlong(v) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
+}
+
+__global__ void __launch_bounds__(kT)
+ingest_key_kernel(int n, const double* __restrict__ pts, unsigned long long* __restrict__ keys, int* __restrict__ vals,
+                  Scal* __restrict__ scal) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+        const double x = pts[i * 3], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+        bad = !(finite64(x) && finite64(y) && finite64(z));
+        keys[i] = ordered_key(x == 0.0 ? 0.0 : x);  // -0.0 == +0.0: one key for both
+        vals[i] = (int)i;
+    }
+    if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(&scal->flags, (unsigned)FLAG_NONFINITE);
+}
+
+__global__ void __launch_bounds__(kT)
+ingest_gather_kernel(int n, const int* __restrict__ perm, const double* __restrict__ pts, const double* __restrict__ col,
+                     const int* __restrict__ lab, double* __restrict__ out_pts, float* __restrict__ out_col,
+                     unsigned char* __restrict__ out_lab, int* __restrict__ out_perm, unsigned long long* __restrict__ out_hist,
+                     Scal* __restrict__ scal) {
+    __shared__ unsigned long long s_min[kWaves], s_max[kWaves];
+    __shared__ unsigned s_hist[kHistBins];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long i = (long long)blockIdx.x * kT + tid;
+    const bool live = i < n;
+    if (tid < kHistBins) s_hist[tid] = 0u;
+    __syncthreads();
+    unsigned long long kmin = ~0ull, kmax = 0ull;
+    int bin = -1;  // histogram bin of this row's label; -1: counted nowhere
+    bool bad_label = false;
+    if (live) {
+        const long long src = perm[i];
+        const double x = pts[src * 3], y = pts[src * 3 + 1], z = pts[src * 3 + 2];
+        double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+        if (col) { c0 = col[src * 3]; c1 = col[src * 3 + 1]; c2 = col[src * 3 + 2]; }
+        const int L = lab ? lab[src] : 0;
+        out_pts[i * 3] = x; out_pts[i * 3 + 1] = y; out_pts[i * 3 + 2] = z;
+        if (col) { out_col[i * 3] = (float)c0; out_col[i * 3 + 1] = (float)c1; out_col[i * 3 + 2] = (float)c2; }
+        out_lab[i] = (unsigned char)L;
+        if (out_perm) out_perm[i] = (int)src;
+        kmin = kmax = ordered_key(z);
+        bad_label = L < 0 || L > 255;
+        bin = (L >= 0 && L <= 9) ? (L < 9 ? L : 8) : -1;  // np.histogram(labels, range(10)): the last bin is [8, 9]
+    }
+    // label histogram: per bin one ballot per wave, counted into LDS by the wave's first lane
+#pragma unroll
+    for (int b = 0; b < kHistBins; ++b) {
+        const unsigned long long m = __ballot(bin == b);
+        if (lane == 0 && m != 0ull) atomicAdd(&s_hist[b], (unsigned)__popcll(m));
+    }
+    const unsigned long long anybad = __ballot(bad_label);
+    if (lane == 0 && anybad != 0ull) atomicOr(&scal->flags, (unsigned)FLAG_LABEL);
+    // z range
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned long long a = __shfl_xor(kmin, o), b = __shfl_xor(kmax, o);
+        kmin = a < kmin ? a : kmin;
+        kmax = b > kmax ? b : kmax;
+    }
+    if (lane == 0) { s_min[wave] = kmin; s_max[wave] = kmax; }
+    __syncthreads();
+    if (tid == 0) {  // every workgroup holds at least one live row
+        unsigned long long lo = s_min[0], hi = s_max[0];
+        for (int w = 1; w < kWaves; ++w) { lo = s_min[w] < lo ? s_min[w] : lo; hi = s_max[w] > hi ? s_max[w] : hi; }
+        atomicMin(&scal->zmin, lo);
+        atomicMax(&scal->zmax, hi);
+    }
+    if (tid < kHistBins && s_hist[tid] != 0u) atomicAdd(&out_hist[tid], (unsigned long long)s_hist[tid]);
+}
+
+__global__ void ingest_finish_kernel(const Scal* __restrict__ scal, double* __restrict__ out_zrange, int* __restrict__ status) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    out_zrange[0] = ordered_to_double(scal->zmin);
+    out_zrange[1] = ordered_to_double(scal->zmax);
+    const unsigned f = scal->flags;
+    *status = (f & FLAG_NONFINITE) ? 1 : ((f & FLAG_LABEL) ? 2 : 0);
+}
+
+}  // namespace
+
+extern "C" int pn2_scene_ingest_workspace_size(int n, unsigned long long* bytes) {
+    if (n <= 0) return PN2_EINVAL;
+    if (!bytes) return PN2_ENULL;
+    Layout L;
+    const hipError_t e = layout(n, &L);
+    if (e != hipSuccess) return (int)e;
+    *bytes = (unsigned long long)L.total;
+    return PN2_OK;
+}
+
+extern "C" int pn2_scene_ingest(int n, const double* points, const double* colors, const int* labels, double* out_points,
+                                float* out_colors, unsigned char* out_labels, int* out_perm, double* out_zrange,
+                                long long* out_hist, int* status, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n <= 0) return PN2_EINVAL;
+    if (!points || !out_points || !out_labels || !out_zrange || !out_hist || !status || !workspace) return PN2_ENULL;
+    if (colors && !out_colors) return PN2_ENULL;
+    if ((((uintptr_t)points | (uintptr_t)colors | (uintptr_t)out_points | (uintptr_t)out_zrange | (uintptr_t)out_hist) & 7) != 0 ||
+        (((uintptr_t)labels | (uintptr_t)out_colors | (uintptr_t)out_perm | (uintptr_t)status) & 3) != 0 ||
+        ((uintptr_t)workspace & 255) != 0)
+        return PN2_EINVAL;
+    Layout L;
+    if (workspace_bytes < fixed_layout(n, &L)) return PN2_EINVAL;  // refused before the sort is asked for its share
+    const hipError_t le = layout(n, &L);
+    if (le != hipSuccess) return (int)le;
+    if (workspace_bytes < L.total) return PN2_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    unsigned long long* keys_in = reinterpret_cast<unsigned long long*>(ws + L.keys_in);
+    unsigned long long* keys_out = reinterpret_cast<unsigned long long*>(ws + L.keys_out);
+    int* vals_in = reinterpret_cast<int*>(ws + L.vals_in);
+    int* vals_out = reinterpret_cast<int*>(ws + L.vals_out);
+    Scal* scal = reinterpret_cast<Scal*>(ws + L.scal);
+    hipError_t e = hipMemsetAsync(&scal->zmin, 0xFF, sizeof(unsigned long long), st);  // running minimum: all ones
+    if (e == hipSuccess) e = hipMemsetAsync(&scal->zmax, 0, sizeof(Scal) - offsetof(Scal, zmax), st);  // maximum, flags
+    if (e == hipSuccess) e = hipMemsetAsync(out_hist, 0, kHistBins * sizeof(long long), st);
+    if (e != hipSuccess) return (int)e;
+    const int blocks = (int)(((long long)n + kT - 1) / kT);
+    ingest_key_kernel<<<blocks, kT, 0, st>>>(n, points, keys_in, vals_in, scal);
+    size_t cub = L.cub_bytes;
+    e = hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub, keys_in, keys_out, vals_in, vals_out, n, 0, 64, st);
+    if (e != hipSuccess) return (int)e;
+    ingest_gather_kernel<<<blocks, kT, 0, st>>>(n, vals_out, points, colors, labels, out_points, colors ? out_colors : nullptr,
+                                                out_labels, out_perm, reinterpret_cast<unsigned long long*>(out_hist), scal);
+    ingest_finish_kernel<<<1, 64, 0, st>>>(scal, out_zrange, status);
+    PN2_RETURN_IF_LAUNCH_FAILED();
+    return PN2_OK;
+}

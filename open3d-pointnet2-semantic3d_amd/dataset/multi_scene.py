@@ -18,6 +18,9 @@ angle) replays the reference's np.random draws instead (parity tests; costs host
 The host-side attributes (scene_probas, label_weights, counts, the split table) need no GPU; the store is uploaded on the
 first sample call.  Call it once eagerly before capturing it in a graph.  One call at a time per dataset object: the
 workspace is shared between calls.
+
+ingest="device" builds the store where it will lie instead (csrc/pn2_store.hip: sort by x, gather, z range and label
+histogram per scene in one call): the constructor then needs the GPU, and the per-scene arrays are views of the store.
 """
 import json
 import os
@@ -46,16 +49,42 @@ def default_splits():
     return out
 
 
-def label_weights_of(labels_per_scene):
-    """1 / log(1.2 + class frequency) over the scenes (semantic_dataset.py:280-290): np.histogram over range(10) (its last
-    bin is closed: labels 8 and 9 share it), summed in float64, cast to float32, normalised -> float32 (9,)."""
+def label_weights_from_counts(counts_per_scene):
+    """the second half of label_weights_of: per scene the nine counts of np.histogram(labels, range(10)) (the host path takes
+    them from numpy, the device path from pn2_scene_ingest) -> summed in float64, cast to float32, normalised -> float32 (9,)"""
     w = np.zeros(9)
-    for labels in labels_per_scene:
-        tmp, _ = np.histogram(labels, range(10))
+    for tmp in counts_per_scene:
         w += tmp
     w = w.astype(np.float32)
     w = w / np.sum(w)
     return 1 / np.log(1.2 + w)
+
+
+def label_weights_of(labels_per_scene):
+    """1 / log(1.2 + class frequency) over the scenes (semantic_dataset.py:280-290): np.histogram over range(10) (its last
+    bin is closed: labels 8 and 9 share it), summed in float64, cast to float32, normalised -> float32 (9,)."""
+    return label_weights_from_counts(np.histogram(labels, range(10))[0] for labels in labels_per_scene)
+
+
+_INGEST_RES = 12  # int64 words per scene that pn2_scene_ingest's small outputs share: zrange (2 float64), hist (9), status
+
+
+def _ingest_labels(labels, dev):
+    """labels of any integer or bool dtype, a tensor or an array -> int32 on dev.  A dtype wider than int32 is clamped to
+    [-1, 256] first: what lies outside [0, 255] stays outside, and nothing wraps into it."""
+    if not torch.is_tensor(labels):
+        labels = np.asarray(labels)
+        if labels.dtype.kind not in "iub":
+            raise ValueError("labels: an integer or bool dtype, got %s" % labels.dtype)
+        if labels.dtype.kind != "b" and labels.dtype.itemsize >= 4 and labels.dtype != np.int32:
+            labels = np.minimum(labels, 256) if labels.dtype.kind == "u" else np.clip(labels, -1, 256)
+        return torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(dev)
+    if labels.dtype.is_floating_point or labels.dtype.is_complex:
+        raise ValueError("labels: an integer or bool dtype, got %s" % labels.dtype)
+    labels = labels.to(dev)
+    if labels.dtype not in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32):
+        labels = labels.to(torch.int64).clamp(-1, 256)  # (an unsigned value that wraps lands on -1: still outside)
+    return labels.to(torch.int32).contiguous()
 
 
 def _rank_seed(seed):
@@ -66,10 +95,26 @@ def _rank_seed(seed):
 
 class SemanticDataset:
     def __init__(self, num_points_per_sample, split, use_color, box_size_x, box_size_y, path, device="cuda", seed=0,
-                 scenes=None, splits=None):
+                 scenes=None, splits=None, ingest="host", keep_perm=False):
         """The reference's constructor (semantic_dataset.py:214-290).  path/split: loads <path>/<name>.pcd and .labels for
         every scene name of the split (test: no labels).  scenes=[(points, labels, colors, name), ...]: the arrays
-        directly (labels / colors may be None).  splits: overrides the split -> scene-name table."""
+        directly (labels / colors may be None).  splits: overrides the split -> scene-name table.
+        ingest="host": the scenes are read, sorted by x and measured in numpy; scene_points / scene_labels / scene_colors are
+        host arrays and the store is uploaded by the first sample call.
+        ingest="device": the store is built in HBM by pn2_scene_ingest (csrc/pn2_store.hip), one call per scene, straight into
+        the scene's slice: files are read by scene_io.read_point_cloud_pcd / preprocess.load_labels, `scenes` may hold device
+        tensors (points float32 / float64, labels of any integer or bool dtype, colours float) or host arrays (uploaded once);
+        nothing of a scene's size comes back to the host.  scene_points / scene_labels / scene_colors are then device views of
+        the store (float64, uint8, float32; scene_colors[i] is None without colour).  Rows with equal x keep their input order
+        (a stable sort; numpy's default argsort on the host path leaves that order unspecified), so the two stores are equal
+        bit for bit wherever a scene's x values are distinct.  A NaN or an infinity in a coordinate is a ValueError.
+        keep_perm (ingest="device"): scene_perm[i], an int32 device tensor, maps a position in the sorted scene to its row in the
+        input (last_sel - scene_offsets[scene] indexes it)."""
+        if ingest not in ("host", "device"):
+            raise ValueError("ingest: 'host' or 'device', got %r" % (ingest,))
+        if keep_perm and ingest != "device":
+            raise ValueError("keep_perm needs ingest='device'")
+        self.ingest = ingest
         self.num_points_per_sample = int(num_points_per_sample)
         self.split = split
         self.use_color = bool(use_color)
@@ -86,54 +131,157 @@ class SemanticDataset:
             table = splits if splits is not None else default_splits()
             if split not in table:
                 raise ValueError("unknown split %r (known: %s)" % (split, sorted(table)))
-            scenes = []
-            for name in table[split]:
-                prefix = os.path.join(path, name)
-                pts, cols = read_point_cloud_pcd(prefix + ".pcd")
-                labels = load_labels(prefix + ".labels") if has_label else None
-                scenes.append((pts, labels, cols, name))
+            if ingest == "device":  # read scene by scene, straight into the store
+                scenes = [(None, None, None, name) for name in table[split]]
+            else:
+                scenes = []
+                for name in table[split]:
+                    prefix = os.path.join(path, name)
+                    pts, cols = read_point_cloud_pcd(prefix + ".pcd")
+                    labels = load_labels(prefix + ".labels") if has_label else None
+                    scenes.append((pts, labels, cols, name))
         if not scenes:
             raise ValueError("no scenes")
         self.scene_names, self.file_paths_without_ext = [], []
         self.scene_points, self.scene_labels, self.scene_colors = [], [], []
-        for pts, labels, cols, name in scenes:
-            pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
-            if len(pts) == 0:
-                raise ValueError("scene %r has no points" % (name,))
-            labels = np.zeros(len(pts), dtype=bool) if (labels is None or not has_label) else np.asarray(labels)
-            cols = np.asarray(cols, dtype=np.float64) if (cols is not None and self.use_color) else np.zeros_like(pts)
-            if labels.shape != (len(pts),) or cols.shape != pts.shape:
-                raise ValueError("scene %r: labels (n,) and colors (n,3) must match points (n,3)" % (name,))
-            sort_idx = np.argsort(pts[:, 0])  # SemanticFileData.__init__ (:84-88)
-            self.scene_points.append(np.ascontiguousarray(pts[sort_idx]))
-            self.scene_labels.append(np.ascontiguousarray(labels[sort_idx]))
-            self.scene_colors.append(np.ascontiguousarray(cols[sort_idx]))
-            self.scene_names.append(name)
-            self.file_paths_without_ext.append(os.path.join(path, name) if path else name)
-        self.num_scenes = len(self.scene_points)
-        self.scene_counts = np.array([len(p) for p in self.scene_points], dtype=np.int64)
+        self._store = None
+        if ingest == "device":
+            counts, z_size, hists = self._ingest_device(scenes, has_label, keep_perm)
+        else:
+            for pts, labels, cols, name in scenes:
+                pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+                if len(pts) == 0:
+                    raise ValueError("scene %r has no points" % (name,))
+                labels = np.zeros(len(pts), dtype=bool) if (labels is None or not has_label) else np.asarray(labels)
+                cols = np.asarray(cols, dtype=np.float64) if (cols is not None and self.use_color) else np.zeros_like(pts)
+                if labels.shape != (len(pts),) or cols.shape != pts.shape:
+                    raise ValueError("scene %r: labels (n,) and colors (n,3) must match points (n,3)" % (name,))
+                sort_idx = np.argsort(pts[:, 0])  # SemanticFileData.__init__ (:84-88)
+                self.scene_points.append(np.ascontiguousarray(pts[sort_idx]))
+                self.scene_labels.append(np.ascontiguousarray(labels[sort_idx]))
+                self.scene_colors.append(np.ascontiguousarray(cols[sort_idx]))
+                self.scene_names.append(name)
+                self.file_paths_without_ext.append(os.path.join(path, name) if path else name)
+            counts = [len(p) for p in self.scene_points]
+            # scene_z_size of _extract_z_box (:132), once per scene
+            z_size = [np.max(p, axis=0)[2] - np.min(p, axis=0)[2] for p in self.scene_points]
+        self.num_scenes = len(counts)
+        self.scene_counts = np.array(counts, dtype=np.int64)
         total = self.get_total_num_points()
         if total >= 2 ** 31:
             raise ValueError("the store holds at most 2^31 - 1 points")
-        self.scene_probas = np.array([len(p) / total for p in self.scene_points], dtype=np.float64)  # :268-271
+        self.scene_probas = np.array([c / total for c in counts], dtype=np.float64)  # :268-271
         cdf = self.scene_probas.cumsum()  # np.random.choice(..., p=scene_probas)
         self.scene_cdf = cdf / cdf[-1]
         self.scene_offsets = np.concatenate([[0], np.cumsum(self.scene_counts)]).astype(np.int64)
-        # scene_z_size of _extract_z_box (:132), once per scene
-        self.scene_z_size = np.array([np.max(p, axis=0)[2] - np.min(p, axis=0)[2] for p in self.scene_points])
-        if split in ("train", "train_full"):
-            self.label_weights = label_weights_of(self.scene_labels)
-        else:
+        self.scene_z_size = np.array(z_size)
+        if split not in ("train", "train_full"):
             self.label_weights = np.zeros(9)
-        for lab in self.scene_labels:
-            if lab.size and (lab.min() < 0 or lab.max() > 255):
-                raise ValueError("labels must lie in [0, 255]")
+        elif ingest == "device":
+            self.label_weights = label_weights_from_counts(hists)
+        else:
+            self.label_weights = label_weights_of(self.scene_labels)
+        if ingest == "host":  # (pn2_scene_ingest's status said the same of the device store)
+            for lab in self.scene_labels:
+                if lab.size and (lab.min() < 0 or lab.max() > 255):
+                    raise ValueError("labels must lie in [0, 255]")
         self.max_chunks = int(max(1, max((c + _CHUNK - 1) // _CHUNK for c in self.scene_counts)))
         self._dev = None
 
+    # ---- ingest="device" ---------------------------------------------------------------------------------------------
+    def _ingest_device(self, scenes, has_label, keep_perm):
+        """Builds the resident store (self._store: points (total,3) float64, colors (total,3) float32 or None, labels (total,)
+        uint8) with one pn2_scene_ingest call per scene, each writing its scene's slice, and sets the per-scene attributes to
+        views of it.  scenes: (points, labels, colors, name) with tensors or arrays, or (None, None, None, name) for a scene
+        read from <path>/<name>.pcd and .labels.  One workspace, sized for the largest scene, serves every call; per scene one
+        96-byte read-back (z range, label histogram, status).  -> counts [n], scene_z_size (ns,) float64, hists (ns,9) int64"""
+        from .. import preprocess, scene_io  # (they import this package's siblings: not at module level)
+        from ..util.point_cloud_util import read_pcd_header
+        dev = self.device
+        if dev.type != "cuda":
+            raise ValueError("ingest='device' builds the store on the MI355X: got device %s (there is no CPU path in the "
+                             "product; ingest='host' keeps the scenes in numpy)" % dev)
+        if dev.index is None:
+            dev = self.device = torch.device("cuda", torch.cuda.current_device())
+        counts = []
+        for pts, _, _, name in scenes:
+            if pts is None:
+                with open(os.path.join(self.path, name) + ".pcd", "rb") as f:
+                    n = read_pcd_header(f)[1]
+            else:
+                n = int(np.prod(tuple(pts.shape))) // 3 if hasattr(pts, "shape") else len(np.asarray(pts).reshape(-1, 3))
+            if n == 0:
+                raise ValueError("scene %r has no points" % (name,))
+            counts.append(n)
+        total = sum(counts)
+        if total >= 2 ** 31:
+            raise ValueError("the store holds at most 2^31 - 1 points")
+        ws_bytes, nbytes = 0, u64_array([0])
+        for n in sorted(set(counts)):  # (a host-side query; the sort's share need not grow with n)
+            launch("pn2_scene_ingest_workspace_size", dev, n, nbytes, stream=False)
+            ws_bytes = max(ws_bytes, int(nbytes[0]))
+        with torch.cuda.device(dev):
+            store = dict(points=torch.empty((total, 3), dtype=torch.float64, device=dev),
+                         colors=torch.empty((total, 3), dtype=torch.float32, device=dev) if self.use_color else None,
+                         labels=torch.empty((total,), dtype=torch.uint8, device=dev))
+            perm = torch.empty((total,), dtype=torch.int32, device=dev) if keep_perm else None
+            ws = torch.empty((ws_bytes + 256,), dtype=torch.uint8, device=dev)
+            ws = ws[(-ws.data_ptr()) % 256:]
+            res = torch.empty((len(scenes), _INGEST_RES), dtype=torch.int64, device=dev)
+        z_size, hists, o = [], [], 0
+        if keep_perm:
+            self.scene_perm = []
+        for k, ((pts, labels, cols, name), n) in enumerate(zip(scenes, counts)):
+            if pts is None:
+                prefix = os.path.join(self.path, name)
+                pts, cols = scene_io.read_point_cloud_pcd(prefix + ".pcd", dev, want_colors=self.use_color)
+                labels = preprocess.load_labels(prefix + ".labels", dev) if has_label else None
+            if torch.is_tensor(pts):
+                if not pts.dtype.is_floating_point:
+                    raise ValueError("scene %r: points float32 or float64, got %s" % (name, pts.dtype))
+                pts = pts.to(dev, torch.float64).reshape(-1, 3).contiguous()
+            else:
+                pts = torch.from_numpy(np.ascontiguousarray(np.asarray(pts, dtype=np.float64).reshape(-1, 3))).to(dev)
+            labels = None if (labels is None or not has_label) else _ingest_labels(labels, dev)
+            if cols is None or not self.use_color:
+                cols = None
+            elif torch.is_tensor(cols):
+                cols = cols.to(dev, torch.float64).contiguous()
+            else:
+                cols = torch.from_numpy(np.ascontiguousarray(cols, dtype=np.float64)).to(dev)
+            if pts.shape[0] != n or (labels is not None and tuple(labels.shape) != (n,)) or \
+                    (cols is not None and tuple(cols.shape) != (n, 3)):
+                raise ValueError("scene %r: labels (n,) and colors (n,3) must match points (n,3)" % (name,))
+            e = o + n
+            out_c = None if store["colors"] is None else store["colors"][o:e]
+            if out_c is not None and cols is None:
+                out_c.zero_()  # colour asked for, none given: zeros, as on the host path
+            launch("pn2_scene_ingest", dev, n, ptr(pts), ptr(cols), ptr(labels), ptr(store["points"][o:e]), ptr(out_c),
+                   ptr(store["labels"][o:e]), None if perm is None else ptr(perm[o:e]), ptr(res[k, 0:2]), ptr(res[k, 2:11]),
+                   ptr(res[k, 11:12]), ptr(ws), ws.numel())
+            r = res[k].cpu()  # the scene's one read-back; the inputs above may go once it has returned
+            status = int(r[11:12].view(torch.int32)[0])
+            if status == 1:
+                raise ValueError("scene %r: non-finite coordinate" % (name,))
+            if status == 2:
+                raise ValueError("labels must lie in [0, 255]")
+            zr = r[0:2].view(torch.float64).numpy()
+            z_size.append(zr[1] - zr[0])
+            hists.append(r[2:11].numpy().copy())
+            self.scene_points.append(store["points"][o:e])
+            self.scene_labels.append(store["labels"][o:e])
+            self.scene_colors.append(out_c)
+            if keep_perm:
+                self.scene_perm.append(perm[o:e])
+            self.scene_names.append(name)
+            self.file_paths_without_ext.append(os.path.join(self.path, name) if self.path else name)
+            o = e
+        self._store = store
+        return counts, np.array(z_size), np.array(hists, dtype=np.int64).reshape(-1, 9)
+
     # ---- the reference's small methods -------------------------------------------------------------------------------
     def get_total_num_points(self):
-        return np.sum([len(p) for p in self.scene_points])
+        return np.sum(self.scene_counts)
 
     def get_num_batches(self, batch_size):
         return int(self.get_total_num_points() / (batch_size * self.num_points_per_sample))
@@ -151,9 +299,13 @@ class SemanticDataset:
         dev = self.device
         if d is None:
             t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
-            d = dict(points=t(np.concatenate(self.scene_points), np.float64),
-                     colors=t(np.concatenate(self.scene_colors), np.float32) if self.use_color else None,
-                     labels=t(np.concatenate(self.scene_labels).astype(np.uint8), np.uint8),
+            if self._store is not None:  # ingest="device": the store already lies in HBM
+                big = self._store
+            else:
+                big = dict(points=t(np.concatenate(self.scene_points), np.float64),
+                           colors=t(np.concatenate(self.scene_colors), np.float32) if self.use_color else None,
+                           labels=t(np.concatenate(self.scene_labels).astype(np.uint8), np.uint8))
+            d = dict(points=big["points"], colors=big["colors"], labels=big["labels"],
                      offsets=t(self.scene_offsets, np.int32), cdf=t(self.scene_cdf, np.float64),
                      zsize=t(self.scene_z_size, np.float64), lw=t(self.label_weights, np.float32),
                      counter=torch.zeros(1, dtype=torch.int64, device=dev), workspaces={})
