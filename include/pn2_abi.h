@@ -1015,6 +1015,44 @@ int pn2_augment(int b, int n, int c, int flags, int rotate_axis, double perturb_
                 size_t workspace_bytes, double *out_params, int *out_perm, float *out, int *out_labels, float *out_weights,
                 void *stream);
 
+/* The per-frame front end of the KITTI flow (csrc/pn2_frame.hip): dataset/kitti_dataset.py:15-26 and :40-54 of the reference.
+ * Between the two calls the cropped frame is x-sorted by pn2_scene_ingest (stable, with out_perm).
+ *
+ * pn2_frame_crop: frame = n rows of float32, row stride row_floats >= 3 floats, x y z first (a KITTI .bin row is x y z intensity:
+ * row_floats = 4).  A row is kept iff lo <= p <= hi on all three axes, compared in float64, INCLUSIVE on both sides (the project's
+ * definition of Open3D's crop_point_cloud); a NaN or +-inf coordinate drops its row by the comparison.  Kept rows
+ * stay in frame order: out_points (n,3) float64 = the float32 values widened exactly, out_src (n) int32 = the frame row of each,
+ * *out_count (device int32) = how many; rows [count, n) of both outputs are not written.  Two launches, no host
+ * synchronisation.  workspace: 256-byte aligned, pn2_frame_crop_workspace_size(n) bytes (one sized for n serves any smaller n),
+ * nothing kept between calls.  n <= PN2_FRAME_MAX_ROWS, else PN2_ERANGE.
+ *
+ * pn2_frame_sample: points (cnt,3) float64, the cropped frame sorted by x; one sample of npts points of the whole frame.
+ *   cnt <= npts          out_sel[j] = j mod cnt (the reference's doubling loop; cnt == npts takes this branch, unshuffled).
+ *   cnt > npts, mask     replay: mask = cnt bytes, the reference's shuffled boolean mask; out_sel = its set positions, ascending.
+ *                        A mask that does not select exactly npts: status PN2_FRAME_ST_MASK.
+ *   cnt > npts, no mask  the npts smallest of the keys draw64(sample_stream(seed, *counter, 0), i), i in [0, cnt), ties broken
+ *                        by index, emitted in ascending index order (csrc/pn2_rng.h; the subset-key index space of
+ *                        pn2_dataset_sample).  PN2_FRAME_ST_CAND: more than 4096 keys share the deciding 12-bit bin (about
+ *                        cnt / 4096 are expected).
+ *   mask == NULL (either count): the last launch advances *counter (device int64) by one, so a captured call replays into fresh
+ *   subsets.  With a mask, counter is not touched and may be NULL.
+ * box_min = the float64 minimum over the SAMPLED points; shift = (min_x + box_size_x / 2, min_y + box_size_y / 2, min_z);
+ * out_centered (npts,3) float32 = float32(p - shift), the subtraction in float64; out_raw (npts,3) float64 = the points;
+ * status (1) int32.  With a non-zero status all three outputs are zero-filled.  At most four launches and two memsets, no host
+ * synchronisation; workspace: 256-byte aligned, pn2_frame_sample_workspace_size(cnt) bytes, cleared by the call itself. */
+#define PN2_FRAME_MAX_ROWS 16777216
+#define PN2_FRAME_ST_OK 0
+#define PN2_FRAME_ST_MASK 3
+#define PN2_FRAME_ST_CAND 4
+int pn2_frame_crop_workspace_size(int n, unsigned long long *bytes);
+int pn2_frame_crop(int n, const float *frame, int row_floats, double lo_x, double lo_y, double lo_z, double hi_x, double hi_y,
+                   double hi_z, double *out_points, int *out_src, int *out_count, void *workspace, size_t workspace_bytes,
+                   void *stream);
+int pn2_frame_sample_workspace_size(int cnt, unsigned long long *bytes);
+int pn2_frame_sample(int cnt, int npts, const double *points, const unsigned char *mask, double box_size_x, double box_size_y,
+                     unsigned long long seed, long long *counter, void *workspace, size_t workspace_bytes, int *out_sel,
+                     float *out_centered, double *out_raw, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

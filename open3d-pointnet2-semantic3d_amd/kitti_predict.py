@@ -1,0 +1,46 @@
+"""Labels for KITTI LiDAR frames: the reference's kitti_predict.py (PredictInterpolator), without its visualiser.
+
+    predictor = PredictInterpolator(checkpoint_path, dataset.num_classes, model.SEMANTIC_NO_COLOR_HYPERPARAMS)
+    for frame in dataset.list_file_data:                                  # dataset.KittiDataset
+        dense_labels, dense_colors = predictor.label_frame(frame)         # one label per point of frame.points
+
+Per frame: one sample of num_point points (dataset.KittiFileData.get_batch_of_one_z_box_from_origin), the colourless forward
+and argmax (predict.Predictor: one captured graph per batch shape, replayed for every later frame), and the 3-NN vote of the
+sparse labels onto the whole cropped frame (interpolate_label_with_color).  Nothing is captured here and no stream is made:
+the Predictor is used as it is.  After the frame's construction nothing on this path waits for the device.
+"""
+import torch
+
+from .predict import Predictor, _on_device
+
+
+class PredictInterpolator:
+    """kitti_predict.py:30-104.  checkpoint_path: a file written by train.Trainer.save(), or None for fresh variables."""
+
+    def __init__(self, checkpoint_path, num_classes, hyper_params, device="cuda"):
+        self.hp = dict(hyper_params)
+        self.predictor = Predictor(checkpoint_path, num_classes, self.hp, device=device)
+        self.device = self.predictor.device
+
+    def predict_and_interpolate(self, sparse_points_centered_batched, sparse_points_batched, dense_points):
+        """sparse_points_centered_batched (B,N,3): the network's input; sparse_points_batched (B,N,3): the same points
+        uncentred; dense_points (nd,3).  Device tensors or numpy arrays of any float dtype: they are cast to float32, as the
+        reference's placeholders do (:35,57,59).  Any batch is flattened to (B*N,3) sparse points (:49,58).
+        -> dense_labels (nd,) int32, dense_colors (nd,3) uint8 on the device: the majority label of the 3 nearest sparse points
+        (:100) and its colour."""
+        sparse_labels = self.predictor.predict(_on_device(sparse_points_centered_batched, torch.float32, self.device))
+        sparse_points = _on_device(sparse_points_batched, torch.float32, self.device).reshape(-1, 3)
+        return self.predictor.interpolate_labels(sparse_points, sparse_labels.reshape(-1), dense_points)
+
+    def label_frame(self, file_data):
+        """(extension) a dataset.KittiFileData -> (dense_labels, dense_colors) for file_data.points: the body of the reference's
+        frame loop (:175-191)"""
+        centered, raw = file_data.get_batch_of_one_z_box_from_origin(self.hp["num_point"])
+        return self.predict_and_interpolate(centered, raw, file_data.points)
+
+    def labels_for_raw_frame(self, file_data, dense_labels, n):
+        """(extension) dense_labels (cnt,) of file_data.points scattered back to the n rows of the raw frame -> (n,) int32, -1
+        for the rows the crop dropped"""
+        out = torch.full((int(n),), -1, dtype=torch.int32, device=dense_labels.device)
+        out[file_data.source_index.long()] = dense_labels.to(torch.int32)
+        return out

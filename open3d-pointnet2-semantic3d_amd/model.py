@@ -25,6 +25,9 @@ SEMANTIC_HYPERPARAMS = {
     "l3_radius": 2.0, "l3_nsample": 32, "l3_npoint": 64,
     "l4_radius": 4.0, "l4_nsample": 32, "l4_npoint": 16,
 }
+# semantic_no_color.json of the reference (the configuration kitti_predict.py loads): the same values without colour, and the box
+# the KITTI frames are cropped to (box_size_x / box_size_y, :17-18 there)
+SEMANTIC_NO_COLOR_HYPERPARAMS = dict(SEMANTIC_HYPERPARAMS, use_color=0, box_size_x=60, box_size_y=20)
 
 SA_MLPS = ([32, 32, 64], [64, 64, 128], [128, 128, 256], [256, 256, 512])  # model.py:36-87
 FP_MLPS = ([256, 256], [256, 256], [256, 128], [128, 128, 128])            # model.py:90-129

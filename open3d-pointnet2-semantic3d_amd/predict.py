@@ -10,8 +10,8 @@ labels onto the dense cloud with 3-NN and evaluates against the dense ground tru
 
 Every step stays on the device: the batches come from dataset.SemanticDataset.sample_batch_in_file, forward + argmax are one
 captured graph per batch shape, the label pairs are counted by pn2_label_confusion (util.metric.ConfusionMatrix with device
-storage) and the vote is tf_ops.tf_interpolate.interpolate_label_with_color over chunks of the dense cloud.  The Semantic3D
-flow (use_color = 1) is what this module is tested on.
+storage) and the vote is tf_ops.tf_interpolate.interpolate_label_with_color over chunks of the dense cloud.  It is tested
+on the Semantic3D flow (use_color = 1) and, through kitti_predict.PredictInterpolator, on the colourless KITTI flow.
 """
 import numpy as np
 import torch
