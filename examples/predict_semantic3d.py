@@ -12,7 +12,12 @@
     --raw PATH    the dense clouds, <PATH>/<scene>.pcd and, where they exist, .labels (dataset/semantic_raw)
     without --data / --raw: small synthetic scenes -- a raw cloud as the dense side, its down_sample_arrays result as the store
 
+    --tiled       instead of num_samples random columns, the tiled cover of the scene (pn2.predict.predict_scene_tiled): every
+                  point of the store is predicted --phases times (1: one grid; 2: a second grid shifted by half a box votes
+                  too) and the sparse side of the 3-NN vote is the whole store; columns below --min-points points are skipped
+
 usage: python examples/predict_semantic3d.py [--ckpt FILE] [--set validation] [--num_samples 8] [--data PATH --raw PATH]
+       [--tiled [--phases 1|2] [--min-points K]]
        size flags (synthetic runs, tests): --points N --npoint a,b,c,d --scene-points P --scenes K --voxel V --batch-size B"""
 import argparse
 import os
@@ -89,6 +94,9 @@ def main():
     ap.add_argument("--chunk", type=int, default=1 << 24, help="dense points per interpolation call")
     ap.add_argument("--ingest", choices=("host", "device"), default="host",
                     help="where the store is sorted and measured: numpy, or pn2_scene_ingest straight into HBM")
+    ap.add_argument("--tiled", action="store_true", help="label every point of the store: the tiled cover, not random columns")
+    ap.add_argument("--phases", type=int, choices=(1, 2), default=1, help="--tiled: grids that vote (2: one shifted by half a box)")
+    ap.add_argument("--min-points", type=int, default=1, help="--tiled: columns with fewer points are skipped")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     hp = dict(pn2.model.SEMANTIC_HYPERPARAMS)
@@ -113,10 +121,18 @@ def main():
         print("Processing %s" % name)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        points, labels = pn2.predict.predict_scene(predictor, dataset, k, args.num_samples, args.batch_size, confusion=cm_sparse)
-        dataset.check_last()
-        torch.cuda.synchronize()
-        print("    %d samples of %d points in %.1f ms" % (args.num_samples, hp["num_point"], (time.perf_counter() - t0) * 1e3))
+        if args.tiled:
+            phases = [(0.0, 0.0), (hp["box_size_x"] / 2, hp["box_size_y"] / 2)][:args.phases]
+            labels, _ = pn2.predict.predict_scene_tiled(predictor, dataset, k, args.batch_size, phases, args.min_points,
+                                                        confusion=cm_sparse)
+            points = torch.as_tensor(dataset.scene_points[k]).to(dev, torch.float32)  # the whole store is the sparse side
+            torch.cuda.synchronize()
+            print("    %d points, %d grid(s) of columns in %.1f ms" % (len(points), len(phases), (time.perf_counter() - t0) * 1e3))
+        else:
+            points, labels = pn2.predict.predict_scene(predictor, dataset, k, args.num_samples, args.batch_size, confusion=cm_sparse)
+            dataset.check_last()
+            torch.cuda.synchronize()
+            print("    %d samples of %d points in %.1f ms" % (args.num_samples, hp["num_point"], (time.perf_counter() - t0) * 1e3))
         pn2.write_point_cloud_pcd(os.path.join(sparse_dir, name + ".pcd"), points)
         pn2.write_labels(os.path.join(sparse_dir, name + ".labels"), labels)
         print("    Exported sparse pcd and labels to %s" % os.path.join(sparse_dir, name))

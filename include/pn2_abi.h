@@ -1053,6 +1053,65 @@ int pn2_frame_sample(int cnt, int npts, const double *points, const unsigned cha
                      unsigned long long seed, long long *counter, void *workspace, size_t workspace_bytes, int *out_sel,
                      float *out_centered, double *out_raw, int *status, void *stream);
 
+/* The tiled cover of one scene of the store (csrc/pn2_tile.hip): every point of the scene predicted once per pass, where
+ * predict.py's random columns leave coverage to chance.  The scene is cut into the box_size_x x box_size_y columns the network
+ * is trained on, every column into as many npts-sized samples as it takes to use each of its points once; each prediction is
+ * written back to the point it came from, and passes on shifted grids vote.  The rule (tests/tile_ref.py is its numpy model):
+ *
+ * pn2_tile_plan: points (n,3) float64, sorted by x ascending as the store keeps them.
+ *   grid     ox = points[0,0] - phase_x, oy = min(points[:,1]) - phase_y: the minimum over float64 values, -0.0 the smaller of
+ *            two zeros; one float64 subtraction each.  Point p lies in tile (i, j) = (floor((p.x - ox) / box_size_x),
+ *            floor((p.y - oy) / box_size_y)): a float64 subtraction, a float64 DIVISION (never a product with a reciprocal),
+ *            floor.  A point exactly on a boundary belongs to the upper tile.  phase >= 0 keeps both indices >= 0.
+ *   order    (n) int32: the scene positions sorted by (i, j) ascending, equal tiles in ascending position (stable).  A tile is a
+ *            maximal run of equal (i, j) in order: its start a, its size m.
+ *   samples  (sample_cap,4) int32, rows [a, m, s, S]: a tile with m < min_points has none (its m points are counted as
+ *            skipped), any other S = ceil(m / npts) of them, s = 0 .. S-1, listed tile by tile.  Sample s owns the members of
+ *            rank r = s (mod S): c = ceil((m - s) / S) <= npts of them.  Row k of [0, npts) of the sample is scene position
+ *            order[a + s + (k mod c) * S]; rows k < c are LIVE (the one occurrence of their point in this pass), rows k >= c
+ *            the cyclic refill (the doubling loop of semantic_dataset.py:101-106): they feed the network and never vote.  With
+ *            min_points = 1 every point of the scene is live in exactly one row of exactly one sample.
+ *   header   (8) int32 = [n_tiles, n_samples, skipped_points, status, 0, 0, 0, 0]: n_tiles counts every occupied tile, skipped
+ *            ones included; n_samples is the true total even beyond sample_cap (the caller can plan again).
+ *   status   0 ok; 1 a NaN or +-inf in an x or y; 2 a tile index outside [0, 2^31); 3 n_samples > sample_cap (rows
+ *            [0, sample_cap) are written); the lowest non-zero code wins.  With status 1 or 2 order and samples are written
+ *            inside their bounds, but what they hold is not specified.
+ * Eight launches, two memsets and a radix sort (hipcub, 64 key bits, stable); every reduction is in integers or ordered keys.  No host
+ * synchronisation, no allocation; workspace 256-byte aligned, pn2_tile_plan_workspace_size(n) bytes, cleared by the call, nothing
+ * kept between calls.  sample_cap = 0 (samples may be NULL) only counts.
+ * PN2_EINVAL: n, npts <= 0, min_points < 1, sample_cap < 0, a box size that is not positive and finite, a phase that is not
+ * finite and >= 0, a workspace too small, a misaligned pointer (samples: 16 bytes); PN2_ERANGE: n or npts >
+ * PN2_FRAME_MAX_ROWS; PN2_ENULL: points, order, header or workspace NULL, samples NULL with sample_cap > 0.
+ *
+ * pn2_tile_gather: the batch of the b samples q0 .. q0 + b - 1 of a plan; n_samples and the status are read from the plan's
+ * device header, not passed by the host.  For slot i, sample q = q0 + i:
+ *   box_min = the float64 minimum over the sample's rows (-0.0 the smaller of two zeros); shift = (min_x + box_size_x / 2,
+ *   min_y + box_size_y / 2, min_z) as _center_box (semantic_dataset.py:109-121);
+ *   out_data (b,npts,3|6) float32: [k,0:3] = float32(p - shift), the subtraction in float64 and one rounding; [k,3:6] the
+ *   float32 colour, copied, with use_color (colors (n,3) float32); out_sel (b,npts) int32 = the scene position of each row;
+ *   out_live (b) int32 = c.
+ *   A slot with q >= n_samples is a copy of sample n_samples - 1 with live = 0, so the ragged last batch keeps the full batch
+ *   shape; with n_samples = 0, or a plan whose status is not 0, every slot is zero-filled with sel = -1 and live = 0.
+ * One launch.  PN2_EINVAL: b, npts <= 0, q0 < 0, a bad box size, a misaligned pointer; PN2_ERANGE: npts > PN2_FRAME_MAX_ROWS,
+ * b > 65535 or b * npts >= 2^31; PN2_ENULL: a NULL pointer (colors only with use_color).
+ *
+ * pn2_tile_vote: votes (n,num_class) int32: votes[sel, pred] += 1 for every live row (k < live[q]) of the batch whose prediction
+ * lies in [0, num_class); a live row whose prediction does not (or whose sel is negative) is left out and, when dropped != NULL,
+ * counted there.  Rows k >= live[q] are ignored.  votes and *dropped accumulate across calls and are never zeroed here.  Integer
+ * adds only: the result does not depend on arrival order.  One launch.  PN2_EUNSUP: num_class > 64.
+ *
+ * pn2_tile_labels: labels[i] = the first maximal class of votes[i, :] (np.argmax); a point without any vote gets 0. */
+int pn2_tile_plan_workspace_size(int n, unsigned long long *bytes);
+int pn2_tile_plan(int n, const double *points, double box_size_x, double box_size_y, double phase_x, double phase_y, int npts,
+                  int min_points, int sample_cap, int *order, int *samples, int *header, void *workspace,
+                  size_t workspace_bytes, void *stream);
+int pn2_tile_gather(int b, int npts, int q0, int use_color, const double *points, const float *colors, const int *order,
+                    const int *samples, const int *header, double box_size_x, double box_size_y, float *out_data, int *out_sel,
+                    int *out_live, void *stream);
+int pn2_tile_vote(int b, int npts, int num_class, const int *sel, const int *live, const int *pred, int *votes,
+                  long long *dropped, void *stream);
+int pn2_tile_labels(int n, int num_class, const int *votes, int *labels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

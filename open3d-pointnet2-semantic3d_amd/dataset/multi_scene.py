@@ -441,9 +441,75 @@ class SemanticDataset:
         self.last_status, self.last_angle = info[:, 7], finfo[:, 0]
         return data, points_raw, label
 
+    def tile_cover(self, scene, phase=(0.0, 0.0), min_points=1):
+        """The tiled cover of scene `scene` (pn2_tile_plan, csrc/pn2_tile.hip): the scene cut into box_size_x x box_size_y
+        columns on a grid shifted by `phase` (metres, >= 0), every column with at least min_points points split into as many
+        num_points_per_sample-sized samples as it takes to use each of its points once.  -> TileCover.  One plan call and one
+        32-byte read-back (the header); works on ingest="host" (the store is uploaded first) and ingest="device" stores."""
+        scene = int(scene)
+        if not 0 <= scene < self.num_scenes:
+            raise ValueError("scene %d: the store holds scenes 0 .. %d" % (scene, self.num_scenes - 1))
+        px, py = float(phase[0]), float(phase[1])
+        if not (0.0 <= px < float("inf") and 0.0 <= py < float("inf")):
+            raise ValueError("phase: two finite offsets >= 0, got %r" % (phase,))
+        if int(min_points) < 1:
+            raise ValueError("min_points must be at least 1")
+        v = self._scene_view(self._upload(1), scene)
+        return TileCover(self, scene, v["points"], v["colors"], (px, py), int(min_points))
+
     def check_last(self):
         """raise if a sample of the last batch was rejected (zero-filled); one host synchronisation."""
         st = self.last_status.cpu().tolist()
         if any(st):
             raise RuntimeError("SemanticDataset: rejected samples: %s" % {i: STATUS_NAMES.get(v, v) for i, v in enumerate(st) if v})
 
+
+
+TILE_STATUS_NAMES = {1: "non-finite x or y", 2: "tile index outside [0, 2^31)", 3: "more samples than the table holds"}
+
+
+class TileCover:
+    """One pass of the tiled cover of a scene (SemanticDataset.tile_cover): `order` (n,) int32, `samples` (num_samples,4) int32
+    rows [a, m, s, S] and `header` (8,) int32 on the device, as pn2_tile_plan leaves them (include/pn2_abi.h has the rule), and
+    from the header's one read-back num_tiles, num_samples and skipped_points.  Sample q holds num_points_per_sample rows of
+    one column; its first live[q] rows are the one occurrence of their points in this pass, the rest repeat them."""
+
+    def __init__(self, dataset, scene, points, colors, phase, min_points):
+        dev = dataset.device
+        n, npts = int(points.shape[0]), dataset.num_points_per_sample
+        self.scene, self.phase, self.min_points, self.num_points = scene, phase, min_points, n
+        self.num_points_per_sample = npts
+        self.box_size_x, self.box_size_y = float(dataset.box_size_x), float(dataset.box_size_y)
+        self.use_color = dataset.use_color
+        self._points, self._colors, self._dev = points, colors if dataset.use_color else None, dev
+        nbytes = u64_array([0])
+        launch("pn2_tile_plan_workspace_size", dev, n, nbytes, stream=False)
+        with torch.cuda.device(dev):
+            ws = torch.empty((int(nbytes[0]) + 256,), dtype=torch.uint8, device=dev)
+            ws = ws[(-ws.data_ptr()) % 256:]
+            self.order = torch.empty((n,), dtype=torch.int32, device=dev)
+            self.header = torch.empty((8,), dtype=torch.int32, device=dev)
+            # every sample holds at least one point of its own: n rows hold any table (cut to num_samples rows below)
+            table = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        launch("pn2_tile_plan", dev, n, ptr(points), self.box_size_x, self.box_size_y, phase[0], phase[1], npts, min_points, n,
+               ptr(self.order), ptr(table), ptr(self.header), ptr(ws), ws.numel())
+        h = self.header.cpu().tolist()  # the one host read of the pass
+        if h[3] != 0:
+            raise ValueError("scene %r: %s" % (dataset.scene_names[scene], TILE_STATUS_NAMES.get(h[3], h[3])))
+        self.num_tiles, self.num_samples, self.skipped_points = h[0], h[1], h[2]
+        self.samples = table[:max(self.num_samples, 1)].clone()  # (one row at least: a pointer for an empty table)
+
+    def batch(self, q0, batch_size):
+        """-> data (B,N,6|3) float32 (centred xyz [| rgb]), sel (B,N) int32 (positions in the x-sorted scene), live (B,) int32
+        for samples q0 .. q0 + B - 1 (pn2_tile_gather).  A slot beyond the last sample repeats it with live = 0 (every batch
+        has the full shape); a cover without samples gives zeros, sel = -1, live = 0.  No host synchronisation."""
+        b, npts, dev = int(batch_size), self.num_points_per_sample, self._dev
+        if b <= 0 or int(q0) < 0:
+            raise ValueError("batch_size must be positive and q0 non-negative")
+        data = torch.empty((b, npts, 6 if self.use_color else 3), dtype=torch.float32, device=dev)
+        sel = torch.empty((b, npts), dtype=torch.int32, device=dev)
+        live = torch.empty((b,), dtype=torch.int32, device=dev)
+        launch("pn2_tile_gather", dev, b, npts, int(q0), int(self.use_color), ptr(self._points), ptr(self._colors),
+               ptr(self.order), ptr(self.samples), ptr(self.header), self.box_size_x, self.box_size_y, ptr(data), ptr(sel),
+               ptr(live))
+        return data, sel, live

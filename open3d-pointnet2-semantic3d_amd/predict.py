@@ -195,3 +195,42 @@ def label_dense(sparse_points, sparse_labels, dense_points, dense_gt_labels=None
             # int64 ground truth stays int64: a value beyond int32 must be dropped, not wrapped into a class
             confusion.increment_from_list(_on_device(gt, torch.int64 if wide else torch.int32, dev), labels[lo:hi])
     return labels, colors
+
+
+def predict_scene_tiled(predictor, dataset, scene, batch_size=64, phases=((0.0, 0.0),), min_points=1, confusion=None):
+    """A label for every point of scene `scene` of a dataset.SemanticDataset: the whole-scene evaluation of PointNet++'s
+    ScanNet code on this network's columns, where predict_scene leaves coverage to its random draws.  Per phase (a grid shift
+    in metres, >= 0) the scene is cut into box_size_x x box_size_y columns, every column with at least min_points points into
+    as many num_point-sized samples as it takes to use each of its points once (dataset.tile_cover: pn2_tile_plan); the samples
+    are predicted in batches of exactly batch_size (the last one padded with a repeated sample that does not vote, so the
+    predictor captures ONE graph), and every prediction is added to its point's row of `votes` (pn2_tile_vote).  The label of a
+    point is the first class with the most votes over all phases; a point nobody voted for (a column below min_points in every
+    phase) gets 0, "unlabeled".  phases=((0, 0), (box_size_x / 2, box_size_y / 2)) is the usual overlapping cover.
+    -> labels (n,) int32, votes (n, num_classes) int32, on the device, aligned with dataset.scene_points[scene] (the scene
+    sorted by x): with ingest="device", keep_perm=True, labels[i] belongs to input row dataset.scene_perm[scene][i], so
+    out = torch.empty_like(labels); out[dataset.scene_perm[scene].long()] = labels is in input order.
+    confusion (util.metric.ConfusionMatrix): counts the (scene label, final label) pair of every point, once.
+    Per phase one 32-byte read-back (the plan's header: how many batches to launch); the batch loop does not wait for the
+    device, apart from the capture of a batch shape the predictor has not seen."""
+    from ._lib import launch, ptr
+    batch_size = int(batch_size)
+    if batch_size <= 0:
+        raise ValueError("batch_size must be positive")
+    phases = [(float(p[0]), float(p[1])) for p in phases]
+    if not phases:
+        raise ValueError("phases: at least one (phase_x, phase_y)")
+    dev, c, npts = predictor.device, predictor.num_classes, dataset.num_points_per_sample
+    n = int(dataset.scene_counts[int(scene)])
+    votes = torch.zeros((n, c), dtype=torch.int32, device=dev)
+    labels = torch.empty((n,), dtype=torch.int32, device=dev)
+    for phase in phases:
+        cover = dataset.tile_cover(scene, phase, min_points)
+        for q0 in range(0, cover.num_samples, batch_size):
+            data, sel, live = cover.batch(q0, batch_size)
+            pred = predictor.predict(data)
+            launch("pn2_tile_vote", dev, batch_size, npts, c, ptr(sel), ptr(live), ptr(pred), ptr(votes), None)
+    launch("pn2_tile_labels", dev, n, c, ptr(votes), ptr(labels))
+    if confusion is not None:
+        gt = dataset.scene_labels[int(scene)]
+        confusion.increment_from_list(_on_device(gt, torch.int32, dev), labels)
+    return labels, votes
