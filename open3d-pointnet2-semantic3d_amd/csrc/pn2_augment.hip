@@ -15,6 +15,7 @@
 //                    any element-aligned base works.
 #include "pn2_common.h"
 #include "pn2_rng.h"
+#include "pn2_wg.h"  // al256
 
 namespace {
 
@@ -25,7 +26,6 @@ constexpr unsigned long long kTag = 1ull << 41;
 constexpr unsigned long long kTagAngle = kTag, kTagPerturb = kTag + 2, kTagScale = kTag + 8, kTagShift = kTag + 9,
                              kTagRatio = kTag + 12, kTagJitter = 2 * kTag, kTagDrop = 4 * kTag, kTagPerm = 8 * kTag;
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 // workspace: [counter snapshot | params (b, kP) f64 | row 0 of every cloud (b, PN2_AUG_INPLACE_MAX_C) f32]
 inline size_t ws_params_off() { return 256; }
 inline size_t ws_row0_off(int b) { return 256 + al256((size_t)b * kP * 8); }

@@ -22,6 +22,8 @@
 #include "pn2_common.h"
 #include "pn2_ordered.h"  // ordered_key, ordered_to_double
 #include "pn2_rng.h"
+#include "pn2_subset.h"  // the exact-N key selection of launches 1-3: kBinBits, kBins, kCandCap, subset_*
+#include "pn2_wg.h"
 
 namespace {
 
@@ -29,9 +31,6 @@ constexpr int kT = 256;             // threads per workgroup
 constexpr int kWaves = kT / 64;
 constexpr int kChunk = 1024;        // slab points per chunk (4 ordered passes of kT)
 constexpr int kG = 64;              // workgroups per sample in launches 1-3
-constexpr int kBinBits = 12;
-constexpr int kBins = 1 << kBinBits;
-constexpr int kCandCap = 4096;      // candidates (members in bin T) per sample; ~cnt / 4096 expected
 constexpr int kInfo = 8;            // ints per sample: scene, centre, cnt, slab lo, slab hi, T, need, status
 constexpr int kFInfo = 3;           // doubles per sample: angle, cos, sin
 enum { I_SCENE, I_CENTER, I_CNT, I_LO, I_HI, I_T, I_NEED, I_STATUS };
@@ -48,24 +47,18 @@ struct Ws {  // workspace carve-up; hist and ncand are kept zero between batches
     int* defcnt;                     // b * max_chunks
     unsigned long long* mins;        // b * 3 ordered float64 keys
 };
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline size_t ws_layout(int b, int max_chunks, unsigned char* base, Ws* w) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { unsigned char* p = base ? base + o : nullptr; o += al256(bytes); return p; };
-    unsigned char* h = take((size_t)b * kBins * 4);
-    unsigned char* nc = take((size_t)b * 4);
-    unsigned char* ck = take((size_t)b * kCandCap * 8);
-    unsigned char* ci = take((size_t)b * kCandCap * 4);
-    unsigned char* mc = take((size_t)b * max_chunks * 4);
-    unsigned char* dc = take((size_t)b * max_chunks * 4);
-    unsigned char* mn = take((size_t)b * 3 * 8);
-    if (w) {
-        w->hist = reinterpret_cast<unsigned*>(h); w->ncand = reinterpret_cast<unsigned*>(nc);
-        w->cand_key = reinterpret_cast<unsigned long long*>(ck); w->cand_idx = reinterpret_cast<int*>(ci);
-        w->memcnt = reinterpret_cast<int*>(mc); w->defcnt = reinterpret_cast<int*>(dc);
-        w->mins = reinterpret_cast<unsigned long long*>(mn);
-    }
-    return o;
+    WsCarver c{base};
+    Ws t;
+    t.hist = c.take<unsigned>((size_t)b * kBins);
+    t.ncand = c.take<unsigned>((size_t)b);
+    t.cand_key = c.take<unsigned long long>((size_t)b * kCandCap);
+    t.cand_idx = c.take<int>((size_t)b * kCandCap);
+    t.memcnt = c.take<int>((size_t)b * max_chunks);
+    t.defcnt = c.take<int>((size_t)b * max_chunks);
+    t.mins = c.take<unsigned long long>((size_t)b * 3);
+    if (w) *w = t;
+    return c.used;
 }
 
 struct Store {
@@ -88,15 +81,6 @@ struct Draws {  // replay inputs (all NULL: device random numbers from seed and 
 
 // fmix64, sample_stream, draw64, unit53: csrc/pn2_rng.h.  Tags of the per-sample draws live above every point index
 constexpr unsigned long long kTagScene = 1ull << 40, kTagCenter = kTagScene + 1, kTagAngle = kTagScene + 2;
-
-// first index i in [lo, hi) with x[3*i] >= v (np.searchsorted(points[:, 0], v), side='left', inside one scene segment)
-__device__ __forceinline__ int lower_bound_x(const double* __restrict__ pts, int lo, int hi, double v) {
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (pts[(size_t)mid * 3] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 struct Column {
     int scene, center, lo, hi;        // scene, scene-local centre index, global slab [lo, hi)
@@ -140,37 +124,6 @@ __device__ __forceinline__ bool in_column(const Column& c, const double* __restr
     return (x >= c.b0) & (x <= c.e0) & (y >= c.b1) & (y <= c.e1) & (z >= c.b2) & (z <= c.e2);  // :146-153
 }
 
-// exclusive prefix of per-thread flags over the workgroup (thread order); `total` = workgroup sum.  wsum: kWaves ints.
-__device__ __forceinline__ int wg_excl_scan(int flag, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(flag);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const int v = wsum[w];
-        if (w < wave) base += v;
-        tot += v;
-    }
-    __syncthreads();
-    total = tot;
-    return base + before;
-}
-
-// workgroup sum of a per-thread int; red: kWaves ints
-__device__ __forceinline__ long long wg_sum(long long v, long long* red) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long t = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) t += red[w];
-    __syncthreads();
-    return t;
-}
 
 __device__ __forceinline__ int num_chunks(const Column& c) { return (c.hi - c.lo + kChunk - 1) / kChunk; }
 
@@ -212,10 +165,10 @@ ds_count_kernel(Store st, Draws dr, unsigned long long seed, const long long* __
             const int i = c.lo + ch * kChunk + it * kT + tid;
             if (in_column(c, st.pts, i)) {
                 ++mine;
-                if (!replay) atomicAdd(&lhist[draw64(c.h, (unsigned long long)(i - o0)) >> (64 - kBinBits)], 1u);
+                if (!replay) atomicAdd(&lhist[subset_bin(draw64(c.h, (unsigned long long)(i - o0)))], 1u);
             }
         }
-        const long long tot = wg_sum(mine, red);
+        const long long tot = wg_sum<kWaves, long long>(mine, red);
         if (tid == 0) ws.memcnt[s * max_chunks + ch] = (int)tot;
         any = any || tot > 0;
     }
@@ -233,6 +186,7 @@ ds_select_kernel(Store st, Draws dr, unsigned long long seed, const long long* _
                  double hy, int max_chunks, Ws ws, int* __restrict__ info) {
     __shared__ long long red[kWaves];
     __shared__ int wsum[kWaves];
+    __shared__ int sums[kT];
     __shared__ int s_T, s_below;
     const int s = blockIdx.y, tid = threadIdx.x;
     const Column c = make_column(st, dr, seed, counter, s, hx, hy);
@@ -242,30 +196,11 @@ ds_select_kernel(Store st, Draws dr, unsigned long long seed, const long long* _
     const int* __restrict__ mc = ws.memcnt + s * max_chunks;
     long long part = 0;
     for (int ch = tid; ch < nch; ch += kT) part += mc[ch];
-    const int cnt = (int)wg_sum(part, red);
+    const int cnt = (int)wg_sum<kWaves, long long>(part, red);
     const bool subset = cnt > npts;
     int T = kBins, below = 0;
     if (subset && !replay) {
-        // bin T: the first bin whose inclusive count reaches npts.  Thread t owns bins [16t, 16t + 16).
-        constexpr int per = kBins / kT;
-        const unsigned* __restrict__ gh = ws.hist + (size_t)s * kBins;
-        int local = 0;
-        for (int k = 0; k < per; ++k) local += (int)gh[tid * per + k];
-        // exclusive scan of the per-thread sums (small: kT values through LDS)
-        __shared__ int sums[kT];
-        sums[tid] = local;
-        __syncthreads();
-        int before = 0;
-        for (int t = 0; t < tid; ++t) before += sums[t];
-        if (before < npts && before + local >= npts) {
-            int acc = before;
-            for (int k = 0; k < per; ++k) {
-                const int v = (int)gh[tid * per + k];
-                if (acc + v >= npts) { s_T = tid * per + k; s_below = acc; break; }
-                acc += v;
-            }
-        }
-        __syncthreads();
+        subset_find_bin<kT>(ws.hist + (size_t)s * kBins, npts, sums, &s_T, &s_below);
         T = s_T; below = s_below;
     }
     if (blockIdx.x == 0 && tid == 0) {
@@ -291,26 +226,17 @@ ds_select_kernel(Store st, Draws dr, unsigned long long seed, const long long* _
                 win = in;
             } else if (mask) {
                 int tot;
-                const int off = wg_excl_scan(in, wsum, tot);
+                const int off = wg_excl_scan_flag<kWaves>(in, wsum, tot);
                 const int p = prefix + run + off;
                 win = in && p < dr.mask_cap && mask[p] != 0;
                 run += tot;
             } else if (in) {
-                const unsigned long long k = draw64(c.h, (unsigned long long)(i - o0));
-                const int bin = (int)(k >> (64 - kBinBits));
-                if (bin < T) {
-                    win = true;
-                } else if (bin == T) {
-                    const unsigned slot = atomicAdd(&ws.ncand[s], 1u);
-                    if (slot < (unsigned)kCandCap) {
-                        ws.cand_key[(size_t)s * kCandCap + slot] = k;
-                        ws.cand_idx[(size_t)s * kCandCap + slot] = i;
-                    }
-                }
+                win = subset_below_or_push(draw64(c.h, (unsigned long long)(i - o0)), i, T, &ws.ncand[s],
+                                           ws.cand_key + (size_t)s * kCandCap, ws.cand_idx + (size_t)s * kCandCap);
             }
             chosen += win;
         }
-        const long long tot = wg_sum(chosen, red);
+        const long long tot = wg_sum<kWaves, long long>(chosen, red);
         if (tid == 0) ws.defcnt[s * max_chunks + ch] = (int)tot;
     }
 }
@@ -345,23 +271,12 @@ ds_emit_kernel(Store st, Draws dr, unsigned long long seed, const long long* __r
             if (blockIdx.x == 0 && tid == 0) in[I_STATUS] = ST_CAND;
             return;
         }
-        // the candidate of rank need-1 in (key, index) order is the cut: exactly `need` candidates are <= it
-        for (int a = tid; a < nc; a += kT) {
-            const unsigned long long ka = ck[a];
-            const int ia = ci[a];
-            int rank = 0;
-            for (int b = 0; b < nc; ++b) {
-                const unsigned long long kb = ck[b];
-                rank += (kb < ka) || (kb == ka && ci[b] < ia);
-            }
-            if (rank == need - 1) { cut_key = ka; cut_idx = ia; }
-        }
-        __syncthreads();
+        subset_find_cut<kT>(ck, ci, nc, need, &cut_key, &cut_idx);
     }
     if (replay && subset && blockIdx.x == 0) {  // the reference's mask must select exactly npts members (:96-100)
         long long part = 0;
         for (int ch = tid; ch < nch; ch += kT) part += dc[ch];
-        const long long tot = wg_sum(part, red);
+        const long long tot = wg_sum<kWaves, long long>(part, red);
         if (tid == 0 && tot != npts) in[I_STATUS] = ST_MASK;  // ds_write zero-fills the sample
     }
     const unsigned long long cutk = cands ? cut_key : 0ull;
@@ -375,14 +290,9 @@ ds_emit_kernel(Store st, Draws dr, unsigned long long seed, const long long* __r
         // chosen members before this chunk: per-chunk counts of launch 2 + candidates at or under the cut before it
         long long part = 0, mpart = 0;
         for (int k = tid; k < ch; k += kT) { part += dc[k]; mpart += mc[k]; }
-        if (cands)
-            for (int a = tid; a < nc; a += kT) {
-                const unsigned long long ka = ck[a];
-                const int ia = ci[a];
-                part += ia < start && (ka < cutk || (ka == cutk && ia <= cuti));
-            }
-        const int prefix = (int)wg_sum(part, red);
-        const int mprefix = mask ? (int)wg_sum(mpart, red) : 0;
+        if (cands) part += subset_cands_before<kT>(ck, ci, nc, start, cutk, cuti);
+        const int prefix = (int)wg_sum<kWaves, long long>(part, red);
+        const int mprefix = mask ? (int)wg_sum<kWaves, long long>(mpart, red) : 0;
         int run = 0, mrun = 0;
         for (int it = 0; it < kChunk / kT; ++it) {
             const int i = start + it * kT + tid;
@@ -392,17 +302,15 @@ ds_emit_kernel(Store st, Draws dr, unsigned long long seed, const long long* __r
                 win = inc;
             } else if (mask) {
                 int tot;
-                const int off = wg_excl_scan(inc, wsum, tot);
+                const int off = wg_excl_scan_flag<kWaves>(inc, wsum, tot);
                 const int p = mprefix + mrun + off;
                 win = inc && p < dr.mask_cap && mask[p] != 0;
                 mrun += tot;
             } else if (inc) {
-                const unsigned long long k = draw64(c.h, (unsigned long long)(i - o0));
-                const int bin = (int)(k >> (64 - kBinBits));
-                win = bin < T || (bin == T && (k < cutk || (k == cutk && i <= cuti)));
+                win = subset_wins(draw64(c.h, (unsigned long long)(i - o0)), i, T, cutk, cuti);
             }
             int tot;
-            const int off = wg_excl_scan(win, wsum, tot);
+            const int off = wg_excl_scan_flag<kWaves>(win, wsum, tot);
             const int pos = prefix + run + off;
             if (win && pos < ncap) {
                 sel[pos] = i;
@@ -413,13 +321,8 @@ ds_emit_kernel(Store st, Draws dr, unsigned long long seed, const long long* __r
         }
     }
     // box_min = np.min(points, axis=0) over the selected points (_center_box, :111); duplicates (cnt <= npts) change nothing
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        m0 = fmin(m0, __shfl_xor(m0, o)); m1 = fmin(m1, __shfl_xor(m1, o)); m2 = fmin(m2, __shfl_xor(m2, o));
-    }
-    if ((tid & 63) == 0) { smin[0][tid >> 6] = m0; smin[1][tid >> 6] = m1; smin[2][tid >> 6] = m2; }
-    __syncthreads();
-    if (tid < 3) {
+    wg_min3_stage<kWaves>(m0, m1, m2, smin);
+    if (tid < 3) {  // (its own tail: from smin[a][0] upwards, then across workgroups as ordered keys)
         double v = smin[tid][0];
         for (int w = 1; w < kWaves; ++w) v = fmin(v, smin[tid][w]);
         if (v < 1.0e300) atomicMin(&ws.mins[s * 3 + tid], ordered_key(v));

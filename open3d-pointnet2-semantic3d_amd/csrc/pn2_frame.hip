@@ -5,14 +5,17 @@
 //                      (semantic_dataset.py:90-121) over the WHOLE cropped, x-sorted frame: one sample of npts points.
 // The x-sort between the two is pn2_scene_ingest (csrc/pn2_store.hip).
 //
-// pn2_frame_sample restates, for one cloud whose count is a host integer, two things that exist per batch elsewhere: the
-// mask / repeat / centre half of scene_sample_kernel (pn2_scene.hip: that one reads an index list and a device count per sample and
-// leaves a rejected sample unwritten) and the "npts smallest 64-bit keys, exactly" of pn2_dataset.hip (histogram of the top key
-// bits, the bin T holding the npts-th key, a short candidate list, the exact cut inside T with ties broken by index; there the
-// members are a column of a multi-scene store found by binary search).  It shares their rule and their stream: pn2_rng.h unchanged,
-// subset keys draw64(sample_stream(seed, *counter, 0), i) for i in [0, cnt), the index space pn2_dataset.hip uses for them.
+// pn2_frame_sample is, for one cloud whose count is a host integer, two things that exist per batch elsewhere, and it runs the same
+// code as they do: the mask / repeat / centre tail of scene_sample_kernel (pn2_center.h; the scene kernel maps positions through an
+// index list and leaves a rejected sample unwritten, this one takes positions as rows and zero-fills) and the "npts smallest 64-bit
+// keys, exactly" of pn2_dataset.hip (pn2_subset.h; there the members are a column of a multi-scene store found by binary search).
+// Its own are the launches, the workspace and the status codes.  The stream is pn2_rng.h's: subset keys
+// draw64(sample_stream(seed, *counter, 0), i) for i in [0, cnt), the index space pn2_dataset.hip uses for them.
+#include "pn2_center.h"
 #include "pn2_common.h"
 #include "pn2_rng.h"
+#include "pn2_subset.h"
+#include "pn2_wg.h"
 
 namespace {
 
@@ -20,46 +23,10 @@ constexpr int kT = 256;             // threads per workgroup of the chunked laun
 constexpr int kWaves = kT / 64;
 constexpr int kChunk = 1024;        // rows per chunk (4 ordered passes of kT)
 constexpr int kFinT = 1024;         // threads of the one-workgroup finishing launch
-constexpr int kBinBits = 12;
-constexpr int kBins = 1 << kBinBits;
-constexpr int kCandCap = 4096;      // candidates (members of bin T); ~cnt / 4096 expected, cnt <= PN2_FRAME_MAX_ROWS
+constexpr int kFinW = kFinT / 64;
 enum { M_T, M_NEED, M_INTS };       // meta words fs_select leaves for fs_emit
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int chunks_of(int n) { return (n + kChunk - 1) / kChunk; }
-
-// exclusive prefix of per-thread flags over the workgroup (thread order); `total` = workgroup sum.  wsum: W ints.
-template <int W>
-__device__ __forceinline__ int wg_excl_scan(int flag, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(flag);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        const int v = wsum[w];
-        if (w < wave) base += v;
-        tot += v;
-    }
-    __syncthreads();
-    total = tot;
-    return base + before;
-}
-
-// workgroup sum of a per-thread int (kT threads); red: kWaves ints
-__device__ __forceinline__ int wg_sum(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int t = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) t += red[w];
-    __syncthreads();
-    return t;
-}
 
 // ---- crop ------------------------------------------------------------------------------------------------------------
 struct Box { double lo0, lo1, lo2, hi0, hi1, hi2; };
@@ -79,7 +46,7 @@ fc_count_kernel(int n, const float* __restrict__ frame, int ld, Box box, int* __
     int mine = 0;
 #pragma unroll
     for (int it = 0; it < kChunk / kT; ++it) mine += in_box(box, frame, ld, n, ch * kChunk + it * kT + tid);
-    const int tot = wg_sum(mine, red);
+    const int tot = wg_sum<kWaves>(mine, red);
     if (tid == 0) chunk_cnt[ch] = tot;
 }
 
@@ -91,13 +58,13 @@ fc_emit_kernel(int n, const float* __restrict__ frame, int ld, Box box, const in
     const int ch = blockIdx.x, tid = threadIdx.x;
     int part = 0;
     for (int k = tid; k < ch; k += kT) part += chunk_cnt[k];
-    const int prefix = wg_sum(part, red);  // rows kept before this chunk
+    const int prefix = wg_sum<kWaves>(part, red);  // rows kept before this chunk
     int run = 0;
     for (int it = 0; it < kChunk / kT; ++it) {
         const int i = ch * kChunk + it * kT + tid;
         const bool in = in_box(box, frame, ld, n, i);
         int tot;
-        const int off = wg_excl_scan<kWaves>(in, wsum, tot);
+        const int off = wg_excl_scan_flag<kWaves>(in, wsum, tot);
         if (in) {
             const size_t pos = (size_t)(prefix + run + off);  // < n: at most i rows are kept before row i
             const float* p = frame + (size_t)i * ld;
@@ -119,19 +86,16 @@ struct SampleWs {  // workspace carve-up; hist and ncand are cleared by the call
     int* meta;                     // M_INTS
 };
 inline size_t sample_ws_layout(int cnt, unsigned char* base, SampleWs* w) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { unsigned char* p = base ? base + o : nullptr; o += al256(bytes); return p; };
-    unsigned char* h = take((size_t)(kBins + 1) * 4);
-    unsigned char* ck = take((size_t)kCandCap * 8);
-    unsigned char* ci = take((size_t)kCandCap * 4);
-    unsigned char* dc = take((size_t)chunks_of(cnt) * 4);
-    unsigned char* mt = take((size_t)M_INTS * 4);
-    if (w) {
-        w->hist = reinterpret_cast<unsigned*>(h); w->ncand = w->hist + kBins;
-        w->cand_key = reinterpret_cast<unsigned long long*>(ck); w->cand_idx = reinterpret_cast<int*>(ci);
-        w->defcnt = reinterpret_cast<int*>(dc); w->meta = reinterpret_cast<int*>(mt);
-    }
-    return o;
+    WsCarver c{base};
+    SampleWs t;
+    t.hist = c.take<unsigned>((size_t)kBins + 1);
+    t.ncand = t.hist + kBins;
+    t.cand_key = c.take<unsigned long long>((size_t)kCandCap);
+    t.cand_idx = c.take<int>((size_t)kCandCap);
+    t.defcnt = c.take<int>((size_t)chunks_of(cnt));
+    t.meta = c.take<int>((size_t)M_INTS);
+    if (w) *w = t;
+    return c.used;
 }
 
 // launch 1 (device mode, cnt > npts): histogram of the top kBinBits bits of every point's key
@@ -145,7 +109,7 @@ fs_hist_kernel(int cnt, unsigned long long seed, const long long* __restrict__ c
     for (int ch = blockIdx.x; ch * kChunk < cnt; ch += gridDim.x)
         for (int it = 0; it < kChunk / kT; ++it) {
             const int i = ch * kChunk + it * kT + tid;
-            if (i < cnt) atomicAdd(&lhist[draw64(h, (unsigned long long)i) >> (64 - kBinBits)], 1u);
+            if (i < cnt) atomicAdd(&lhist[subset_bin(draw64(h, (unsigned long long)i))], 1u);
         }
     __syncthreads();
     for (int j = tid; j < kBins; j += kT)
@@ -160,39 +124,16 @@ fs_select_kernel(int cnt, int npts, unsigned long long seed, const long long* __
     __shared__ int s_T, s_below;
     const int ch = blockIdx.x, tid = threadIdx.x;
     const unsigned long long h = sample_stream(seed, (unsigned long long)counter[0], 0);
-    // T: the first bin whose inclusive count reaches npts (cnt > npts: there is one).  Thread t owns bins [16t, 16t + 16).
-    constexpr int per = kBins / kT;
-    int local = 0;
-    for (int k = 0; k < per; ++k) local += (int)ws.hist[tid * per + k];
-    sums[tid] = local;
-    __syncthreads();
-    int before = 0;
-    for (int t = 0; t < tid; ++t) before += sums[t];
-    if (before < npts && before + local >= npts) {
-        int acc = before;
-        for (int k = 0; k < per; ++k) {
-            const int v = (int)ws.hist[tid * per + k];
-            if (acc + v >= npts) { s_T = tid * per + k; s_below = acc; break; }
-            acc += v;
-        }
-    }
-    __syncthreads();
+    subset_find_bin<kT>(ws.hist, npts, sums, &s_T, &s_below);  // cnt > npts: there is such a bin
     const int T = s_T;
     if (ch == 0 && tid == 0) { ws.meta[M_T] = T; ws.meta[M_NEED] = npts - s_below; }
     int chosen = 0;
     for (int it = 0; it < kChunk / kT; ++it) {
         const int i = ch * kChunk + it * kT + tid;
         if (i >= cnt) continue;
-        const unsigned long long k = draw64(h, (unsigned long long)i);
-        const int bin = (int)(k >> (64 - kBinBits));
-        if (bin < T) {
-            ++chosen;
-        } else if (bin == T) {
-            const unsigned slot = atomicAdd(ws.ncand, 1u);
-            if (slot < (unsigned)kCandCap) { ws.cand_key[slot] = k; ws.cand_idx[slot] = i; }
-        }
+        chosen += subset_below_or_push(draw64(h, (unsigned long long)i), i, T, ws.ncand, ws.cand_key, ws.cand_idx);
     }
-    const int tot = wg_sum(chosen, red);
+    const int tot = wg_sum<kWaves>(chosen, red);
     if (tid == 0) ws.defcnt[ch] = tot;
 }
 
@@ -214,39 +155,20 @@ fs_emit_kernel(int cnt, int npts, unsigned long long seed, const long long* __re
     }
     const unsigned long long* __restrict__ ck = ws.cand_key;
     const int* __restrict__ ci = ws.cand_idx;
-    for (int a = tid; a < nc; a += kT) {
-        const unsigned long long ka = ck[a];
-        const int ia = ci[a];
-        int rank = 0;
-        for (int b = 0; b < nc; ++b) {
-            const unsigned long long kb = ck[b];
-            rank += (kb < ka) || (kb == ka && ci[b] < ia);
-        }
-        if (rank == need - 1) { cut_key = ka; cut_idx = ia; }
-    }
-    __syncthreads();
+    subset_find_cut<kT>(ck, ci, nc, need, &cut_key, &cut_idx);
     const unsigned long long cutk = cut_key;
     const int cuti = cut_idx;
     const int start = ch * kChunk;
     int part = 0;
     for (int k = tid; k < ch; k += kT) part += ws.defcnt[k];
-    for (int a = tid; a < nc; a += kT) {
-        const unsigned long long ka = ck[a];
-        const int ia = ci[a];
-        part += ia < start && (ka < cutk || (ka == cutk && ia <= cuti));
-    }
-    const int prefix = wg_sum(part, red);  // chosen points before this chunk
+    part += subset_cands_before<kT>(ck, ci, nc, start, cutk, cuti);
+    const int prefix = wg_sum<kWaves>(part, red);  // chosen points before this chunk
     int run = 0;
     for (int it = 0; it < kChunk / kT; ++it) {
         const int i = start + it * kT + tid;
-        bool win = false;
-        if (i < cnt) {
-            const unsigned long long k = draw64(h, (unsigned long long)i);
-            const int bin = (int)(k >> (64 - kBinBits));
-            win = bin < T || (bin == T && (k < cutk || (k == cutk && i <= cuti)));
-        }
+        const bool win = i < cnt && subset_wins(draw64(h, (unsigned long long)i), i, T, cutk, cuti);
         int tot;
-        const int off = wg_excl_scan<kWaves>(win, wsum, tot);
+        const int off = wg_excl_scan_flag<kWaves>(win, wsum, tot);
         const int pos = prefix + run + off;
         if (win && pos < npts) sel[pos] = i;
         run += tot;
@@ -260,24 +182,15 @@ __global__ void __launch_bounds__(kFinT)
 fs_finish_kernel(int mode, int cnt, int npts, const double* __restrict__ pts, const unsigned char* __restrict__ mask, double hx,
                  double hy, long long* __restrict__ counter, int* __restrict__ sel, float* __restrict__ cen,
                  double* __restrict__ raw, int* __restrict__ status) {
-    __shared__ int wsum[kFinT / 64];
-    __shared__ double smin[3][kFinT / 64];
+    __shared__ int wsum[kFinW];
+    __shared__ double smin[3][kFinW];
     const int tid = threadIdx.x;
     if (tid == 0 && counter) counter[0] = counter[0] + 1;  // the next call draws fresh keys (graph replays included)
     int st = mode == MODE_KEYS ? status[0] : PN2_FRAME_ST_OK;
     if (mode == MODE_MASK) {  // the reference's shuffled boolean mask: the set positions, ascending
-        int count = 0;
-        for (int base = 0; base < cnt; base += kFinT) {
-            const int i = base + tid;
-            const int in = (i < cnt) && mask[i] != 0;
-            int tot;
-            const int off = wg_excl_scan<kFinT / 64>(in, wsum, tot);
-            if (in && count + off < npts) sel[count + off] = i;
-            count += tot;
-        }
-        if (count != npts) st = PN2_FRAME_ST_MASK;  // it must select exactly npts points (:96-100)
+        if (center_select_mask<kFinW>(cnt, npts, mask, nullptr, sel, wsum) != npts) st = PN2_FRAME_ST_MASK;
     } else if (mode == MODE_REPEAT) {
-        for (int j = tid; j < npts; j += kFinT) sel[j] = j % cnt;  // arange(cnt) doubled until it reaches npts, then cut (:102-106)
+        center_select_repeat<kFinW>(cnt, npts, nullptr, sel);
     } else if (st == PN2_FRAME_ST_OK) {  // fs_emit wrote every entry; nothing below gathers through one that is not a row
         int bad = 0;
         for (int j = tid; j < npts; j += kFinT) bad |= (unsigned)sel[j] >= (unsigned)cnt;
@@ -293,25 +206,8 @@ fs_finish_kernel(int mode, int cnt, int npts, const double* __restrict__ pts, co
         return;
     }
     __syncthreads();
-    double m0 = 1.0e300, m1 = 1.0e300, m2 = 1.0e300;  // box_min = np.min(points, axis=0) over the sampled points (:112)
-    for (int j = tid; j < npts; j += kFinT) {
-        const size_t k = (size_t)sel[j];
-        m0 = fmin(m0, pts[k * 3]); m1 = fmin(m1, pts[k * 3 + 1]); m2 = fmin(m2, pts[k * 3 + 2]);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        m0 = fmin(m0, __shfl_xor(m0, o)); m1 = fmin(m1, __shfl_xor(m1, o)); m2 = fmin(m2, __shfl_xor(m2, o));
-    }
-    if ((tid & 63) == 0) { smin[0][tid >> 6] = m0; smin[1][tid >> 6] = m1; smin[2][tid >> 6] = m2; }
-    __syncthreads();
-    for (int w = 0; w < kFinT / 64; ++w) { m0 = fmin(m0, smin[0][w]); m1 = fmin(m1, smin[1][w]); m2 = fmin(m2, smin[2][w]); }
-    const double sh0 = m0 + hx, sh1 = m1 + hy, sh2 = m2;  // shift (:113-119), float64
-    for (int j = tid; j < npts; j += kFinT) {
-        const size_t k = (size_t)sel[j];
-        const double x = pts[k * 3], y = pts[k * 3 + 1], z = pts[k * 3 + 2];
-        cen[j * 3 + 0] = (float)(x - sh0); cen[j * 3 + 1] = (float)(y - sh1); cen[j * 3 + 2] = (float)(z - sh2);  // :120
-        raw[j * 3 + 0] = x; raw[j * 3 + 1] = y; raw[j * 3 + 2] = z;
-    }
+    const CenterShift sh = center_shift<kFinW>(npts, pts, sel, hx, hy, smin);
+    for (int j = tid; j < npts; j += kFinT) center_put(pts, (size_t)sel[j], j, sh, cen, raw);
 }
 
 }  // namespace

@@ -8,54 +8,29 @@
 // RNG), never generated inside a kernel.
 #include <hipcub/hipcub.hpp>
 
+#include "pn2_center.h"
 #include "pn2_common.h"
 #include "pn2_ordered.h"  // ordered_key, ordered_to_double
+#include "pn2_wg.h"
 
 namespace {
 
 constexpr int kScT = 1024;  // threads per sample
-
-// exclusive prefix of per-thread flags inside a 1024-thread block; returns this thread's offset and the block total
-__device__ __forceinline__ int block_excl_scan(int flag, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(flag);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < kScT / 64; ++w) {
-        const int c = wsum[w];
-        if (w < wave) base += c;
-        tot += c;
-    }
-    __syncthreads();  // wsum reusable
-    total = tot;
-    return base + before;
-}
-
-// first index i in [0, n) with x[3*i] >= v  (np.searchsorted(points[:, 0], v), side='left'); points sorted by x
-__device__ __forceinline__ int lower_bound_x(const double* __restrict__ pts, int n, double v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (pts[(size_t)mid * 3] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+constexpr int kScW = kScT / 64;
 
 // _extract_z_box (semantic_dataset.py:123-163): one workgroup per sample; writes the scene indices of the column in
 // scene order (= the order of points[scene_extract_mask]) and their count.
 __global__ void __launch_bounds__(kScT)
 scene_extract_kernel(int n, const double* __restrict__ pts, const double* __restrict__ centers, double hx, double hy,
                      double zsize, int cap, int* __restrict__ idx_all, int* __restrict__ cnt_all) {
-    __shared__ int wsum[kScT / 64];
+    __shared__ int wsum[kScW];
     const int s = blockIdx.x, tid = threadIdx.x;
     const double cx = centers[s * 3 + 0], cy = centers[s * 3 + 1], cz = centers[s * 3 + 2];
     // box_min = center_point - [bx/2, by/2, scene_z_size], box_max = center_point + [...]  (:133-142), float64
     const double lo0 = cx - hx, lo1 = cy - hy, lo2 = cz - zsize;
     const double hi0 = cx + hx, hi1 = cy + hy, hi2 = cz + zsize;
-    const int i_min = lower_bound_x(pts, n, lo0);  // :144
-    const int i_max = lower_bound_x(pts, n, hi0);  // :145 (side='left': points with x == box_max[0] stay outside)
+    const int i_min = lower_bound_x(pts, 0, n, lo0);  // :144
+    const int i_max = lower_bound_x(pts, 0, n, hi0);  // :145 (side='left': points with x == box_max[0] stay outside)
     int* __restrict__ out = idx_all + (size_t)s * cap;
     int count = 0;
     for (int base = i_min; base < i_max; base += kScT) {
@@ -66,7 +41,7 @@ scene_extract_kernel(int n, const double* __restrict__ pts, const double* __rest
             in = (x >= lo0) & (x <= hi0) & (y >= lo1) & (y <= hi1) & (z >= lo2) & (z <= hi2);  // :146-153
         }
         int tot;
-        const int off = block_excl_scan(in, wsum, tot);
+        const int off = wg_excl_scan_flag<kScW>(in, wsum, tot);
         if (in && count + off < cap) out[count + off] = i;
         count += tot;
     }
@@ -83,8 +58,8 @@ scene_sample_kernel(int npts, int cap, const double* __restrict__ pts, const int
                     const unsigned char* __restrict__ mask_all, double hx, double hy, int* __restrict__ sel_all,
                     float* __restrict__ centered_all, double* __restrict__ raw_all, int* __restrict__ lab_all,
                     float* __restrict__ col_all, int* __restrict__ status) {
-    __shared__ int wsum[kScT / 64];
-    __shared__ double smin[3][kScT / 64];
+    __shared__ int wsum[kScW];
+    __shared__ double smin[3][kScW];
     const int s = blockIdx.x, tid = threadIdx.x;
     const int cnt = cnt_all[s];
     const int* __restrict__ idx = idx_all + (size_t)s * cap;
@@ -94,38 +69,15 @@ scene_sample_kernel(int npts, int cap, const double* __restrict__ pts, const int
         return;
     }
     if (cnt > npts) {
-        const unsigned char* __restrict__ mask = mask_all + (size_t)s * cap;
-        int count = 0;
-        for (int base = 0; base < cnt; base += kScT) {
-            const int i = base + tid;
-            const int in = (i < cnt) && mask[i] != 0;
-            int tot;
-            const int off = block_excl_scan(in, wsum, tot);
-            if (in && count + off < npts) sel[count + off] = idx[i];
-            count += tot;
-        }
-        if (count != npts) {  // the mask must hold exactly npts selections (:96-100)
+        if (center_select_mask<kScW>(cnt, npts, mask_all + (size_t)s * cap, idx, sel, wsum) != npts) {
             if (tid == 0) status[s] = 3;
             return;
         }
     } else {
-        for (int j = tid; j < npts; j += kScT) sel[j] = idx[j % cnt];  // :102-106
+        center_select_repeat<kScW>(cnt, npts, idx, sel);
     }
     __syncthreads();
-    // box_min = np.min(points, axis=0) over the SAMPLED points (:111)
-    double m0 = 1.0e300, m1 = 1.0e300, m2 = 1.0e300;
-    for (int j = tid; j < npts; j += kScT) {
-        const int k = sel[j];
-        m0 = fmin(m0, pts[(size_t)k * 3]); m1 = fmin(m1, pts[(size_t)k * 3 + 1]); m2 = fmin(m2, pts[(size_t)k * 3 + 2]);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        m0 = fmin(m0, __shfl_xor(m0, o)); m1 = fmin(m1, __shfl_xor(m1, o)); m2 = fmin(m2, __shfl_xor(m2, o));
-    }
-    if ((tid & 63) == 0) { smin[0][tid >> 6] = m0; smin[1][tid >> 6] = m1; smin[2][tid >> 6] = m2; }
-    __syncthreads();
-    for (int w = 0; w < kScT / 64; ++w) { m0 = fmin(m0, smin[0][w]); m1 = fmin(m1, smin[1][w]); m2 = fmin(m2, smin[2][w]); }
-    const double sh0 = m0 + hx, sh1 = m1 + hy, sh2 = m2;  // shift (:112-118), float64
+    const CenterShift sh = center_shift<kScW>(npts, pts, sel, hx, hy, smin);
     if (tid == 0) status[s] = 0;
     float* __restrict__ cen = centered_all + (size_t)s * npts * 3;
     double* __restrict__ raw = raw_all ? raw_all + (size_t)s * npts * 3 : nullptr;
@@ -133,9 +85,7 @@ scene_sample_kernel(int npts, int cap, const double* __restrict__ pts, const int
     float* __restrict__ col = col_all ? col_all + (size_t)s * npts * 3 : nullptr;
     for (int j = tid; j < npts; j += kScT) {
         const int k = sel[j];
-        const double x = pts[(size_t)k * 3], y = pts[(size_t)k * 3 + 1], z = pts[(size_t)k * 3 + 2];
-        cen[j * 3 + 0] = (float)(x - sh0); cen[j * 3 + 1] = (float)(y - sh1); cen[j * 3 + 2] = (float)(z - sh2);  // :119, then astype(float32)
-        if (raw) { raw[j * 3 + 0] = x; raw[j * 3 + 1] = y; raw[j * 3 + 2] = z; }
+        center_put(pts, (size_t)k, j, sh, cen, raw);
         if (lab) lab[j] = labels ? labels[k] : 0;
         if (col) {
 #pragma unroll
@@ -245,7 +195,6 @@ struct VoxLayout {
     size_t keys_in, keys_out, vals_in, vals_out, flags, scan, starts, mm, misc, cub, total;
     size_t cub_bytes;
 };
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline VoxLayout vox_layout(int n) {
     VoxLayout L;
     size_t o = 0;

@@ -9,6 +9,7 @@
 
 #include "pn2_common.h"
 #include "pn2_itoa.h"
+#include "pn2_wg.h"  // al256
 
 namespace {
 
@@ -94,7 +95,6 @@ struct FormatLayout {
     size_t total_at, base_at, cub_at, bytes, cub_bytes;
     int nwg;
 };
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline hipError_t format_layout(int nrows, FormatLayout& L) {
     L.nwg = (nrows + kFmtT - 1) / kFmtT;
     size_t o = 0;

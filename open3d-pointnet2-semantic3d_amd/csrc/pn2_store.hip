@@ -23,6 +23,7 @@
 
 #include "pn2_common.h"
 #include "pn2_ordered.h"  // ordered_key, ordered_to_double
+#include "pn2_wg.h"          // finite64, al256
 
 namespace {
 
@@ -40,7 +41,6 @@ struct Layout {
     size_t keys_in, keys_out, vals_in, vals_out, scal, cub, total;
     size_t cub_bytes;
 };
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 // the part in front of the sort's own temporary storage: known without asking the sort
 inline size_t fixed_layout(int n, Layout* L) {
     size_t o = 0;
@@ -60,10 +60,6 @@ inline hipError_t layout(int n, Layout* L) {
     L->cub = o; o += al256(cub);
     L->total = o;
     return e;
-}
-
-__device__ __forceinline__ bool finite64(double v) {
-    return ((unsigned long long)__double_as_longlong(v) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
 }
 
 __global__ void __launch_bounds__(kT)

@@ -9,6 +9,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "pn2_common.h"
+#include "pn2_wg.h"  // al256
 
 namespace {
 
@@ -97,7 +98,6 @@ struct IndexLayout {
     size_t count, base, cub, total, cub_bytes;
     int ntiles;
 };
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline hipError_t index_layout(int nbytes, IndexLayout& L) {
     L.ntiles = (nbytes + kTile - 1) / kTile;
     size_t o = 0;

@@ -30,6 +30,7 @@
 
 #include "pn2_common.h"
 #include "pn2_ordered.h"  // ordered_key, ordered_to_double
+#include "pn2_wg.h"
 
 namespace {
 
@@ -52,7 +53,6 @@ struct Layout {
     size_t keys_in, keys_out, vals_in, tile_start, chunk_a, chunk_b, scal, cub, total;
     size_t cub_bytes;
 };
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int chunks_of(int n) { return (n + kChunk - 1) / kChunk; }
 // the part in front of the sort's own temporary storage: known without asking the sort
 inline size_t fixed_layout(int n, Layout* L) {
@@ -75,67 +75,6 @@ inline hipError_t layout(int n, Layout* L) {
     L->cub = o; o += al256(cub);
     L->total = o;
     return e;
-}
-
-__device__ __forceinline__ bool finite64(double v) {
-    return ((unsigned long long)__double_as_longlong(v) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
-}
-
-// workgroup sum of a per-thread int (kT threads); red: kWaves ints
-__device__ __forceinline__ int wg_sum(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int t = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) t += red[w];
-    __syncthreads();
-    return t;
-}
-
-// exclusive prefix of per-thread flags over the workgroup (thread order); `total` = workgroup sum.  wsum: W ints.
-template <int W>
-__device__ __forceinline__ int wg_excl_scan_flag(bool flag, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(flag);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        const int v = wsum[w];
-        if (w < wave) base += v;
-        tot += v;
-    }
-    __syncthreads();
-    total = tot;
-    return base + before;
-}
-
-// the same for per-thread counts
-template <int W>
-__device__ __forceinline__ int wg_excl_scan_int(int v, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        const int s = wsum[w];
-        if (w < wave) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    total = tot;
-    return base + inc - v;
 }
 
 // ---- plan ------------------------------------------------------------------------------------------------------------------
@@ -194,7 +133,7 @@ tp_head_count_kernel(int n, const unsigned long long* __restrict__ keys, int* __
     int mine = 0;
 #pragma unroll
     for (int it = 0; it < kChunk / kT; ++it) mine += is_head(n, keys, ch * kChunk + it * kT + tid);
-    const int tot = wg_sum(mine, red);
+    const int tot = wg_sum<kWaves>(mine, red);
     if (tid == 0) chunk_cnt[ch] = tot;
 }
 
@@ -261,8 +200,8 @@ tp_tile_count_kernel(int n, int npts, int min_points, const int* __restrict__ ti
             skipped += S == 0 ? m : 0;
         }
     }
-    const int tot = wg_sum(samples, red);
-    const int skp = wg_sum(skipped, red);
+    const int tot = wg_sum<kWaves>(samples, red);
+    const int skp = wg_sum<kWaves>(skipped, red);
     if (tid == 0) {
         chunk_cnt[ch] = tot;  // (a chunk beyond the last tile: 0, the scan reads every entry)
         if (skp) atomicAdd(&scal->skipped, skp);

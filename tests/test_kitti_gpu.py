@@ -209,6 +209,54 @@ def test_sample_device_mode(pn2, cuda, cnt, npts):
     assert not np.array_equal(other[0], sel)
 
 
+def dataset_sel_raw(pn2, dev, pts, npts, seed, counter, max_chunks=8):
+    """one raw device-mode pn2_dataset_sample call, b = 1, on a one-scene store made of `pts` with half-sizes beyond the scene's
+    extent (the column is the whole scene wherever the centre falls) -> out_sel (npts,) as numpy (scene-local: offset 0)"""
+    import torch
+    L = pn2._lib
+    cnt = len(pts)
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
+    p, off, cdf = t(pts, np.float64), t([0, cnt], np.int32), t([1.0], np.float64)
+    zsize = t([pts[:, 2].max() - pts[:, 2].min()], np.float64)
+    need = L.u64_array([0])
+    L.launch("pn2_dataset_workspace_size", dev, 1, max_chunks, need, stream=False)
+    ws = torch.zeros(int(need[0]) + 256, dtype=torch.uint8, device=dev)  # the histogram and the candidate count start at zero
+    base = (-ws.data_ptr()) % 256
+    info = torch.empty((1, 8), dtype=torch.int32, device=dev)
+    finfo = torch.empty((1, 3), dtype=torch.float64, device=dev)
+    gsel = Guarded(torch, dev, (1, npts), torch.int32)
+    data = torch.empty((1, npts, 3), dtype=torch.float32, device=dev)
+    lab = torch.empty((1, npts), dtype=torch.int32, device=dev)
+    wts = torch.empty((1, npts), dtype=torch.float32, device=dev)
+    L.launch("pn2_dataset_sample", dev, 1, npts, 1, max_chunks, 0, 0, L.ptr(p), None, None, L.ptr(off), L.ptr(cdf), L.ptr(zsize),
+             None, 0, 100.0, 100.0, seed, L.ptr(counter), None, None, None, 0, None, L.ptr(ws[base:]), int(need[0]), L.ptr(info),
+             L.ptr(finfo), L.ptr(gsel.t), L.ptr(data), L.ptr(lab), L.ptr(wts))
+    torch.cuda.synchronize()
+    gsel.check("cnt %d npts %d" % (cnt, npts))
+    info = info.cpu().numpy()[0]
+    assert info[7] == 0 and info[2] == cnt, info  # status ok, the column is the whole scene
+    return gsel.t[0].cpu().numpy()
+
+
+@pytest.mark.parametrize("cnt,npts", [(1025, 16), (4097, 1024)])
+def test_dataset_and_frame_draw_the_same_subset(pn2, cuda, cnt, npts):
+    """one selection behind two entry points: the same (seed, counter) over the same cnt points gives pn2_dataset_sample (b = 1,
+    sample 0, a column that is the whole scene) and pn2_frame_sample the same index list.  1025: one row past a chunk; 4097: four
+    chunks and one row, about one key per bin, so bin T is populated and the cut decides."""
+    import torch
+    rs = np.random.RandomState(cnt)
+    pts = np.stack([np.arange(cnt) * 0.002 - 4.5, rs.uniform(-5, 5, cnt), rs.uniform(-2, 5, cnt)], 1)  # x strictly ascending
+    seed, c0 = 11 + cnt, 3
+    counter = torch.full((1,), c0, dtype=torch.int64, device=cuda)
+    by_dataset = torch.from_numpy(dataset_sel_raw(pn2, cuda, pts, npts, seed, counter))
+    assert int(counter.item()) == c0 + 1
+    counter.fill_(c0)
+    sel, _, _, st = sample_raw(pn2, cuda, pts, npts, 10, 10, seed=seed, counter=counter)
+    assert st == 0
+    assert torch.equal(by_dataset, torch.from_numpy(sel))
+    assert np.array_equal(sel, F.select(cnt, npts, seed=seed, counter=c0)[0])
+
+
 def test_centring_uses_the_minimum_of_the_sampled_points(pn2, cuda):
     pts = _sorted_points(100)
     pts[50, 1], pts[50, 2] = -4.9990234375, -1.9990234375  # the frame's minimum in y and z, and row 0 holds its minimum in x
