@@ -16,8 +16,13 @@
                   point of the store is predicted --phases times (1: one grid; 2: a second grid shifted by half a box votes
                   too) and the sparse side of the 3-NN vote is the whole store; columns below --min-points points are skipped
 
+    --soft        soft voting: the class probabilities (score rows, integers in units of 2^-30) are kept instead of their argmax.
+                  With --tiled they are summed over the grids (predict_scene_tiled(vote="soft")), without it they are the score
+                  rows of the sampled points (predict_scene(scores=True)); either way the dense cloud takes, per point, the class
+                  whose scores summed over its 3 nearest sparse points are the largest (pn2.predict.label_dense_scores)
+
 usage: python examples/predict_semantic3d.py [--ckpt FILE] [--set validation] [--num_samples 8] [--data PATH --raw PATH]
-       [--tiled [--phases 1|2] [--min-points K]]
+       [--tiled [--phases 1|2] [--min-points K]] [--soft]
        size flags (synthetic runs, tests): --points N --npoint a,b,c,d --scene-points P --scenes K --voxel V --batch-size B"""
 import argparse
 import os
@@ -97,6 +102,7 @@ def main():
     ap.add_argument("--tiled", action="store_true", help="label every point of the store: the tiled cover, not random columns")
     ap.add_argument("--phases", type=int, choices=(1, 2), default=1, help="--tiled: grids that vote (2: one shifted by half a box)")
     ap.add_argument("--min-points", type=int, default=1, help="--tiled: columns with fewer points are skipped")
+    ap.add_argument("--soft", action="store_true", help="vote with class probabilities instead of labels, through to the dense cloud")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     hp = dict(pn2.model.SEMANTIC_HYPERPARAMS)
@@ -123,13 +129,17 @@ def main():
         t0 = time.perf_counter()
         if args.tiled:
             phases = [(0.0, 0.0), (hp["box_size_x"] / 2, hp["box_size_y"] / 2)][:args.phases]
-            labels, _ = pn2.predict.predict_scene_tiled(predictor, dataset, k, args.batch_size, phases, args.min_points,
-                                                        confusion=cm_sparse)
+            labels, scores = pn2.predict.predict_scene_tiled(predictor, dataset, k, args.batch_size, phases, args.min_points,
+                                                             confusion=cm_sparse, vote="soft" if args.soft else "hard")
             points = torch.as_tensor(dataset.scene_points[k]).to(dev, torch.float32)  # the whole store is the sparse side
             torch.cuda.synchronize()
             print("    %d points, %d grid(s) of columns in %.1f ms" % (len(points), len(phases), (time.perf_counter() - t0) * 1e3))
         else:
-            points, labels = pn2.predict.predict_scene(predictor, dataset, k, args.num_samples, args.batch_size, confusion=cm_sparse)
+            if args.soft:
+                points, labels, scores = pn2.predict.predict_scene(predictor, dataset, k, args.num_samples, args.batch_size,
+                                                                   confusion=cm_sparse, scores=True)
+            else:
+                points, labels = pn2.predict.predict_scene(predictor, dataset, k, args.num_samples, args.batch_size, confusion=cm_sparse)
             dataset.check_last()
             torch.cuda.synchronize()
             print("    %d samples of %d points in %.1f ms" % (args.num_samples, hp["num_point"], (time.perf_counter() - t0) * 1e3))
@@ -140,9 +150,15 @@ def main():
         dense_points, dense_gt = dense[name]
         cm = M.ConfusionMatrix(dataset.num_classes, device=dev)
         t0 = time.perf_counter()
-        dense_labels, dense_colors = pn2.predict.label_dense(points, labels, dense_points, dense_gt, confusion=cm, chunk=args.chunk)
+        if args.soft:
+            dense_labels, dense_colors, confidence = pn2.predict.label_dense_scores(points, scores, dense_points, dense_gt,
+                                                                                    confusion=cm, chunk=args.chunk)
+        else:
+            dense_labels, dense_colors = pn2.predict.label_dense(points, labels, dense_points, dense_gt, confusion=cm, chunk=args.chunk)
         torch.cuda.synchronize()
         print("    KNN interpolation of %d dense points: %.1f ms" % (len(dense_points), (time.perf_counter() - t0) * 1e3))
+        if args.soft:
+            print("    Soft vote: mean confidence of the dense labels %.4f" % float(confidence.mean()))
         pn2.write_labels(os.path.join(dense_dir, name + ".labels"), dense_labels)
         pn2.write_point_cloud_pcd(os.path.join(dense_dir, name + "_colored.pcd"), dense_points, dense_colors)  # uint8 as it is
         print("    Dense labels and coloured pcd written to %s" % os.path.join(dense_dir, name))

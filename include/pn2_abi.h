@@ -1112,6 +1112,47 @@ int pn2_tile_vote(int b, int npts, int num_class, const int *sel, const int *liv
                   long long *dropped, void *stream);
 int pn2_tile_labels(int n, int num_class, const int *votes, int *labels, void *stream);
 
+/* Soft voting (csrc/pn2_soft_vote.hip, csrc/pn2_label_interp.hip): class probabilities summed over the overlapping predictions
+ * of a point and carried to the dense cloud, where pn2_tile_vote and pn2_interpolate_label_with_color count hard labels.
+ * tests/soft_vote_ref.py is the numpy model of the four rules.
+ *
+ * The score format, used by all four: a SCORE ROW is num_class non-negative integers in units of 2^-30, q_c = rint(p_c * 2^30),
+ * rounded half to even.  A row of q is int32; accumulated scores are int64.  Integer adds only: sums are exact and independent
+ * of the order of arrival, as votes are.  Every entry point checks its arguments in the order of the tile entry points -- sizes
+ * (PN2_EINVAL), ranges (PN2_ERANGE), num_class > 64 (PN2_EUNSUP), a required pointer NULL (PN2_ENULL), alignment (PN2_EINVAL) --
+ * and refuses before any launch.  No host synchronisation, no allocation: capturable into a graph.
+ *
+ * pn2_softmax_scores: logits (rows,num_class) float32 -> q (rows,num_class) int32.  Per row, in float64: m = max_c x_c,
+ *   e_c = exp((double)x_c - m), s = the sum of e_c added in class order, p_c = e_c / s, q_c = (int)rint(p_c * 2^30).  A row with a
+ *   NaN, or with m = +-inf, gets an all-zero score row and is counted in *invalid (optional, accumulates, never zeroed here): such
+ *   a row casts no vote downstream.  -inf entries of an otherwise finite row are p = 0.  One launch.
+ *
+ * pn2_tile_vote_scores: the soft twin of pn2_tile_vote.  scores (n,num_class) int64: for every live row r (k < live[q]) of the
+ *   batch with sel[r] >= 0 and all of q[r, :] >= 0, scores[sel[r], c] += q[r, c] for every class.  A live row with sel < 0 or any
+ *   negative q is left out whole and counted in *dropped (optional).  Rows k >= live[q] are ignored.  scores and *dropped
+ *   accumulate across calls and are never zeroed here.  64-bit integer atomics: duplicated sel within one launch give the exact
+ *   sum.  One launch.  PN2_ERANGE: b * npts >= 2^31.
+ *
+ * pn2_score_labels: labels[i] = the first maximal class of scores[i, :] (an all-zero row gives 0, "unlabeled", like
+ *   pn2_tile_labels); confidence[i] (optional, float32) = (float)((double)top / (double)total), total the sum of the row, and 0
+ *   when total == 0.  Contract: entries >= 0, row sums below 2^63.  One launch.
+ *
+ * pn2_interpolate_scores: the soft twin of pn2_interpolate_label_with_color, with its grid, its exact search (float64 squared L2
+ *   ((dx*dx + dy*dy) + dz*dz), ascending, ties -> lowest index, min(knn, ns) neighbours), its workspace and its size query
+ *   (pn2_interpolate_label_workspace_bytes(ns)); knn <= 16 (PN2_EUNSUP above).  sparse_scores (ns,num_class) int64; contract:
+ *   entries >= 0, row sums <= 2^58.  For a dense point S_c = the int64 sum of sparse_scores[j, c] over its neighbours;
+ *   dense_labels = the first maximal S_c (all zero -> 0), dense_colors the colour of that label from the table of the label
+ *   form, dense_confidence (optional) as in pn2_score_labels.  ns == 0 gives label -1, colour 0, confidence 0.  It queues what
+ *   the label form queues: the grid build (its launches, two memsets and a radix sort) and one query launch.  nd == 0 is PN2_OK
+ *   whatever the pointers; PN2_EINVAL also for a workspace that is too small. */
+int pn2_softmax_scores(int rows, int num_class, const float *logits, int *q, long long *invalid, void *stream);
+int pn2_tile_vote_scores(int b, int npts, int num_class, const int *sel, const int *live, const int *q, long long *scores,
+                         long long *dropped, void *stream);
+int pn2_score_labels(int n, int num_class, const long long *scores, int *labels, float *confidence, void *stream);
+int pn2_interpolate_scores(int ns, int nd, int num_class, const float *sparse_points, const long long *sparse_scores,
+                           const float *dense_points, int *dense_labels, uint8_t *dense_colors, float *dense_confidence, int knn,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

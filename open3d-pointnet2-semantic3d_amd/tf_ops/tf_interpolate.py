@@ -106,3 +106,37 @@ def interpolate_label_with_color(sparse_points, sparse_labels, dense_points, knn
     launch("pn2_interpolate_label_with_color", dev, ns, nd, ptr(sp), ptr(sl), ptr(dp), ptr(labels), ptr(colors), knn, ptr(ws, off),
            wbytes)
     return labels, colors
+
+
+def interpolate_scores_with_color(sparse_points, sparse_scores, dense_points, knn):
+    """The soft twin of interpolate_label_with_color: sparse_points (ns,3) f32, sparse_scores (ns,C) int64 (accumulated score
+    rows in units of 2^-30: predict.predict_scene_tiled(vote="soft")), dense_points (nd,3) f32, knn int -> (dense_labels (nd,)
+    int32, dense_colors (nd,3) uint8, dense_confidence (nd,) float32): the scores of the knn nearest sparse points are summed
+    class by class in int64, the label is the first class with the largest sum and the confidence that sum's share of the total
+    (pn2_interpolate_scores).  The same exact search and the same argument checks as the label form."""
+    require_cuda(sparse_points, sparse_scores, dense_points)
+    if sparse_points.dim() != 2 or sparse_points.shape[1] != 3:
+        raise ValueError("sparse_points must be: (num_sparse_points, 3)")
+    ns = sparse_points.shape[0]
+    if sparse_scores.dim() != 2 or sparse_scores.shape[0] != ns or sparse_scores.shape[1] < 1:
+        raise ValueError("sparse_scores must be: (num_sparse_points, num_class)")
+    if dense_points.dim() != 2 or dense_points.shape[1] != 3:
+        raise ValueError("dense_points must be: (num_dense_points, 3)")
+    if not isinstance(knn, int) or isinstance(knn, bool):
+        raise ValueError("knn must be an int scalar")
+    if knn <= 0:
+        raise ValueError("knn must be positive")
+    if sparse_points.dtype != torch.float32 or dense_points.dtype != torch.float32 or sparse_scores.dtype != torch.int64:
+        raise TypeError("InterpolateScoresWithColor expects float32 points and int64 scores")
+    nd, c = dense_points.shape[0], sparse_scores.shape[1]
+    dev = dense_points.device
+    sp, ss, dp = sparse_points.contiguous(), sparse_scores.contiguous(), dense_points.contiguous()
+    labels = torch.empty((nd,), dtype=torch.int32, device=dev)
+    colors = torch.empty((nd, 3), dtype=torch.uint8, device=dev)
+    confidence = torch.empty((nd,), dtype=torch.float32, device=dev)
+    wbytes = int(lib.pn2_interpolate_label_workspace_bytes(ns))
+    ws = torch.empty((wbytes + 256,), dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    launch("pn2_interpolate_scores", dev, ns, nd, c, ptr(sp), ptr(ss), ptr(dp), ptr(labels), ptr(colors), ptr(confidence), knn,
+           ptr(ws, off), wbytes)
+    return labels, colors, confidence
