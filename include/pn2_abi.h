@@ -566,7 +566,10 @@ int pn2_scene_sample(int b, int npts, int cap, const double *points, const int *
  * min_bound = min(points) - voxel_size/2 + np.bincount(labels).argmax() per voxel.  points/colors (n,3) float64,
  * labels (n) int32 in [0,64) or NULL.  Outputs sized for n voxels; *out_count (device) = number of voxels, sorted by
  * (ix,iy,iz) (Open3D's own order is unspecified).  status (device): 0 ok, 1 voxel index needs more than 21 bits,
- * 2 label outside [0,64).  workspace: 256-byte aligned, pn2_voxel_downsample_workspace_bytes(n) bytes. */
+ * 2 label outside [0,64), 3 a NaN or +-inf coordinate (outranks 1; a bad label in the same cloud may leave 2 instead).
+ * With a non-zero status the outputs are written inside their n rows but hold nothing of use.  out_colors and
+ * out_labels may be NULL.  n <= 0 is PN2_EINVAL: a caller with nothing to down-sample does not call.
+ * workspace: 256-byte aligned, pn2_voxel_downsample_workspace_bytes(n) bytes. */
 size_t pn2_voxel_downsample_workspace_bytes(int n);
 int pn2_voxel_downsample(int n, const double *points, const double *colors, const int *labels, double voxel_size,
                          double *out_points, double *out_colors, int *out_labels, int *out_count, int *status,

@@ -100,6 +100,7 @@ scene_sample_kernel(int npts, int cap, const double* __restrict__ pts, const int
 // members IN INPUT ORDER divided by their count.  Its output ORDER is the iteration order of a std::unordered_map and
 // therefore unspecified: here voxels come out sorted by (ix, iy, iz).  Label of a voxel = np.bincount(labels).argmax()
 // (downsample.py:57-62): the most frequent label, ties -> the smallest label.
+// fmin / fmax skip a NaN and take an infinity: neither is reported here, voxel_key_kernel refuses both (status 3) on the row itself.
 __global__ void voxel_minmax_kernel(int n, const double* __restrict__ pts, double* __restrict__ mm /* 6: min xyz, max xyz, as ordered u64 */) {
     __shared__ double sm[6][4];
     double lo[3] = {1.0e300, 1.0e300, 1.0e300}, hi[3] = {-1.0e300, -1.0e300, -1.0e300};
@@ -134,9 +135,15 @@ __global__ void voxel_key_kernel(int n, const double* __restrict__ pts, const do
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const double mb = ordered_to_double(reinterpret_cast<const unsigned long long*>(mm)[a]) - vs * 0.5;  // downsample.py:47
-        const double r = (pts[i * 3 + a] - mb) / vs;  // a true division, as Open3D does
-        const long long c = (long long)floor(r);
-        if (c < 0 || c >= (1ll << 21)) { atomicExch(err, 1); }
+        const double p = pts[i * 3 + a];
+        const double r = (p - mb) / vs;  // a true division, as Open3D does
+        // The range is tested on the double, before any conversion: (long long) of a NaN or of a value past 2^63 is undefined.
+        // A NaN or +-inf coordinate always lands here (r is NaN or +-inf, whatever the bound: fmin / fmax above skip a NaN and
+        // take an infinity), so no minimum taken from one goes unreported; 3 outranks 1, which the finite rows of a cloud
+        // that holds a -inf raise as well.  A refused row gets index 0: every later pass stays inside its n rows.
+        long long c = 0;
+        if (!(r >= 0.0 && r < 2097152.0)) atomicMax(err, isfinite(p) ? 1 : 3);
+        else c = (long long)floor(r);
         key = (key << 21) | (unsigned long long)(c & 0x1FFFFF);
     }
     keys[i] = key;
@@ -254,7 +261,8 @@ extern "C" size_t pn2_voxel_downsample_workspace_bytes(int n) { return n > 0 ? v
 
 // downsample.py:46-67.  points/colors (n,3) float64, labels (n) int32 in [0,64) or NULL.  Outputs sized for n voxels:
 // out_points / out_colors (n,3) float64, out_labels (n); *out_count (device int) = number of voxels; voxels sorted by
-// (ix,iy,iz).  status (device int): 0 ok, 1 voxel index outside 21 bits per axis, 2 label outside [0,64).
+// (ix,iy,iz).  status (device int): 0 ok, 1 voxel index outside 21 bits per axis, 2 label outside [0,64), 3 a NaN or +-inf
+// coordinate (outranks 1; a bad label in the same cloud may leave 2 instead).  Non-zero: the outputs hold nothing of use.
 extern "C" int pn2_voxel_downsample(int n, const double* points, const double* colors, const int* labels, double voxel_size,
                                     double* out_points, double* out_colors, int* out_labels, int* out_count, int* status,
                                     void* workspace, size_t workspace_bytes, void* stream) {
