@@ -10,11 +10,15 @@
     --ckpt FILE   a checkpoint written by Trainer.save() (without it: fresh random weights, for a dry run)
     --data PATH   the preprocessed (down-sampled) Semantic3D files, <PATH>/<scene>.pcd and .labels (dataset/semantic_data)
     --raw PATH    the dense clouds, <PATH>/<scene>.pcd and, where they exist, .labels (dataset/semantic_raw)
+                  (--data and --raw: a scene without a .pcd is read from <scene>.ply where that exists)
     without --data / --raw: small synthetic scenes -- a raw cloud as the dense side, its down_sample_arrays result as the store
 
     --tiled       instead of num_samples random columns, the tiled cover of the scene (pn2.predict.predict_scene_tiled): every
                   point of the store is predicted --phases times (1: one grid; 2: a second grid shifted by half a box votes
                   too) and the sparse side of the 3-NN vote is the whole store; columns below --min-points points are skipped
+
+    --format      the point-cloud files written under result/: pcd (binary PCD, the default) or ply (binary little-endian PLY,
+                  float coordinates, uchar colours)
 
     --soft        soft voting: the class probabilities (score rows, integers in units of 2^-30) are kept instead of their argmax.
                   With --tiled they are summed over the grids (predict_scene_tiled(vote="soft")), without it they are the score
@@ -22,7 +26,7 @@
                   whose scores summed over its 3 nearest sparse points are the largest (pn2.predict.label_dense_scores)
 
 usage: python examples/predict_semantic3d.py [--ckpt FILE] [--set validation] [--num_samples 8] [--data PATH --raw PATH]
-       [--tiled [--phases 1|2] [--min-points K]] [--soft]
+       [--tiled [--phases 1|2] [--min-points K]] [--soft] [--format pcd|ply]
        size flags (synthetic runs, tests): --points N --npoint a,b,c,d --scene-points P --scenes K --voxel V --batch-size B"""
 import argparse
 import os
@@ -51,7 +55,7 @@ def synthetic_scene(seed, n, ex, ey):
 
 def load_scenes(args, hp, dev):
     """-> dataset (the down-sampled store), dense {scene name: (points float32 (nd,3), labels int32 (nd,) or None)}: device
-    tensors when read from files (pn2.read_point_cloud_pcd / pn2.load_labels), numpy arrays for the synthetic scenes"""
+    tensors when read from files (pn2.read_point_cloud / pn2.load_labels), numpy arrays for the synthetic scenes"""
     N = hp["num_point"]
     if args.data:
         ds = pn2.dataset.SemanticDataset(N, args.set, hp["use_color"], hp["box_size_x"], hp["box_size_y"], args.data, device=dev,
@@ -59,7 +63,7 @@ def load_scenes(args, hp, dev):
         dense = {}
         for name in ds.scene_names:
             prefix = os.path.join(args.raw or args.data, name)
-            pts, _ = pn2.read_point_cloud_pcd(prefix + ".pcd", dev, want_colors=False)
+            pts, _ = pn2.read_point_cloud(pn2.util.point_cloud_util.scene_path(prefix), dev, want_colors=False)
             labels = pn2.load_labels(prefix + ".labels", dev) if os.path.exists(prefix + ".labels") else None
             dense[name] = (pts.to(torch.float32), labels)
         return ds, dense
@@ -102,6 +106,7 @@ def main():
     ap.add_argument("--tiled", action="store_true", help="label every point of the store: the tiled cover, not random columns")
     ap.add_argument("--phases", type=int, choices=(1, 2), default=1, help="--tiled: grids that vote (2: one shifted by half a box)")
     ap.add_argument("--min-points", type=int, default=1, help="--tiled: columns with fewer points are skipped")
+    ap.add_argument("--format", choices=("pcd", "ply"), default="pcd", help="format of the point-cloud files written")
     ap.add_argument("--soft", action="store_true", help="vote with class probabilities instead of labels, through to the dense cloud")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -118,6 +123,7 @@ def main():
     os.makedirs(sparse_dir, exist_ok=True)
     os.makedirs(dense_dir, exist_ok=True)
 
+    write_cloud = pn2.write_point_cloud_ply if args.format == "ply" else pn2.write_point_cloud_pcd
     dataset, dense = load_scenes(args, hp, dev)
     predictor = pn2.predict.Predictor(args.ckpt or None, dataset.num_classes, hp, device=dev)
     print("Model restored" if args.ckpt else "No checkpoint: random weights")
@@ -143,9 +149,9 @@ def main():
             dataset.check_last()
             torch.cuda.synchronize()
             print("    %d samples of %d points in %.1f ms" % (args.num_samples, hp["num_point"], (time.perf_counter() - t0) * 1e3))
-        pn2.write_point_cloud_pcd(os.path.join(sparse_dir, name + ".pcd"), points)
+        write_cloud(os.path.join(sparse_dir, name + "." + args.format), points)
         pn2.write_labels(os.path.join(sparse_dir, name + ".labels"), labels)
-        print("    Exported sparse pcd and labels to %s" % os.path.join(sparse_dir, name))
+        print("    Exported sparse %s and labels to %s" % (args.format, os.path.join(sparse_dir, name)))
 
         dense_points, dense_gt = dense[name]
         cm = M.ConfusionMatrix(dataset.num_classes, device=dev)
@@ -160,8 +166,8 @@ def main():
         if args.soft:
             print("    Soft vote: mean confidence of the dense labels %.4f" % float(confidence.mean()))
         pn2.write_labels(os.path.join(dense_dir, name + ".labels"), dense_labels)
-        pn2.write_point_cloud_pcd(os.path.join(dense_dir, name + "_colored.pcd"), dense_points, dense_colors)  # uint8 as it is
-        print("    Dense labels and coloured pcd written to %s" % os.path.join(dense_dir, name))
+        write_cloud(os.path.join(dense_dir, name + "_colored." + args.format), dense_points, dense_colors)  # uint8 as it is
+        print("    Dense labels and coloured %s written to %s" % (args.format, os.path.join(dense_dir, name)))
         if dense_gt is not None:
             cm.print_metrics(dataset.labels_names)
             cm_global.counts += cm.counts

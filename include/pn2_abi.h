@@ -941,6 +941,52 @@ int pn2_pcd_pack(const void *points, int point_kind, const void *colors, int col
 int pn2_pcd_unpack(const unsigned int *rows, int n, int nfields, int ix, int iy, int iz, int irgb, double *points,
                    double *colors, void *stream);
 
+/* ---- records: rows of any byte stride with typed fields at any byte offset (csrc/pn2_records.hip) -- the payload of a binary
+ * .ply, and of a .pcd whose fields have any SIZE / TYPE / COUNT.  A record is `stride` bytes, 1 <= stride <=
+ * PN2_REC_MAX_STRIDE (PN2_EUNSUP above), n * stride <= PN2_REC_MAX_BYTES (int offsets, PN2_ERANGE).  Seven slots describe the
+ * fields: x y z c0 c1 c2 label, each with a byte offset (-1: absent) and a type code PN2_REC_*; offsets and types are HOST
+ * int[PN2_REC_SLOTS] arrays read at call time.  flags: PN2_REC_BIG_ENDIAN (the fields are big-endian), PN2_REC_FORM_PLAIN (run
+ * the row-per-lane form even where the staged one applies: same bytes, for tests and measurements).
+ * pn2_record_unpack -> points (n,3) float64: the value of x y z, exact (every type is a subset of float64).
+ *   colors (n,3) float64, NULL: not written.  PN2_REC_COLOUR_NONE: zeros.  PN2_REC_COLOUR_THREE: channels c0 c1 c2.
+ *   PN2_REC_COLOUR_PACKED: one 4-byte word in c0 holding 0x00RRGGBB (PCD's rgb / rgba), each byte / 255.0.  The channel rules
+ *   are THIS PROJECT'S OWN DEFINITION, not a standard's: a U8 channel is byte / 255.0 correctly rounded (pn2_pcd_unpack's rule),
+ *   a U16 channel v / 65535.0, an F32 / F64 channel the value itself; other integer types PN2_EUNSUP.
+ *   labels (n) int32, NULL: not written.  An integer field converted to int32 (U32 reinterpreted).  A float field must be finite,
+ *   integral and inside int32; otherwise the label is 0 and *invalid (device int64, ADDED to; required for a float label) goes
+ *   up by one.
+ *   A slot is read only where its output is asked for: x y z always, the colour slots with colors, the label with labels.
+ * pn2_record_pack: the inverse for the layouts the writers need -- x y z as coord_type PN2_REC_F32 ((float)p) or PN2_REC_F64
+ *   from points (n,3) PN2_PCD_F32 / PN2_PCD_F64; then, with color_kind PN2_PCD_COLOR_U8 / _F64, three U8 channels (the byte
+ *   itself / clip(floor(c * 255.0), 0, 255), a NaN 0: pn2_pcd_pack's rule); then, with labels != NULL, an I32.  Tightly packed
+ *   in that order, little-endian: stride 12 / 24 + 3 + 4.
+ * Checks in this order: n, stride, kinds and flags PN2_EINVAL; stride above the limit PN2_EUNSUP; NULL pointers PN2_ENULL;
+ * PN2_ERANGE; then PN2_EINVAL for an unknown type code, a wanted field that is absent or reaches past stride, two wanted fields
+ * that overlap, rows not 16-byte aligned, an output not naturally aligned.
+ * Memory: global memory is touched with naturally aligned accesses only; unpack reads no byte at or past n * stride rounded up
+ * to 16, pack writes no byte at or past n * stride.  Strides up to PN2_REC_STAGE_BYTES / 64 go through LDS in 16-byte pieces. */
+#define PN2_REC_U8 0
+#define PN2_REC_I8 1
+#define PN2_REC_U16 2
+#define PN2_REC_I16 3
+#define PN2_REC_U32 4
+#define PN2_REC_I32 5
+#define PN2_REC_F32 6
+#define PN2_REC_F64 7
+#define PN2_REC_BIG_ENDIAN 1
+#define PN2_REC_FORM_PLAIN 2
+#define PN2_REC_COLOUR_NONE 0
+#define PN2_REC_COLOUR_THREE 1
+#define PN2_REC_COLOUR_PACKED 2
+#define PN2_REC_SLOTS 7
+#define PN2_REC_MAX_STRIDE 1024
+#define PN2_REC_MAX_BYTES 2147483632 /* 2^31 - 16 */
+#define PN2_REC_STAGE_BYTES 32768
+int pn2_record_unpack(const void *rows, int n, int stride, const int *offsets, const int *types, int colour_kind, int flags,
+                      double *points, double *colors, int *labels, long long *invalid, void *stream);
+int pn2_record_pack(const void *points, int point_kind, const void *colors, int color_kind, const int *labels, int n,
+                    int coord_type, int flags, void *rows, void *stream);
+
 /* ---- point-cloud augmentation: util/provider.py of the reference as one pipeline (csrc/pn2_augment.hip) ------------------
  * in (b,n,c) float32 -> out (b,n,c) float32, c >= 3, xyz in channels 0:3; in_labels (b,n) int32 -> out_labels and in_weights
  * (b,n) float32 -> out_weights are optional companions (both of a pair or neither) that are only ever permuted.  Stages run

@@ -7,6 +7,7 @@
 // Built like the rest of the library: no fast-math (the colour rule needs IEEE fp64 multiply and divide), no inline assembly.
 #include <hipcub/hipcub.hpp>
 
+#include "pn2_color.h"  // unit_to_byte
 #include "pn2_common.h"
 #include "pn2_itoa.h"
 #include "pn2_wg.h"  // al256
@@ -109,12 +110,6 @@ inline hipError_t format_layout(int nrows, FormatLayout& L) {
 
 // ---- binary .pcd rows ---------------------------------------------------------------------------------------------------------
 constexpr int kPcdT = 256;
-
-// floor(c * 255.0) clipped to [0, 255], the host writer's np.clip(np.floor(c * 255.0), 0, 255); a NaN gives 0
-__device__ __forceinline__ unsigned unit_to_byte(double c) {
-    const double t = __builtin_floor(c * 255.0);
-    return t >= 255.0 ? 255u : (t > 0.0 ? (unsigned)t : 0u);
-}
 
 template <class P>
 __global__ void __launch_bounds__(kPcdT)

@@ -30,7 +30,7 @@ import torch
 
 from .._lib import launch, ptr, u64_array
 from ..util.metric import SEMANTIC3D_LABELS_NAMES
-from ..util.point_cloud_util import load_labels, read_point_cloud_pcd
+from ..util.point_cloud_util import load_labels, read_point_cloud, scene_path
 
 _SPLITS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "semantic3d_splits.json")
 _CHUNK = 1024  # slab points per chunk in csrc/pn2_dataset.hip
@@ -102,7 +102,7 @@ class SemanticDataset:
         ingest="host": the scenes are read, sorted by x and measured in numpy; scene_points / scene_labels / scene_colors are
         host arrays and the store is uploaded by the first sample call.
         ingest="device": the store is built in HBM by pn2_scene_ingest (csrc/pn2_store.hip), one call per scene, straight into
-        the scene's slice: files are read by scene_io.read_point_cloud_pcd / preprocess.load_labels, `scenes` may hold device
+        the scene's slice: files are read by scene_io.read_point_cloud / preprocess.load_labels, `scenes` may hold device
         tensors (points float32 / float64, labels of any integer or bool dtype, colours float) or host arrays (uploaded once);
         nothing of a scene's size comes back to the host.  scene_points / scene_labels / scene_colors are then device views of
         the store (float64, uint8, float32; scene_colors[i] is None without colour).  Rows with equal x keep their input order
@@ -137,7 +137,7 @@ class SemanticDataset:
                 scenes = []
                 for name in table[split]:
                     prefix = os.path.join(path, name)
-                    pts, cols = read_point_cloud_pcd(prefix + ".pcd")
+                    pts, cols = read_point_cloud(scene_path(prefix))  # <scene>.pcd, else <scene>.ply
                     labels = load_labels(prefix + ".labels") if has_label else None
                     scenes.append((pts, labels, cols, name))
         if not scenes:
@@ -196,7 +196,7 @@ class SemanticDataset:
         read from <path>/<name>.pcd and .labels.  One workspace, sized for the largest scene, serves every call; per scene one
         96-byte read-back (z range, label histogram, status).  -> counts [n], scene_z_size (ns,) float64, hists (ns,9) int64"""
         from .. import preprocess, scene_io  # (they import this package's siblings: not at module level)
-        from ..util.point_cloud_util import read_pcd_header
+        from ..util.point_cloud_util import read_pcd_layout, read_ply_header
         dev = self.device
         if dev.type != "cuda":
             raise ValueError("ingest='device' builds the store on the MI355X: got device %s (there is no CPU path in the "
@@ -206,8 +206,9 @@ class SemanticDataset:
         counts = []
         for pts, _, _, name in scenes:
             if pts is None:
-                with open(os.path.join(self.path, name) + ".pcd", "rb") as f:
-                    n = read_pcd_header(f)[1]
+                file_path = scene_path(os.path.join(self.path, name))
+                with open(file_path, "rb") as f:
+                    n = read_ply_header(f).n if file_path.endswith(".ply") else read_pcd_layout(f).n
             else:
                 n = int(np.prod(tuple(pts.shape))) // 3 if hasattr(pts, "shape") else len(np.asarray(pts).reshape(-1, 3))
             if n == 0:
@@ -234,7 +235,7 @@ class SemanticDataset:
         for k, ((pts, labels, cols, name), n) in enumerate(zip(scenes, counts)):
             if pts is None:
                 prefix = os.path.join(self.path, name)
-                pts, cols = scene_io.read_point_cloud_pcd(prefix + ".pcd", dev, want_colors=self.use_color)
+                pts, cols = scene_io.read_point_cloud(scene_path(prefix), dev, want_colors=self.use_color)
                 labels = preprocess.load_labels(prefix + ".labels", dev) if has_label else None
             if torch.is_tensor(pts):
                 if not pts.dtype.is_floating_point:

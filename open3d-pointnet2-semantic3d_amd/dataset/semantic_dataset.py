@@ -11,7 +11,7 @@ to float32, the dtype the network is fed with.
 import torch
 
 from .._lib import launch, ptr, require_cuda
-from ..util.point_cloud_util import load_labels, read_point_cloud_pcd
+from ..util.point_cloud_util import load_labels, read_point_cloud, scene_path
 
 
 class SemanticFileData:
@@ -26,7 +26,7 @@ class SemanticFileData:
         # sample (status != 0) comes back ZERO-FILLED, never as uninitialised memory, and check_last() reports it.
         self.strict = bool(strict)
         if points is None:
-            points, file_colors = read_point_cloud_pcd(file_path_without_ext + ".pcd")
+            points, file_colors = read_point_cloud(scene_path(file_path_without_ext))  # <prefix>.pcd, else <prefix>.ply
             labels = load_labels(file_path_without_ext + ".labels") if has_label else np.zeros(len(points), dtype=bool)
             colors = file_colors if use_color else np.zeros_like(points)
         points = np.asarray(points, dtype=np.float64)

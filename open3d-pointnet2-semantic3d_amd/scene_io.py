@@ -11,11 +11,20 @@ bytes of the host writer's, every array the bits of the host reader's.
     write_labels(path, labels)                                  # labels: device tensor or array of any integer dtype
     write_point_cloud_pcd(path, points, colors=None)            # points f32 / f64, colors f64 in [0,1] or uint8
     points, colors = read_point_cloud_pcd(path, device)         # (n,3) f64, (n,3) f64 (None with want_colors=False)
+
+Binary .ply files, and .pcd files whose fields are not all 4 bytes wide, are rows of any byte stride with typed fields at any
+byte offset: csrc/pn2_records.hip unpacks and packs them, the headers are read and written by util.point_cloud_util.
+
+    write_point_cloud_ply(path, points, colors=None, labels=None, coord="float")
+    points, colors[, labels] = read_point_cloud_ply(path, device, want_labels=False)
+    points, colors = read_point_cloud(path, device)             # by the extension: .pcd or .ply
 """
+import os
+
 import numpy as np
 import torch
 
-from ._lib import ABI, launch, ptr, u64_array
+from ._lib import ABI, int_array, launch, ptr, u64_array
 from .preprocess import _aligned
 from .util import point_cloud_util
 
@@ -26,6 +35,10 @@ MAX_PCD_ROWS = ABI.constants["PN2_PCD_MAX_ROWS"]
 MAX_PCD_FIELDS = ABI.constants["PN2_PCD_MAX_FIELDS"]
 _POINT_KINDS = {torch.float32: ABI.constants["PN2_PCD_F32"], torch.float64: ABI.constants["PN2_PCD_F64"]}
 _COLOR_NONE, _COLOR_F64, _COLOR_U8 = (ABI.constants["PN2_PCD_COLOR_" + k] for k in ("NONE", "F64", "U8"))
+MAX_REC_STRIDE = ABI.constants["PN2_REC_MAX_STRIDE"]
+MAX_REC_BYTES = ABI.constants["PN2_REC_MAX_BYTES"]
+_REC_BIG_ENDIAN = ABI.constants["PN2_REC_BIG_ENDIAN"]
+_COORD_TYPES = {"float": (ABI.constants["PN2_REC_F32"], 12), "double": (ABI.constants["PN2_REC_F64"], 24)}
 DEFAULT_CHUNK_ROWS = 1 << 20  # 12 MiB of label text at its worst case, 16 MiB of .pcd rows: per chunk one copy and one file call
 
 
@@ -201,15 +214,16 @@ def write_point_cloud_pcd(path, points, colors=None, chunk_rows=DEFAULT_CHUNK_RO
             _stream_out(f, dev, (n + rows - 1) // rows, rows * row_bytes, produce)
 
 
-def _stream_in(f, dev, total_bytes, chunk_bytes, consume):
+def _stream_in(f, dev, total_bytes, chunk_bytes, consume, what="PCD"):
     """The upload pipeline of the reader (preprocess._parse_host for fixed-size chunks): the payload is read into two pinned
     buffers in turn, copied on a copy stream, and consume(k, device bytes) queues chunk k's kernels on the caller's stream
-    while chunk k + 1 is read and copied.  A payload shorter than total_bytes: ValueError."""
+    while chunk k + 1 is read and copied.  A payload shorter than total_bytes: ValueError.  The device buffers end at a multiple
+    of 16 bytes, so a kernel may read the 16-byte piece that a chunk's last byte lies in (pn2_record_unpack does)."""
     copy_stream = None
     try:
         nchunks = (total_bytes + chunk_bytes - 1) // chunk_bytes
         pinned = [torch.empty((chunk_bytes,), dtype=torch.uint8).pin_memory() for _ in range(min(2, nchunks))]
-        staged = [_aligned(chunk_bytes, dev) for _ in range(min(2, nchunks))]
+        staged = [_aligned((chunk_bytes + 15) & ~15, dev) for _ in range(min(2, nchunks))]
         copy_stream = torch.cuda.Stream(dev)
         main = torch.cuda.current_stream(dev)
         copied = [torch.cuda.Event(), torch.cuda.Event()]    # the upload of the buffer has finished (its pinned half is free)
@@ -223,7 +237,7 @@ def _stream_in(f, dev, total_bytes, chunk_bytes, consume):
             while got < nbytes:
                 step = f.readinto(view[got:])
                 if not step:
-                    raise ValueError("truncated PCD payload: %d bytes missing" % (total_bytes - k * chunk_bytes - got))
+                    raise ValueError("truncated %s payload: %d bytes missing" % (what, total_bytes - k * chunk_bytes - got))
                 got += step
             with torch.cuda.stream(copy_stream):
                 copy_stream.wait_event(consumed[b])  # recorded two chunks ago (a fresh event: no wait)
@@ -240,16 +254,22 @@ def _stream_in(f, dev, total_bytes, chunk_bytes, consume):
 def read_point_cloud_pcd(path, device="cuda", want_colors=True, chunk_rows=DEFAULT_CHUNK_ROWS):
     """-> points (n,3) float64, colors (n,3) float64 in [0,1] (zeros when the file has no rgb; None with want_colors=False) on
     the device, the bits of util.point_cloud_util.read_point_cloud_pcd.  The header is parsed on the host; a binary payload is
-    streamed in chunks of chunk_rows whole rows and unpacked on the device; DATA ascii goes through the host reader."""
+    streamed in chunks of chunk_rows whole rows and unpacked on the device; DATA ascii goes through the host reader.  Fields
+    that are all 4 bytes with COUNT 1 are unpacked by pn2_pcd_unpack, any other layout (SIZE 1 / 2 / 8, COUNT above 1) by
+    pn2_record_unpack; a row of more than PN2_REC_MAX_STRIDE bytes: ValueError."""
     dev = _device(device)
     chunk_rows = int(chunk_rows)
     if not 0 < chunk_rows <= MAX_PCD_ROWS:
         raise ValueError("chunk_rows must lie in [1, %d]" % MAX_PCD_ROWS)
     with open(path, "rb") as f:
-        fields, n, data = point_cloud_util.read_pcd_header(f)
+        layout = point_cloud_util.read_pcd_layout(f)
+        fields, n, data = layout.fields, layout.n, layout.data
         if data == "ascii":
             points, colors = point_cloud_util.read_point_cloud_pcd(path)
             return torch.from_numpy(points).to(dev), (torch.from_numpy(colors).to(dev) if want_colors else None)
+        if not point_cloud_util.pcd_is_words(layout):
+            return _unpack_stream(f, dev, n, layout.stride, point_cloud_util.pcd_slots(layout), False, want_colors, False,
+                                  chunk_rows, "PCD")[:2]
         nf = len(fields)
         if nf > MAX_PCD_FIELDS:
             raise ValueError("a PCD row of more than %d fields" % MAX_PCD_FIELDS)
@@ -268,3 +288,100 @@ def read_point_cloud_pcd(path, device="cuda", want_colors=True, chunk_rows=DEFAU
 
                 _stream_in(f, dev, n * 4 * nf, rows * 4 * nf, consume)
         return points, colors
+
+
+def _unpack_stream(f, dev, n, stride, slots, big, want_colors, want_labels, chunk_rows, what):
+    """the payload of n records at f, streamed in chunks of whole rows through pn2_record_unpack -> points, colors, labels
+    (None where not wanted).  slots: (offsets, types, colour kind) as util.point_cloud_util.unpack_records takes them."""
+    offsets, types, colour_kind = slots
+    if stride > MAX_REC_STRIDE:
+        raise ValueError("a %s row of %d bytes: more than %d" % (what, stride, MAX_REC_STRIDE))
+    with torch.cuda.device(dev):
+        points = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        colors = torch.empty((n, 3), dtype=torch.float64, device=dev) if want_colors else None
+        labels = torch.empty((n,), dtype=torch.int32, device=dev) if want_labels else None
+        invalid = torch.zeros((1,), dtype=torch.int64, device=dev)  # float labels that are no int32: they read as 0
+        if n:
+            rows = min(chunk_rows, n, MAX_REC_BYTES // stride)
+            off_a, type_a = int_array(offsets), int_array(types)  # host arrays, read by the call
+
+            def consume(k, rows_bytes):
+                lo, m = k * rows, rows_bytes.numel() // stride
+                launch("pn2_record_unpack", dev, ptr(rows_bytes), m, stride, off_a, type_a, colour_kind,
+                       _REC_BIG_ENDIAN if big else 0, ptr(points[lo:lo + m]), None if colors is None else ptr(colors[lo:lo + m]),
+                       None if labels is None else ptr(labels[lo:lo + m]), ptr(invalid))
+
+            _stream_in(f, dev, n * stride, rows * stride, consume, what)
+    return points, colors, labels
+
+
+def read_point_cloud_ply(path, device="cuda", want_colors=True, want_labels=False, label_property=None,
+                         chunk_rows=DEFAULT_CHUNK_ROWS):
+    """-> points (n,3) float64, colors (n,3) float64 (zeros without red green blue; None with want_colors=False) [, labels (n,)
+    int32 with want_labels] on the device, the bits of util.point_cloud_util.read_point_cloud_ply.  The header is parsed on the
+    host; a binary payload of either byte order is streamed in chunks of chunk_rows whole rows and unpacked by
+    pn2_record_unpack; format ascii goes through the host reader.  The label is the first present of label, class,
+    scalar_label, or label_property; a float label that is no int32 reads as 0."""
+    dev = _device(device)
+    chunk_rows = int(chunk_rows)
+    if chunk_rows <= 0:
+        raise ValueError("chunk_rows must be positive")
+    with open(path, "rb") as f:
+        h = point_cloud_util.read_ply_header(f, label_property)
+        if want_labels and h.slots[0][6] < 0:
+            raise ValueError("a PLY without a label property (one of %s)" % ", ".join(point_cloud_util.PLY_LABEL_NAMES))
+        if h.format == "ascii":
+            out = point_cloud_util.read_point_cloud_ply(path, want_labels, label_property)
+            out = [torch.from_numpy(a).to(dev) for a in out]
+            out[1] = out[1] if want_colors else None
+        else:
+            out = _unpack_stream(f, dev, h.n, h.stride, h.slots, h.format == "binary_big_endian", want_colors, want_labels,
+                                 chunk_rows, "PLY")
+    return tuple(out[:3]) if want_labels else tuple(out[:2])
+
+
+def write_point_cloud_ply(path, points, colors=None, labels=None, coord="float", chunk_rows=DEFAULT_CHUNK_ROWS):
+    """points (n,3) float32 / float64, colors (n,3) float64 in [0,1] or uint8, labels (n,) integers (or None): device tensors or
+    arrays -> a binary little-endian PLY of x y z (coord: float or double) [red green blue uchar] [label int], the file of
+    util.point_cloud_util.write_point_cloud_ply byte for byte.  The rows are packed on the device, chunk_rows per call; n = 0
+    writes the header only."""
+    n, chunk_rows = int(points.shape[0]), int(chunk_rows)
+    if tuple(points.shape) != (n, 3) or (colors is not None and tuple(colors.shape) != (n, 3)) or (
+            labels is not None and tuple(labels.shape) != (n,)):
+        raise ValueError("points and colors: (n, 3), labels: (n,)")
+    if chunk_rows <= 0:
+        raise ValueError("chunk_rows must be positive")
+    header = point_cloud_util.ply_header(n, coord, colors is not None, labels is not None)  # coord is checked here
+    coord_type, row_bytes = _COORD_TYPES[coord]
+    row_bytes += (3 if colors is not None else 0) + (4 if labels is not None else 0)
+    with open(path, "wb") as f:
+        f.write(header.encode())
+        if n == 0:
+            return
+        dev = _where(points)
+        with torch.cuda.device(dev):
+            rows = min(chunk_rows, n, MAX_REC_BYTES // row_bytes)
+
+            def produce(k, out):
+                lo, hi = k * rows, (k + 1) * rows
+                p = _rows_on(points, lo, hi, dev, _POINT_KINDS, "points: float32 or float64")
+                c = None if colors is None else _rows_on(colors, lo, hi, dev, (torch.float64, torch.uint8),
+                                                         "colors: float64 in [0, 1] or uint8")
+                lab = None if labels is None else _rows_i32(labels, lo, hi, dev)
+                kind = _COLOR_NONE if c is None else (_COLOR_U8 if c.dtype == torch.uint8 else _COLOR_F64)
+                launch("pn2_record_pack", dev, ptr(p), _POINT_KINDS[p.dtype], ptr(c), kind, ptr(lab), p.shape[0], coord_type, 0,
+                       ptr(out))
+                return p.shape[0] * row_bytes
+
+            _stream_out(f, dev, (n + rows - 1) // rows, rows * row_bytes, produce)
+
+
+def read_point_cloud(path, device="cuda", **kw):
+    """read_point_cloud_pcd or read_point_cloud_ply by the extension of path (.pcd / .ply in either case), with their keywords;
+    any other extension: ValueError"""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".pcd":
+        return read_point_cloud_pcd(path, device, **kw)
+    if ext == ".ply":
+        return read_point_cloud_ply(path, device, **kw)
+    raise ValueError("a scene file is .pcd or .ply, got %s" % path)
