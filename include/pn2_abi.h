@@ -1202,6 +1202,45 @@ int pn2_interpolate_scores(int ns, int nd, int num_class, const float *sparse_po
                            const float *dense_points, int *dense_labels, uint8_t *dense_colors, float *dense_confidence, int knn,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* The headless renderer (csrc/pn2_render.hip): a point cloud with per-point colours or labels becomes an image on the device, the
+ * counterpart of the reference's Open3D window (visualize.py, colorize.py).  tests/render_ref.py is the numpy model of the rules
+ * and is compared for equality: every accumulation is an integer minimum or count, so no result depends on the order of arrival.
+ * Every entry point checks its arguments in the order of the tile entry points -- sizes (PN2_EINVAL), ranges (PN2_ERANGE),
+ * unsupported (PN2_EUNSUP), a required pointer NULL (PN2_ENULL), alignment (PN2_EINVAL) -- and refuses before any launch.  No
+ * host synchronisation, no allocation: capturable into a graph.  One launch each.
+ *
+ * pn2_label_colors: util/point_cloud_util.py:_label_to_colors.  labels (n) int32, palette (num_class,3) uint8 in device memory,
+ *   colors (n,3) uint8 = palette[labels].  A label outside [0, num_class) gives 0,0,0 and is counted in *bad (optional int64,
+ *   accumulates, never zeroed here) where the reference raises.  PN2_EUNSUP: num_class > 256.
+ *
+ * pn2_render_splat: points (n,3) float32, or float64 with points_f64 = 1.  view: a HOST pointer to 12 doubles, the row-major 3x4
+ *   matrix M, copied by value into the launch (frozen at capture).  zbuf (height*width) uint64, 8-byte aligned, accumulates across
+ *   calls; "empty" is all bits set (the caller clears it with a 0xFF fill).  For point i = (x, y, z), in float64 without
+ *   contraction:
+ *     t_r  = ((M[r][0]*x + M[r][1]*y) + M[r][2]*z) + M[r][3]
+ *     perspective = 0: u = t_0, v = t_1, d = t_2;  perspective = 1: d = t_2, u = t_0 / d, v = t_1 / d, culled when !(d > 0).
+ *     culled unless u, v and d are finite and -2^30 <= u, v < 2^30 (tested in floating point before any conversion to int).
+ *     px = (int)floor(u), py = (int)floor(v); the point covers the pixels (px - size/2 + a, py - size/2 + b), 0 <= a, b < size
+ *     (integer division), each kept iff it lies inside the image; a point that keeps none counts as culled.  *culled
+ *     (optional int64, accumulates) gets one count per culled point.
+ *     f = (float)d + 0.0f (to nearest; -0 becomes +0); k = the order-preserving uint32 image of f (every bit of a negative f
+ *     flipped, the sign bit of a non-negative f set); key = ((uint64)k << 32) | (uint32)(index0 + i);
+ *     zbuf[py*width + px] = min(zbuf[py*width + px], key), a 64-bit unsigned atomic minimum.
+ *   The nearest depth wins, equal float32 depths go to the lowest global index; the result is the same for any order of points,
+ *   any chunking and any order of calls.  PN2_EINVAL: n, width, height or size <= 0, a flag that is neither 0 nor 1;
+ *   PN2_ERANGE: index0 < 0, index0 + n > 2^31 - 1, width * height >= 2^31; PN2_EUNSUP: size > 16.
+ *
+ * pn2_render_resolve: per pixel p of zbuf: index[p] (optional int32) = the low word of the key, -1 where empty; depth[p] (optional
+ *   float32) = f recovered from k, +inf where empty; image[p] (optional, (height,width,3) uint8) = colors[index] of colors
+ *   (npoints,3) uint8, the 3 HOST bytes background (copied by value) where the pixel is empty or its index >= npoints (never read
+ *   out of bounds).  PN2_ENULL: zbuf NULL, all three outputs NULL, image without background or without colors (npoints > 0). */
+int pn2_label_colors(int n, int num_class, const int *labels, const uint8_t *palette, uint8_t *colors, long long *bad,
+                     void *stream);
+int pn2_render_splat(int n, int index0, const void *points, int points_f64, const double *view, int perspective, int width,
+                     int height, int size, unsigned long long *zbuf, long long *culled, void *stream);
+int pn2_render_resolve(int width, int height, const unsigned long long *zbuf, int npoints, const uint8_t *colors,
+                       const uint8_t *background, uint8_t *image, float *depth, int *index, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

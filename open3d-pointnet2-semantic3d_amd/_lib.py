@@ -96,7 +96,8 @@ _STATEFUL = frozenset({"pn2_bn_relu_forward", "pn2_linear_bn_stats",
                        "pn2_linear_bn_stats_fin", "pn2_bn_relu_forward_mode", "pn2_sa_first_layer_bn", "pn2_sa_hoist_rows_bn", "pn2_fp_hoist_rows_bn", "pn2_sa_hoist_rows_multi_bn", "pn2_linear_bwd_fused", "pn2_linear_dgrad_bn_grad_stats",
                        "pn2_adam_step", "pn2_momentum_step", "pn2_linear_wgrad_accumulate",
                        "pn2_augment", "pn2_frame_sample",  # (advance the caller's counter: a second launch draws other numbers)
-                       "pn2_tile_vote", "pn2_tile_vote_scores"})  # (add into the caller's votes / scores)
+                       "pn2_tile_vote", "pn2_tile_vote_scores",  # (add into the caller's votes / scores)
+                       "pn2_render_splat"})  # (takes the minimum into the caller's z-buffer, counts into its culled)
 
 
 class _LibProxy:
