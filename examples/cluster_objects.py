@@ -1,0 +1,95 @@
+"""Group the labelled points of a scene into objects on one MI355X: which points form one car, and how many cars there are.
+
+    python examples/cluster_objects.py --points scene.pcd --labels scene.labels --eps 0.5 --classes 8 --min_points 10 --out result
+    python examples/cluster_objects.py --synthetic 3000 --eps 0.2 --out result
+
+The cloud and the labels are read on the device (pn2.read_point_cloud, pn2.load_labels), the points of each class in --classes
+(every label >= 1 that occurs when it is not given) are clustered with pn2.euclidean_clusters -- two points in one object when a
+chain of points of their label joins them in steps of at most --eps -- and the result is written to
+    <out>/objects.txt   one line per object: id label size min_x min_y min_z max_x max_y max_z (repr-exact floats)
+    <out>/objects.png   the scene from above, every object in a colour of its own, everything else grey (pn2.render)
+with one line per class and its object count on the terminal.  --synthetic N makes N points in tight blobs of known sizes on a
+lattice (synthetic(N) below), so the expected output is known.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import pn2_amd as pn2  # noqa: E402
+
+SYNTHETIC_EPS = 0.2
+
+
+def synthetic(n, seed=0):
+    """-> points (n,3) float32, labels (n,) int32: blobs of 1 + (37 k mod 60) points, each inside a cube of side 0.1 (any two of
+    its points are closer than SYNTHETIC_EPS) at the lattice site (k mod 16, k div 16, 0) (two blobs are at least 0.9 apart);
+    blob k has label 1 + k mod 3; the rows are shuffled."""
+    rs = np.random.RandomState(seed)
+    blob, k = [], 0
+    while len(blob) < n:
+        blob += [k] * min(1 + (37 * k) % 60, n - len(blob))
+        k += 1
+    blob = np.array(blob)
+    site = np.stack([blob % 16, blob // 16, np.zeros_like(blob)], 1).astype(np.float64)
+    points = (site + rs.uniform(-0.05, 0.05, (n, 3))).astype(np.float32)
+    labels = (1 + blob % 3).astype(np.int32)
+    order = rs.permutation(n)
+    return points[order], labels[order]
+
+
+def object_lines(clusters):
+    """-> the lines of objects.txt"""
+    rows = zip(clusters.label.tolist(), clusters.size.tolist(), clusters.bbox.cpu().numpy())
+    return ["%d %d %d %s" % (i, label, size, " ".join(repr(float(v)) for v in box)) for i, (label, size, box) in enumerate(rows)]
+
+
+def main():
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--points", default="", help="scene.pcd or scene.ply")
+    parser.add_argument("--labels", default="", help="scene.labels: one label per point")
+    parser.add_argument("--synthetic", type=int, default=0, help="N points in blobs on a lattice instead of a scene")
+    parser.add_argument("--eps", type=float, default=0.0, help="the largest step between two points of one object")
+    parser.add_argument("--classes", type=int, nargs="*", default=None, help="the labels to cluster (default: every label >= 1)")
+    parser.add_argument("--min_points", type=int, default=1)
+    parser.add_argument("--max_points", type=int, default=0, help="0: no upper bound")
+    parser.add_argument("--out", default="result/objects")
+    parser.add_argument("--width", type=int, default=1280)
+    parser.add_argument("--height", type=int, default=960)
+    flags = parser.parse_args()
+    if flags.synthetic > 0:
+        points, labels = (torch.from_numpy(a).cuda() for a in synthetic(flags.synthetic))
+        eps = flags.eps or SYNTHETIC_EPS
+    elif flags.points and flags.labels:
+        points, _ = pn2.read_point_cloud(flags.points, want_colors=False)
+        labels = pn2.load_labels(flags.labels)
+        if len(points) != len(labels):
+            raise ValueError("len(points) != len(labels)")
+        eps = flags.eps
+    else:
+        parser.error("--points and --labels, or --synthetic N")
+    if not eps > 0:
+        parser.error("--eps")
+    classes = flags.classes if flags.classes else [c for c in torch.unique(labels).tolist() if c >= 1]
+
+    clusters = pn2.euclidean_clusters(points, eps, labels=labels, classes=classes, min_points=flags.min_points,
+                                      max_points=flags.max_points)
+    per_class = torch.bincount(clusters.label, minlength=max(classes) + 1).tolist() if clusters.count else []
+    for c in classes:
+        print("class %d: %d objects" % (c, per_class[c] if c < len(per_class) else 0))
+    print("%d objects, %d of %d points in one" % (clusters.count, int((clusters.ids >= 0).sum()), len(points)))
+
+    os.makedirs(flags.out, exist_ok=True)
+    with open(os.path.join(flags.out, "objects.txt"), "w") as f:
+        f.writelines(line + "\n" for line in object_lines(clusters))
+    image = pn2.render.render_colors(points, pn2.cluster_colors(clusters.ids), "top", flags.width, flags.height, size=2)
+    pn2.render.write_png(os.path.join(flags.out, "objects.png"), image)
+    print("Output written to", flags.out)
+
+
+if __name__ == "__main__":
+    main()

@@ -1241,6 +1241,49 @@ int pn2_render_splat(int n, int index0, const void *points, int points_f64, cons
 int pn2_render_resolve(int width, int height, const unsigned long long *zbuf, int npoints, const uint8_t *colors,
                        const uint8_t *background, uint8_t *image, float *depth, int *index, void *stream);
 
+/* Euclidean clustering (csrc/pn2_cluster.hip): the points of a cloud, optionally of one label each, grouped into objects.
+ * tests/cluster_ref.py is the numpy model of the rules and is compared for equality: nothing in a result depends on the order in
+ * which threads arrive.
+ *
+ *   points (n,3) float32; labels (n) int32 or NULL (one class); eps finite and > 0; min_points >= 1; max_points >= 0 (0: no upper
+ *   bound).
+ *   A point is VALID when its three coordinates are finite and, with labels, its label is >= 0.
+ *   Two valid points i != j are LINKED when their labels are equal (with labels) and, in float64 without contraction,
+ *     (dx*dx + dy*dy) + dz*dz <= (double)eps * (double)eps,   dx = (double)x_i - (double)x_j, dy and dz likewise.
+ *   A COMPONENT is a connected component of that graph; its first = its lowest point index, its size = its point count.  It is
+ *   KEPT when min_points <= size and (max_points == 0 or size <= max_points).  The kept components are numbered 0 .. C-1 by
+ *   ascending first.  ids[i] = the number of the component of i; -1 for an invalid point and for a point of a component that is
+ *   not kept.
+ *
+ * pn2_cluster_points: ids (n) int32 and header (8) int32 on the device: [0] status, [1] C, [2] components before the size filter,
+ *   [3] valid points, [4] points in kept clusters, [5..7] zero.  Status 0 = ok; 1 = more than 2^21 cells of edge eps on an axis
+ *   of the valid points' box (the convention of pn2_voxel_downsample): then every id is -1 and header[1..7] are zero.
+ *   workspace: *bytes of pn2_cluster_workspace_size(n, bytes) (a host query like pn2_tile_plan_workspace_size: PN2_EINVAL for
+ *   n <= 0, PN2_ENULL without bytes), 256-byte aligned.  It queues a sorted-key grid build (its
+ *   launches and a radix sort), a lock-free union-find over the 27 cells around every point, and an ordered numbering; no
+ *   allocation, no synchronisation.  It is eager by nature -- the caller reads C from the header before it can size what follows
+ *   -- and refuses a capturing stream: PN2_EUNSUP, before anything is launched.  Checked before that, in this order, nothing
+ *   launched: PN2_EINVAL (n <= 0, eps not finite or <= 0, min_points < 1, max_points < 0), PN2_ENULL (points, ids, header or
+ *   workspace NULL), PN2_EINVAL (a misaligned pointer, a workspace that is too small).
+ *
+ * pn2_cluster_stats: per cluster c of ids (as written by pn2_cluster_points; nclusters = C >= 1): first[c] = its lowest point
+ *   index, size[c] = its point count, label[c] = labels[first[c]] (0 without labels), bbox (nclusters,6) float32 = min x, y, z
+ *   then max x, y, z: exact minima and maxima of the members' float32 coordinates (-0.0 below +0.0).  Integer atomics only.  An id
+ *   outside [0, nclusters) is ignored; a cluster without points keeps first = 2^31 - 1, size 0, label 0 and a box of NaNs.
+ *   Three launches.  PN2_EINVAL: n or nclusters <= 0, a misaligned pointer; PN2_ERANGE: nclusters > n; PN2_ENULL: any pointer but
+ *   labels NULL.
+ *
+ * pn2_cluster_colors: rgb (n,3) uint8, one colour of full saturation per id: in uint32 arithmetic
+ *     h = id * 0x9E3779B1;  h ^= h >> 15;  h *= 0x85EBCA77;  h ^= h >> 13;  hue = h % 1536;  s = hue >> 8;  f = hue & 255;
+ *     (r,g,b) = (255,f,0), (255-f,255,0), (0,255,f), (0,255-f,255), (f,0,255), (255,0,255-f)  for s = 0 .. 5.
+ *   A negative id gives (96,96,96).  One launch. */
+int pn2_cluster_workspace_size(int n, unsigned long long *bytes);
+int pn2_cluster_points(int n, const float *points, const int *labels, float eps, int min_points, int max_points, int *ids,
+                       int *header, void *workspace, size_t workspace_bytes, void *stream);
+int pn2_cluster_stats(int n, int nclusters, const float *points, const int *labels, const int *ids, int *first, int *size,
+                      int *label, float *bbox, void *stream);
+int pn2_cluster_colors(int n, const int *ids, uint8_t *rgb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

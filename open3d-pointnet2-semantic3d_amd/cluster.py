@@ -1,0 +1,121 @@
+"""Labelled points into objects: Euclidean clustering on the device, where a user of the reference would copy the cloud to the
+host and run a KD-tree and a graph library over it.  The kernels are csrc/pn2_cluster.hip; the rules are in include/pn2_abi.h
+(pn2_cluster_points) and tests/cluster_ref.py is their numpy model.
+
+    c = euclidean_clusters(points, eps=0.5, labels=dense_labels, classes=[8], min_points=10)   # which points form one car
+    c.count, c.ids, c.first, c.size, c.label, c.bbox                                           # how many cars, and where
+    img = render.render_colors(points, cluster_colors(c.ids), "top")                           # coloured by instance
+
+Two points belong to one cluster when a chain of points of their label leads from one to the other in steps of at most eps.
+The number of clusters is data-dependent and is read by the host once (the header): the call is eager and refuses a capturing
+stream.  Nothing in a result depends on the order in which threads arrive.
+"""
+import collections
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from ._lib import launch, ptr, require_cuda
+from .predict import _on_device
+
+# the status word of pn2_cluster_points (include/pn2_abi.h), the convention of downsample.STATUS_NAMES
+STATUS_NAMES = {1: "more than 2^21 cells of edge eps on an axis"}
+
+Clusters = collections.namedtuple("Clusters", "ids count first size label bbox")
+Clusters.__doc__ = """ids (n,) int32: the cluster of every point, -1 for none; count: the number of clusters (a host int, may be 0);
+first, size, label (count,) int32: the lowest point index, the point count and the label (0 without labels) of each cluster, in
+ascending order of first; bbox (count,6) float32: min x, y, z then max x, y, z.  Device tensors except count."""
+
+
+def _device_of(points, labels):
+    for a in (points, labels):
+        if torch.is_tensor(a):
+            require_cuda(a)
+            return a.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def euclidean_clusters(points, eps, labels=None, classes=None, min_points=1, max_points=None):
+    """points (n,3), labels (n,) integers or None: device tensors or numpy arrays (cast to float32 / int32).  classes: an iterable
+    of the labels to cluster -- every other label counts as -1, "no object"; None clusters every label >= 0.  min_points,
+    max_points: the sizes of the clusters kept (max_points None or 0: no upper bound).  -> Clusters.
+    RuntimeError on a capturing stream; ValueError for a bad argument (before the library is touched) and for a cloud that spans
+    more than 2^21 cells of edge eps on an axis (STATUS_NAMES; one host read, of the header)."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("euclidean_clusters is eager (the number of clusters is read by the host): not on a capturing stream")
+    try:
+        with np.errstate(over="ignore"):  # too large for float32 is inf, refused below
+            eps = float(np.float32(eps))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("eps: a number")
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ValueError("eps: finite and greater than 0 as float32")
+    min_points, max_points = int(min_points), int(max_points or 0)
+    if min_points < 1:
+        raise ValueError("min_points: at least 1")
+    if max_points < 0:
+        raise ValueError("max_points: at least 0 (0 or None: no upper bound)")
+    if max_points and max_points < min_points:
+        raise ValueError("max_points below min_points")
+    shape = tuple(points.shape)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError("points: (n,3)")
+    n = shape[0]
+    if labels is not None:
+        if tuple(labels.shape) != (n,):
+            raise ValueError("labels: (n,) for points (n,3)")
+        kind = labels.dtype
+        if (kind.is_floating_point or kind == torch.bool) if torch.is_tensor(labels) else kind.kind not in "iu":
+            raise ValueError("labels: integers")
+    if classes is not None:
+        if labels is None:
+            raise ValueError("classes without labels")
+        classes = sorted({int(c) for c in classes})
+        if any(c < 0 for c in classes):
+            raise ValueError("classes: labels >= 0")
+    if n >= 2 ** 31:
+        raise ValueError("fewer than 2^31 points")
+    dev = _device_of(points, labels)
+    points = _on_device(points, torch.float32, dev)
+    if labels is not None:
+        labels = _on_device(labels, torch.int32, dev)
+        if classes is not None:
+            labels = torch.where(torch.isin(labels, torch.tensor(classes, dtype=torch.int32, device=dev)), labels,
+                                 torch.full_like(labels, -1))
+    ids = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    empty = Clusters(ids, 0, *(torch.empty((0,), dtype=torch.int32, device=dev) for _ in range(3)),
+                     torch.empty((0, 6), dtype=torch.float32, device=dev))
+    if n == 0:
+        return empty  # nothing is launched: the entry point refuses n == 0
+    header = torch.zeros((8,), dtype=torch.int32, device=dev)
+    nbytes = ctypes.c_ulonglong(0)
+    launch("pn2_cluster_workspace_size", dev, n, ctypes.byref(nbytes), stream=False)
+    ws = torch.empty((int(nbytes.value) + 255,), dtype=torch.uint8, device=dev)
+    off = (-ws.data_ptr()) % 256
+    launch("pn2_cluster_points", dev, n, ptr(points), ptr(labels), eps, min_points, max_points, ptr(ids), ptr(header),
+           ws.data_ptr() + off, ws.numel() - off)
+    status, count = header[:2].tolist()  # the one host read
+    if status:
+        raise ValueError("pn2_cluster_points: %s" % STATUS_NAMES[status])
+    if count == 0:
+        return empty
+    first, size, label = (torch.empty((count,), dtype=torch.int32, device=dev) for _ in range(3))
+    bbox = torch.empty((count, 6), dtype=torch.float32, device=dev)
+    launch("pn2_cluster_stats", dev, n, count, ptr(points), ptr(labels), ptr(ids), ptr(first), ptr(size), ptr(label), ptr(bbox))
+    return Clusters(ids, count, first, size, label, bbox)
+
+
+def cluster_colors(ids):
+    """ids (n,) int32 on the device -> (n,3) uint8: one fixed colour of full saturation per id (the hash is in
+    include/pn2_abi.h, pn2_cluster_colors), (96,96,96) for -1.  For render.Renderer.image and render.render_colors."""
+    require_cuda(ids)
+    if ids.dim() != 1 or ids.dtype.is_floating_point or ids.dtype == torch.bool:
+        raise ValueError("ids: (n,) integers")
+    ids = ids.to(torch.int32).contiguous()
+    n = int(ids.shape[0])
+    rgb = torch.empty((n, 3), dtype=torch.uint8, device=ids.device)
+    if n:
+        launch("pn2_cluster_colors", ids.device, n, ptr(ids), ptr(rgb))
+    return rgb

@@ -1,0 +1,528 @@
+// pn2_cluster.hip -- Euclidean clustering: the points of a (labelled) cloud grouped into connected components of the graph that
+// links two valid points of one label no more than eps apart.  The rules are in include/pn2_abi.h (pn2_cluster_points);
+// tests/cluster_ref.py is their numpy model, and everything here is compared with it for equality.
+//
+// pn2_cluster_points queues, on the caller's stream (eager only: the host half of the caller reads the header afterwards):
+//   1 cluster_init_kernel    : the scalars (ordered minima, counters, status).
+//   2 cluster_min_kernel     : the minimum x, y, z of the valid points as ordered uint32 (a float32 minimum is exact), one atomicMin
+//                              per axis per wave; the count of valid points.
+//   3 cluster_key_kernel     : the cell of every valid point and its 63-bit key, x lowest; an invalid point gets the key ~0, which
+//                              sorts last and is never visited.  A cell coordinate >= 2^21 raises the status.
+//   4 hipcub radix sort      : (key, point index) pairs.
+//   5 cluster_gather_kernel  : the sorted points as (x, y, z, label) rows; parent[i] = i, csize[i] = 0.
+//   6 cluster_union_kernel   : one sorted point per lane.  It visits the points IN FRONT of it in the sorted order that lie in the
+//                              27 cells around its own -- five key ranges, because x is the lowest key field: the three rows
+//                              (y-1, y, y+1) of the layer z-1, the row y-1 of its own layer, and its own row up to itself -- and
+//                              unites itself with every one that is linked.  So each linked pair is tested once.
+//   7 cluster_flatten_kernel : root[i] = the root of i (-1 for an invalid point), csize[root] += 1.
+//   8 cluster_flag_kernel    : per scan block of 256 points the number of kept roots; components and kept points counted.
+//   9 cluster_offsets_kernel : one workgroup: the exclusive prefix of the block counts, and the header.
+//  10 cluster_number_kernel  : number[i] of a kept root = block offset + its place in the block (pn2_wg.h's scan), -1 otherwise.
+//  11 cluster_ids_kernel     : ids[i] = number[root[i]], -1 without a root.
+//
+// THE GRID.  h = eps * (1 + 2^-20) in float64, cell = floor(((double)x - (double)min_x) / h) per axis.  Why two points that pass
+// the link test are never two cells apart on an axis: the test (dx*dx + dy*dy) + dz*dz <= eps*eps in float64 bounds |dx| by
+// eps * (1 + 2^-51) (three roundings of 2^-53 each on the left, one on the right).  With a = x - min_x exact, the computed
+// quotient q carries two roundings (the subtraction, the division): |q - a/h| <= 2.01 * 2^-53 * a/h, and a/h < 2^21 for every
+// point that is not refused with status 1, so the error of a quotient is below 2^-31.  Then
+//     q_i - q_j <= (a_i - a_j)/h + 2^-30 <= (1 + 2^-51) / (1 + 2^-20) + 2^-30 < 1 - 2^-21 < 1,
+// and two numbers less than 1 apart have floors at most 1 apart.  (The hair is 2^-20, nine orders of magnitude above what the
+// roundings need, and costs a 27-cell volume one part in 350 000.)
+//
+// THE UNION-FIND.  parent[] over point indices; parent[i] <= i always, and a link always points from the higher root to the lower:
+// a root is the lowest index of its tree, hence at the end the component's `first`.
+//   * find walks down (parent[x] < x unless x is a root: strictly decreasing, bounded by its start) and halves the path with an
+//     atomicMin on nodes that are no roots.  A node that has stopped being a root never becomes one again, so such a write can only
+//     replace an ancestor by an ancestor.
+//   * unite(a, b): find both; equal -> done; otherwise compare-and-swap parent[hi] from hi to lo.  The swap succeeds only while hi
+//     is still its own parent, so no link is ever overwritten.  When it fails it returns the parent hi got meanwhile, old < hi, and
+//     the pair (old, lo) carries the same obligation: it is united next.  max(a, b) falls strictly from one round to the next:
+//     that is the loop's bound.
+//   * parent[] is read with relaxed agent-scope atomic loads.  A stale value is an ancestor of an earlier time: it lengthens a walk
+//     or fails a swap, and no loop's exit rests on it -- find ends on its own decreasing index, unite on the swap's answer.
+// No kernel waits for another workgroup.
+#include <hipcub/hipcub.hpp>
+
+#include "pn2_common.h"
+#include "pn2_wg.h"  // wg_excl_scan_flag, wg_sum, al256, WsCarver
+
+namespace {
+
+constexpr int kT = 256;            // threads of every workgroup here; also the scan block (points per block count)
+constexpr int kW = kT / 64;
+constexpr int kCellBits = 21;
+constexpr int kCellLimit = 1 << kCellBits;
+constexpr unsigned long long kInvalidKey = ~0ull;
+
+// the scalars of one call, at the head of the workspace
+struct Scal {
+    unsigned min_key[3];  // ordered uint32 of the minimum x, y, z over the valid points
+    int status;
+    int nvalid;
+    int ncomp;            // components before the size filter
+    int nkeptpts;         // points in kept clusters
+};
+
+struct Layout {
+    size_t scal, keys_in, keys_out, vals_in, vals_out, spts, parent, csize, root, number, bcount, cub, cub_bytes, total;
+};
+
+inline int scan_blocks(int n) { return (int)(((long long)n + kT - 1) / kT); }
+
+// the offset of the next piece of `count` elements of T
+template <typename T>
+inline size_t piece(WsCarver& c, size_t count) {
+    const size_t o = c.used;
+    c.take<T>(count);
+    return o;
+}
+
+// everything but the sort's share: known without asking the sort
+inline size_t fixed_layout(int n, Layout* L) {
+    WsCarver c{nullptr};
+    const size_t N = (size_t)n;
+    L->scal = piece<Scal>(c, 1);
+    L->keys_in = piece<unsigned long long>(c, N);
+    L->keys_out = piece<unsigned long long>(c, N);
+    L->vals_in = piece<int>(c, N);
+    L->vals_out = piece<int>(c, N);
+    L->spts = piece<float4>(c, N);
+    L->parent = piece<int>(c, N);
+    L->csize = piece<int>(c, N);
+    L->root = piece<int>(c, N);
+    L->number = piece<int>(c, N);
+    L->bcount = piece<int>(c, (size_t)scan_blocks(n));
+    return c.used;
+}
+
+inline hipError_t layout(int n, Layout* L) {
+    const size_t fixed = fixed_layout(n, L);
+    size_t cub = 0;
+    const hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, cub, (const unsigned long long*)nullptr,
+                                                            (unsigned long long*)nullptr, (const int*)nullptr, (int*)nullptr, n, 0, 64);
+    L->cub_bytes = cub;
+    L->cub = fixed;
+    L->total = fixed + al256(cub);
+    return e;
+}
+
+// the order-preserving uint32 image of a float (li_ord / li_unord of the dense-label grid, depth_key of the renderer)
+__device__ __forceinline__ unsigned ord32(float f) {
+    const unsigned b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float unord32(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+__device__ __forceinline__ bool finite32(float f) { return (__float_as_uint(f) & 0x7F800000u) != 0x7F800000u; }
+
+__device__ __forceinline__ bool point_valid(const float* __restrict__ points, const int* __restrict__ labels, long long i) {
+    const float* p = points + (size_t)i * 3;
+    return finite32(p[0]) && finite32(p[1]) && finite32(p[2]) && (!labels || labels[i] >= 0);
+}
+
+__device__ __forceinline__ unsigned wave_umin(unsigned v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned t = (unsigned)__shfl_xor((int)v, o);
+        v = t < v ? t : v;
+    }
+    return v;
+}
+
+__global__ void cluster_init_kernel(Scal* __restrict__ s) {
+    if (threadIdx.x == 0) {
+        s->min_key[0] = s->min_key[1] = s->min_key[2] = 0xFFFFFFFFu;
+        s->status = s->nvalid = s->ncomp = s->nkeptpts = 0;
+    }
+}
+
+__global__ void __launch_bounds__(kT)
+cluster_min_kernel(int n, const float* __restrict__ points, const int* __restrict__ labels, Scal* __restrict__ s) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    const bool ok = i < n && point_valid(points, labels, i);
+    unsigned k0 = 0xFFFFFFFFu, k1 = 0xFFFFFFFFu, k2 = 0xFFFFFFFFu;
+    if (ok) {
+        const float* p = points + (size_t)i * 3;
+        k0 = ord32(p[0]);
+        k1 = ord32(p[1]);
+        k2 = ord32(p[2]);
+    }
+    const unsigned long long bal = __ballot(ok);
+    k0 = wave_umin(k0);
+    k1 = wave_umin(k1);
+    k2 = wave_umin(k2);
+    if (bal != 0ull && (threadIdx.x & 63) == 0) {
+        atomicMin(&s->min_key[0], k0);
+        atomicMin(&s->min_key[1], k1);
+        atomicMin(&s->min_key[2], k2);
+        atomicAdd(&s->nvalid, __popcll(bal));
+    }
+}
+
+__global__ void __launch_bounds__(kT)
+cluster_key_kernel(int n, const float* __restrict__ points, const int* __restrict__ labels, double h, Scal* __restrict__ s,
+                   unsigned long long* __restrict__ keys, int* __restrict__ vals) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    if (i >= n) return;
+    unsigned long long key = kInvalidKey;
+    if (point_valid(points, labels, i)) {
+        const float* p = points + (size_t)i * 3;
+        key = 0ull;
+        bool far = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            // >= 0: the minimum is the least of them and the subtraction is monotone
+            const double q = __builtin_floor(((double)p[a] - (double)unord32(s->min_key[a])) / h);
+            const bool in = q < (double)kCellLimit;  // tested in floating point before the conversion
+            far = far || !in;
+            key |= (unsigned long long)(in ? (long long)q : (long long)(kCellLimit - 1)) << (kCellBits * a);
+        }
+        if (far) atomicMax(&s->status, 1);
+    }
+    keys[i] = key;
+    vals[i] = (int)i;
+}
+
+__global__ void __launch_bounds__(kT)
+cluster_gather_kernel(int n, const float* __restrict__ points, const int* __restrict__ labels, const int* __restrict__ order,
+                      float4* __restrict__ spts, int* __restrict__ parent, int* __restrict__ csize) {
+    const long long t = (long long)blockIdx.x * kT + threadIdx.x;
+    if (t >= n) return;
+    parent[t] = (int)t;
+    csize[t] = 0;
+    const int i = order[t];
+    const float* p = points + (size_t)i * 3;
+    spts[t] = make_float4(p[0], p[1], p[2], __int_as_float(labels ? labels[i] : 0));
+}
+
+__device__ __forceinline__ int load_parent(const int* parent, int x) {
+    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// x strictly decreases: parent[x] < x unless x is a root
+__device__ __forceinline__ int uf_find(int* parent, int x) {
+    for (;;) {
+        const int p = load_parent(parent, x);
+        if (p >= x) return x;  // p == x: a root (p > x cannot be; it would end the walk all the same)
+        const int g = load_parent(parent, p);
+        if (g < p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // x is no root: halve
+        x = p;
+    }
+}
+
+// max(a, b) strictly decreases from round to round
+__device__ __forceinline__ void uf_unite(int* parent, int a, int b) {
+    for (;;) {
+        a = uf_find(parent, a);
+        b = uf_find(parent, b);
+        if (a == b) return;
+        const int hi = a > b ? a : b, lo = a > b ? b : a;
+        int seen = hi;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            return;
+        if (seen >= hi) return;  // cannot be (a failed swap saw parent[hi] != hi, and parent[hi] <= hi): the bound, stated
+        a = seen;  // hi was hooked by somebody else meanwhile: its new parent is united with lo instead
+        b = lo;
+    }
+}
+
+// first t in [0, hi) with keys[t] >= k
+__device__ __forceinline__ int lower_bound_key(const unsigned long long* __restrict__ keys, int hi, unsigned long long k) {
+    int lo = 0;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < k) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(kT)
+cluster_union_kernel(int n, const unsigned long long* __restrict__ keys, const int* __restrict__ order,
+                     const float4* __restrict__ spts, double eps2, const Scal* __restrict__ s, int* parent) {
+    const long long s0 = (long long)blockIdx.x * kT + threadIdx.x;
+    if (s0 >= n || s->status != 0) return;
+    const int me = (int)s0;
+    const unsigned long long key = keys[me];
+    if (key == kInvalidKey) return;
+    const int cx = (int)(key & (kCellLimit - 1)), cy = (int)((key >> kCellBits) & (kCellLimit - 1)),
+              cz = (int)((key >> (2 * kCellBits)) & (kCellLimit - 1));
+    const int x0 = cx > 0 ? cx - 1 : 0, x1 = cx < kCellLimit - 1 ? cx + 1 : cx;
+    const float4 p = spts[me];
+    const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
+    const int label = __float_as_int(p.w);
+    const int i = order[me];
+    // the rows in front of this point: (z-1; y-1, y, y+1), (z; y-1), (z; y) up to the point itself
+    for (int r = 0; r < 5; ++r) {
+        const int z = r < 3 ? cz - 1 : cz;
+        const int y = r < 3 ? cy - 1 + r : (r == 3 ? cy - 1 : cy);
+        if (z < 0 || y < 0 || y >= kCellLimit) continue;
+        const unsigned long long row = ((unsigned long long)z << (2 * kCellBits)) | ((unsigned long long)y << kCellBits);
+        const unsigned long long klo = row | (unsigned long long)x0, khi = row | (unsigned long long)x1;
+        // t rises to `me` at the most: only sorted positions in front of this one are visited
+        for (int t = lower_bound_key(keys, me, klo); t < me && keys[t] <= khi; ++t) {
+            const float4 q = spts[t];
+            if (__float_as_int(q.w) != label) continue;
+            const double dx = px - (double)q.x, dy = py - (double)q.y, dz = pz - (double)q.z;
+            if ((dx * dx + dy * dy) + dz * dz <= eps2) uf_unite(parent, i, order[t]);
+        }
+    }
+}
+
+// one atomic per distinct value among the lanes of a wave that hold one (`has`); at most 64 rounds, each retires a lane
+__device__ __forceinline__ void wave_count_into(int* __restrict__ counts, bool has, int slot) {
+    unsigned long long todo = __ballot(has);
+    const int lane = threadIdx.x & 63;
+    while (todo != 0ull) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int v = __shfl(slot, leader);
+        const unsigned long long same = __ballot(has && slot == v) & todo;
+        if (lane == leader) atomicAdd(counts + v, __popcll(same));
+        todo &= ~same;
+    }
+}
+
+__global__ void __launch_bounds__(kT)
+cluster_flatten_kernel(int n, const float* __restrict__ points, const int* __restrict__ labels, const int* __restrict__ parent,
+                       const Scal* __restrict__ s, int* __restrict__ root, int* __restrict__ csize) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    const bool ok = i < n && s->status == 0 && point_valid(points, labels, i);
+    int r = -1;
+    if (ok) {
+        r = (int)i;
+        for (int p = parent[r]; p < r; p = parent[r]) r = p;  // the union kernel is over: plain loads; r strictly decreases
+    }
+    if (i < n) root[i] = r;
+    wave_count_into(csize, ok, r);
+}
+
+__device__ __forceinline__ bool size_kept(int size, int min_points, int max_points) {
+    return size >= min_points && (max_points == 0 || size <= max_points);
+}
+
+__global__ void __launch_bounds__(kT)
+cluster_flag_kernel(int n, const int* __restrict__ root, const int* __restrict__ csize, int min_points, int max_points,
+                    Scal* __restrict__ s, int* __restrict__ bcount) {
+    __shared__ int red[kW];
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    const bool is_root = i < n && root[i] == (int)i;
+    const int size = is_root ? csize[i] : 0;
+    const bool kept = is_root && size_kept(size, min_points, max_points);
+    const int ncomp = wg_sum<kW>(is_root ? 1 : 0, red);
+    const int nkept = wg_sum<kW>(kept ? 1 : 0, red);
+    const int npts = wg_sum<kW>(kept ? size : 0, red);  // sizes sum to <= n: no overflow
+    if (threadIdx.x == 0) {
+        bcount[blockIdx.x] = nkept;
+        if (ncomp) atomicAdd(&s->ncomp, ncomp);
+        if (npts) atomicAdd(&s->nkeptpts, npts);
+    }
+}
+
+// one workgroup: bcount -> its exclusive prefix, in chunks of kT with a running carry; then the header
+__global__ void __launch_bounds__(kT)
+cluster_offsets_kernel(int nblocks, int* __restrict__ bcount, const Scal* __restrict__ s, int* __restrict__ header) {
+    __shared__ int wsum[kW];
+    int carry = 0;
+    for (int base = 0; base < nblocks; base += kT) {
+        const int b = base + (int)threadIdx.x;
+        const int v = b < nblocks ? bcount[b] : 0;
+        int total;
+        const int before = wg_excl_scan_int<kW>(v, wsum, total);
+        if (b < nblocks) bcount[b] = carry + before;
+        carry += total;
+    }
+    if (threadIdx.x == 0) {
+        const bool ok = s->status == 0;
+        header[0] = s->status;
+        header[1] = ok ? carry : 0;
+        header[2] = ok ? s->ncomp : 0;
+        header[3] = ok ? s->nvalid : 0;
+        header[4] = ok ? s->nkeptpts : 0;
+        header[5] = header[6] = header[7] = 0;
+    }
+}
+
+__global__ void __launch_bounds__(kT)
+cluster_number_kernel(int n, const int* __restrict__ root, const int* __restrict__ csize, int min_points, int max_points,
+                      const int* __restrict__ boffset, int* __restrict__ number) {
+    __shared__ int wsum[kW];
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    const bool kept = i < n && root[i] == (int)i && size_kept(csize[i], min_points, max_points);
+    int total;
+    const int before = wg_excl_scan_flag<kW>(kept ? 1 : 0, wsum, total);
+    if (i < n) number[i] = kept ? boffset[blockIdx.x] + before : -1;
+}
+
+__global__ void __launch_bounds__(kT)
+cluster_ids_kernel(int n, const int* __restrict__ root, const int* __restrict__ number, int* __restrict__ ids) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    if (i >= n) return;
+    const int r = root[i];
+    ids[i] = r >= 0 ? number[r] : -1;
+}
+
+// ---- statistics ---------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kT)
+stats_init_kernel(int nclusters, int* __restrict__ first, int* __restrict__ size, unsigned* __restrict__ box) {
+    const int c = blockIdx.x * kT + threadIdx.x;
+    if (c >= nclusters) return;
+    first[c] = 0x7FFFFFFF;
+    size[c] = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        box[(size_t)c * 6 + a] = 0xFFFFFFFFu;
+        box[(size_t)c * 6 + 3 + a] = 0u;
+    }
+}
+
+__global__ void __launch_bounds__(kT)
+stats_points_kernel(int n, int nclusters, const float* __restrict__ points, const int* __restrict__ ids, int* __restrict__ first,
+                    int* __restrict__ size, unsigned* __restrict__ box) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    const int c = i < n ? ids[i] : -1;
+    const bool in = c >= 0 && c < nclusters;  // an id outside the tables is never written
+    wave_count_into(size, in, c);
+    if (!in) return;
+    // minima only fall and maxima only rise: a stale read costs an atomic, never a result
+    if ((int)i < __hip_atomic_load(first + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT)) atomicMin(first + c, (int)i);
+    unsigned* b = box + (size_t)c * 6;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const unsigned k = ord32(points[(size_t)i * 3 + a]);
+        if (k < __hip_atomic_load(b + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT)) atomicMin(b + a, k);
+        if (k > __hip_atomic_load(b + 3 + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT)) atomicMax(b + 3 + a, k);
+    }
+}
+
+__global__ void __launch_bounds__(kT)
+stats_finish_kernel(int n, int nclusters, const int* __restrict__ labels, const int* __restrict__ first, int* __restrict__ label,
+                    unsigned* __restrict__ box) {
+    const int c = blockIdx.x * kT + threadIdx.x;
+    if (c >= nclusters) return;
+    const int f = first[c];
+    label[c] = labels && f >= 0 && f < n ? labels[f] : 0;  // an empty cluster (an id the caller never used) keeps first = INT_MAX
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        unsigned* w = box + (size_t)c * 6 + a;
+        *w = __float_as_uint(unord32(*w));
+    }
+}
+
+// h = id * 0x9E3779B1; h ^= h >> 15; h *= 0x85EBCA77; h ^= h >> 13 (uint32); hue = h % 1536: six sectors of 256 steps
+__global__ void __launch_bounds__(kT)
+cluster_colors_kernel(int n, const int* __restrict__ ids, unsigned char* __restrict__ rgb) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    if (i >= n) return;
+    const int id = ids[i];
+    unsigned r = 96u, g = 96u, b = 96u;
+    if (id >= 0) {
+        unsigned h = (unsigned)id * 0x9E3779B1u;
+        h ^= h >> 15;
+        h *= 0x85EBCA77u;
+        h ^= h >> 13;
+        const unsigned hue = h % 1536u, f = hue & 255u;
+        switch (hue >> 8) {
+            case 0: r = 255u; g = f; b = 0u; break;
+            case 1: r = 255u - f; g = 255u; b = 0u; break;
+            case 2: r = 0u; g = 255u; b = f; break;
+            case 3: r = 0u; g = 255u - f; b = 255u; break;
+            case 4: r = f; g = 0u; b = 255u; break;
+            default: r = 255u; g = 0u; b = 255u - f; break;
+        }
+    }
+    unsigned char* out = rgb + (size_t)i * 3;
+    out[0] = (unsigned char)r;
+    out[1] = (unsigned char)g;
+    out[2] = (unsigned char)b;
+}
+
+}  // namespace
+
+extern "C" int pn2_cluster_workspace_size(int n, unsigned long long* bytes) {
+    if (n <= 0) return PN2_EINVAL;
+    if (!bytes) return PN2_ENULL;
+    Layout L;
+    const hipError_t e = layout(n, &L);
+    if (e != hipSuccess) return (int)e;
+    *bytes = (unsigned long long)L.total;
+    return PN2_OK;
+}
+
+extern "C" int pn2_cluster_points(int n, const float* points, const int* labels, float eps, int min_points, int max_points, int* ids,
+                                  int* header, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n <= 0 || !(eps > 0.0f) || !(eps <= 3.402823466e38f) || min_points < 1 || max_points < 0) return PN2_EINVAL;
+    if (!points || !ids || !header || !workspace) return PN2_ENULL;
+    if ((((uintptr_t)points | (uintptr_t)labels | (uintptr_t)ids | (uintptr_t)header) & 3) != 0 || ((uintptr_t)workspace & 255) != 0)
+        return PN2_EINVAL;
+    Layout L;
+    if (workspace_bytes < fixed_layout(n, &L)) return PN2_EINVAL;  // refused before the sort is asked for its share
+    const hipError_t le = layout(n, &L);
+    if (le != hipSuccess) return (int)le;
+    if (workspace_bytes < L.total) return PN2_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // eager by nature: the caller reads the header (the number of clusters sizes what follows).  Refused on a capturing stream.
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(st, &capturing);
+    if (e != hipSuccess) return (int)e;
+    if (capturing != hipStreamCaptureStatusNone) return PN2_EUNSUP;
+
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    Scal* scal = reinterpret_cast<Scal*>(ws + L.scal);
+    unsigned long long* keys_in = reinterpret_cast<unsigned long long*>(ws + L.keys_in);
+    unsigned long long* keys_out = reinterpret_cast<unsigned long long*>(ws + L.keys_out);
+    int* vals_in = reinterpret_cast<int*>(ws + L.vals_in);
+    int* vals_out = reinterpret_cast<int*>(ws + L.vals_out);
+    float4* spts = reinterpret_cast<float4*>(ws + L.spts);
+    int* parent = reinterpret_cast<int*>(ws + L.parent);
+    int* csize = reinterpret_cast<int*>(ws + L.csize);
+    int* root = reinterpret_cast<int*>(ws + L.root);
+    int* number = reinterpret_cast<int*>(ws + L.number);
+    int* bcount = reinterpret_cast<int*>(ws + L.bcount);
+    const double h = (double)eps * (1.0 + 1.0 / 1048576.0);
+    const double eps2 = (double)eps * (double)eps;
+    const int blocks = scan_blocks(n);
+
+    cluster_init_kernel<<<1, 64, 0, st>>>(scal);
+    cluster_min_kernel<<<blocks, kT, 0, st>>>(n, points, labels, scal);
+    cluster_key_kernel<<<blocks, kT, 0, st>>>(n, points, labels, h, scal, keys_in, vals_in);
+    PN2_RETURN_IF_LAUNCH_FAILED();
+    size_t cub = L.cub_bytes;
+    e = hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub, keys_in, keys_out, vals_in, vals_out, n, 0, 64, st);
+    if (e != hipSuccess) return (int)e;
+    cluster_gather_kernel<<<blocks, kT, 0, st>>>(n, points, labels, vals_out, spts, parent, csize);
+    cluster_union_kernel<<<blocks, kT, 0, st>>>(n, keys_out, vals_out, spts, eps2, scal, parent);
+    cluster_flatten_kernel<<<blocks, kT, 0, st>>>(n, points, labels, parent, scal, root, csize);
+    cluster_flag_kernel<<<blocks, kT, 0, st>>>(n, root, csize, min_points, max_points, scal, bcount);
+    cluster_offsets_kernel<<<1, kT, 0, st>>>(blocks, bcount, scal, header);
+    cluster_number_kernel<<<blocks, kT, 0, st>>>(n, root, csize, min_points, max_points, bcount, number);
+    cluster_ids_kernel<<<blocks, kT, 0, st>>>(n, root, number, ids);
+    PN2_RETURN_IF_LAUNCH_FAILED();
+    return PN2_OK;
+}
+
+extern "C" int pn2_cluster_stats(int n, int nclusters, const float* points, const int* labels, const int* ids, int* first, int* size,
+                                 int* label, float* bbox, void* stream) {
+    if (n <= 0 || nclusters <= 0) return PN2_EINVAL;
+    if (nclusters > n) return PN2_ERANGE;
+    if (!points || !ids || !first || !size || !label || !bbox) return PN2_ENULL;
+    if ((((uintptr_t)points | (uintptr_t)labels | (uintptr_t)ids | (uintptr_t)first | (uintptr_t)size | (uintptr_t)label |
+          (uintptr_t)bbox) & 3) != 0)
+        return PN2_EINVAL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned* box = reinterpret_cast<unsigned*>(bbox);
+    const int cblocks = scan_blocks(nclusters);
+    stats_init_kernel<<<cblocks, kT, 0, st>>>(nclusters, first, size, box);
+    stats_points_kernel<<<scan_blocks(n), kT, 0, st>>>(n, nclusters, points, ids, first, size, box);
+    stats_finish_kernel<<<cblocks, kT, 0, st>>>(n, nclusters, labels, first, label, box);
+    PN2_RETURN_IF_LAUNCH_FAILED();
+    return PN2_OK;
+}
+
+extern "C" int pn2_cluster_colors(int n, const int* ids, uint8_t* rgb, void* stream) {
+    if (n <= 0) return PN2_EINVAL;
+    if (!ids || !rgb) return PN2_ENULL;
+    if (((uintptr_t)ids & 3) != 0) return PN2_EINVAL;
+    cluster_colors_kernel<<<scan_blocks(n), kT, 0, static_cast<hipStream_t>(stream)>>>(n, ids, rgb);
+    PN2_RETURN_IF_LAUNCH_FAILED();
+    return PN2_OK;
+}

@@ -11,6 +11,7 @@ the Predictor is used as it is.  After the frame's construction nothing on this 
 """
 import torch
 
+from .cluster import euclidean_clusters
 from .predict import Predictor, _on_device
 
 
@@ -44,3 +45,10 @@ class PredictInterpolator:
         out = torch.full((int(n),), -1, dtype=torch.int32, device=dense_labels.device)
         out[file_data.source_index.long()] = dense_labels.to(torch.int32)
         return out
+
+    def objects_for_frame(self, file_data, dense_labels, eps, classes, min_points=1, max_points=None):
+        """(extension) the labelled points of file_data.points grouped into objects: cluster.euclidean_clusters over the points
+        whose dense label is one of `classes`, two points in one object when a chain of steps of at most eps joins them
+        -> cluster.Clusters (ids index file_data.points).  Eager: reads the number of objects back."""
+        return euclidean_clusters(file_data.points, eps, labels=dense_labels, classes=classes, min_points=min_points,
+                                  max_points=max_points)
