@@ -2,6 +2,7 @@
 
     python examples/cluster_objects.py --points scene.pcd --labels scene.labels --eps 0.5 --classes 8 --min_points 10 --out result
     python examples/cluster_objects.py --synthetic 3000 --eps 0.2 --out result
+    python examples/cluster_objects.py --points frame.pcd --labels frame.labels --eps 0.5 --ground 0.2 --out result
 
 The cloud and the labels are read on the device (pn2.read_point_cloud, pn2.load_labels), the points of each class in --classes
 (every label >= 1 that occurs when it is not given) are clustered with pn2.euclidean_clusters -- two points in one object when a
@@ -10,6 +11,9 @@ chain of points of their label joins them in steps of at most --eps -- and the r
     <out>/objects.png   the scene from above, every object in a colour of its own, everything else grey (pn2.render)
 with one line per class and its object count on the terminal.  --synthetic N makes N points in tight blobs of known sizes on a
 lattice (synthetic(N) below), so the expected output is known.
+--ground THR takes the ground out first: pn2.segment_plane with the axis (0,0,1) and a normal within 15 degrees of it
+(--ground-trials hypotheses), its inliers are left out of the clustering, and objects.txt begins with the line
+    ground count a b c d                        the exact, unnormalised plane a*x + b*y + c*z + d = 0 (repr-exact floats)
 """
 import argparse
 import os
@@ -23,6 +27,7 @@ sys.path.insert(0, ROOT)
 import pn2_amd as pn2  # noqa: E402
 
 SYNTHETIC_EPS = 0.2
+GROUND_MAX_ANGLE = 15.0  # degrees between the ground's normal and the z axis, at the most
 
 
 def synthetic(n, seed=0):
@@ -57,6 +62,8 @@ def main():
     parser.add_argument("--classes", type=int, nargs="*", default=None, help="the labels to cluster (default: every label >= 1)")
     parser.add_argument("--min_points", type=int, default=1)
     parser.add_argument("--max_points", type=int, default=0, help="0: no upper bound")
+    parser.add_argument("--ground", type=float, default=0.0, help="remove the ground first: points within this distance of it")
+    parser.add_argument("--ground-trials", type=int, default=1024, help="RANSAC hypotheses for --ground")
     parser.add_argument("--out", default="result/objects")
     parser.add_argument("--width", type=int, default=1280)
     parser.add_argument("--height", type=int, default=960)
@@ -75,6 +82,12 @@ def main():
     if not eps > 0:
         parser.error("--eps")
     classes = flags.classes if flags.classes else [c for c in torch.unique(labels).tolist() if c >= 1]
+    ground_lines = []
+    if flags.ground > 0:
+        ground = pn2.segment_plane(points, flags.ground, trials=flags.ground_trials, axis=(0, 0, 1), max_angle=GROUND_MAX_ANGLE)
+        labels = torch.where(ground.inliers, torch.full_like(labels, -1), labels)
+        ground_lines = ["ground %d %s" % (ground.count, " ".join(repr(v) for v in ground.raw.tolist()))]
+        print("ground: %d of %d points" % (ground.count, len(points)))
 
     clusters = pn2.euclidean_clusters(points, eps, labels=labels, classes=classes, min_points=flags.min_points,
                                       max_points=flags.max_points)
@@ -85,7 +98,7 @@ def main():
 
     os.makedirs(flags.out, exist_ok=True)
     with open(os.path.join(flags.out, "objects.txt"), "w") as f:
-        f.writelines(line + "\n" for line in object_lines(clusters))
+        f.writelines(line + "\n" for line in ground_lines + object_lines(clusters))
     image = pn2.render.render_colors(points, pn2.cluster_colors(clusters.ids), "top", flags.width, flags.height, size=2)
     pn2.render.write_png(os.path.join(flags.out, "objects.png"), image)
     print("Output written to", flags.out)

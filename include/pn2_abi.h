@@ -1284,6 +1284,61 @@ int pn2_cluster_stats(int n, int nclusters, const float *points, const int *labe
                       int *label, float *bbox, void *stream);
 int pn2_cluster_colors(int n, const int *ids, uint8_t *rgb, void *stream);
 
+/* Plane segmentation (csrc/pn2_plane.hip): the dominant plane of a cloud by random sample consensus (RANSAC) -- the ground of a
+ * LiDAR frame, a road, a floor, a facade.  tests/plane_ref.py is the numpy model of the rules and is compared for equality: the
+ * decisions are float64 comparisons in a fixed order (the library is built without contraction) and everything after them is
+ * integer, so nothing in a result depends on the order in which threads arrive.  No square root and no division anywhere.
+ *
+ *   points (n,3) float32; labels (n) int32 or NULL.  A point is VALID when its three coordinates are finite and, with labels, its
+ *   label is >= 0 (the rule of pn2_cluster_points).
+ *   A PLANE is six doubles (x0,y0,z0, a,b,c): a point on it and an unnormalised normal.  nn = (a*a + b*b) + c*c.  The plane is
+ *   VOID when nn is not finite or not > 0.
+ *   A point p is an INLIER of a non-void plane when, with e = (a*(x-x0) + b*(y-y0)) + c*(z-z0) in float64 (x the float32
+ *   coordinate widened), the comparison  e*e <= thr2*nn  is true, thr2 = (double)thr * (double)thr, thr float32, finite and > 0.
+ *   A NaN on either side makes the comparison false, and so does an e*e that overflows against a finite thr2*nn.
+ *   AXIS CONSTRAINT (optional): axis (3) float64 ON THE HOST or NULL, cos2 in [0,1].  A non-void plane is additionally void when
+ *     dt*dt >= (cos2*nn) * ((ax*ax + ay*ay) + az*az),  dt = (a*ax + b*ay) + c*az,  is false: its normal is further from the axis
+ *   (or its opposite) than the angle whose squared cosine is cos2.
+ *
+ * pn2_plane_score: counts[t] = the number of valid inliers of plane t of planes (nplanes,6) float64, 0 for a void plane; counts
+ *   (nplanes) int32.  Public in its own right: it scores hypotheses carried over from an earlier frame.  Two launches: one that
+ *   clears counts (no memset node), one in which a lane owns a plane and a workgroup 256 planes and chunks of 1024 points staged
+ *   in LDS as doubles; every lane adds its partial count with one integer atomicAdd.  PN2_EINVAL: n < 1, nplanes outside
+ *   [1, 2^24], thr not finite or <= 0; PN2_ENULL: points, planes or counts NULL; PN2_EINVAL: points, labels, counts not 4-byte
+ *   or planes not 8-byte aligned; PN2_EUNSUP: a capturing stream (below).
+ *
+ * pn2_plane_workspace_size: *bytes = the workspace of pn2_plane_ransac(n, trials) (a host query like pn2_cluster_workspace_size:
+ *   PN2_EINVAL for n < 1 or trials outside [1, 2^20], PN2_ENULL without bytes).
+ *
+ * pn2_plane_ransac queues, with no allocation and no synchronisation:
+ *   1 the valid point indices in ascending order (an ordered compaction); V = their number.
+ *   2 the hypotheses t = 0 .. trials-1: with h = sample_stream(seed, 0, 0) of csrc/pn2_rng.h, the sample points A, B, C are the
+ *     valid points of rank draw64(h, 2^45 + 3t + j) % V, j = 0, 1, 2 (unsigned 64-bit); as doubles, u = B-A, v = C-A, the normal
+ *     is (uy*vz - uz*vy, uz*vx - ux*vz, ux*vy - uy*vx) and the origin A.  Repeated ranks and collinear points give nn == 0: void.
+ *     With an axis, the planes it excludes are void too.
+ *   3 the scores of pn2_plane_score (a void trial scores 0; a non-void one at least 1: its origin is a valid point with e == 0).
+ *   4 the winner: the largest count, the lowest t among equal counts.
+ *   5 inlier (n) uint8: 1 for the valid inliers of the winner, 0 for every other point;
+ *     plane (4) float64 = the raw (a,b,c,d), d = -((a*x0 + b*y0) + c*z0), oriented by negating all four exactly: with an axis so
+ *     that dt >= 0, without one so that the first non-zero of (c,b,a) is positive.  Not normalised: it stays comparable for
+ *     equality.
+ *   6 header (8) int32: [0] status, [1] inlier count, [2] winning trial, [3..5] the point indices of A, B, C, [6] V, [7] the
+ *     number of non-void trials.  Status 0 = ok; 1 = V < 3; 2 = every trial void.  With a status other than 0, inlier is all 0,
+ *     plane is four zeros and header[1..5] = 0, 0, -1, -1, -1.
+ *   workspace: 256-byte aligned, at least pn2_plane_workspace_size bytes.  Refusals, nothing launched and nothing written, in this
+ *   order: PN2_EINVAL (n < 1, trials outside [1, 2^20], thr not finite or <= 0, with an axis: cos2 outside [0,1] or NaN, an axis
+ *   that is non-finite or all zero), PN2_ENULL (points, inlier, plane, header or workspace NULL), PN2_EINVAL (points, labels,
+ *   header not 4-byte or plane not 8-byte aligned, workspace not 256-byte aligned or too small), PN2_EUNSUP (a capturing stream).
+ *
+ * Both pn2_plane_score and pn2_plane_ransac refuse a capturing stream.  They allocate nothing and would be capturable; nothing in
+ * the project captures them yet, so the refusal stands until a later change lifts it together with a capture test. */
+int pn2_plane_score(int n, const float *points, const int *labels, int nplanes, const double *planes, float thr, int *counts,
+                    void *stream);
+int pn2_plane_workspace_size(int n, int trials, unsigned long long *bytes);
+int pn2_plane_ransac(int n, const float *points, const int *labels, float thr, int trials, unsigned long long seed,
+                     const double *axis, double cos2, unsigned char *inlier, double *plane, int *header, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

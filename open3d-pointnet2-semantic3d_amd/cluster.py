@@ -37,6 +37,41 @@ def _device_of(points, labels):
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def _check_cloud(points, labels, classes):
+    """the shape and dtype checks of a (labelled) cloud, before the library is touched -> n, the sorted classes or None"""
+    shape = tuple(points.shape)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError("points: (n,3)")
+    n = shape[0]
+    if labels is not None:
+        if tuple(labels.shape) != (n,):
+            raise ValueError("labels: (n,) for points (n,3)")
+        kind = labels.dtype
+        if (kind.is_floating_point or kind == torch.bool) if torch.is_tensor(labels) else kind.kind not in "iu":
+            raise ValueError("labels: integers")
+    if classes is not None:
+        if labels is None:
+            raise ValueError("classes without labels")
+        classes = sorted({int(c) for c in classes})
+        if any(c < 0 for c in classes):
+            raise ValueError("classes: labels >= 0")
+    if n >= 2 ** 31:
+        raise ValueError("fewer than 2^31 points")
+    return n, classes
+
+
+def _device_cloud(points, labels, classes):
+    """-> the device, float32 points and int32 labels (or None) on it, every label outside `classes` turned into -1"""
+    dev = _device_of(points, labels)
+    points = _on_device(points, torch.float32, dev)
+    if labels is not None:
+        labels = _on_device(labels, torch.int32, dev)
+        if classes is not None:
+            labels = torch.where(torch.isin(labels, torch.tensor(classes, dtype=torch.int32, device=dev)), labels,
+                                 torch.full_like(labels, -1))
+    return dev, points, labels
+
+
 def euclidean_clusters(points, eps, labels=None, classes=None, min_points=1, max_points=None):
     """points (n,3), labels (n,) integers or None: device tensors or numpy arrays (cast to float32 / int32).  classes: an iterable
     of the labels to cluster -- every other label counts as -1, "no object"; None clusters every label >= 0.  min_points,
@@ -59,31 +94,8 @@ def euclidean_clusters(points, eps, labels=None, classes=None, min_points=1, max
         raise ValueError("max_points: at least 0 (0 or None: no upper bound)")
     if max_points and max_points < min_points:
         raise ValueError("max_points below min_points")
-    shape = tuple(points.shape)
-    if len(shape) != 2 or shape[1] != 3:
-        raise ValueError("points: (n,3)")
-    n = shape[0]
-    if labels is not None:
-        if tuple(labels.shape) != (n,):
-            raise ValueError("labels: (n,) for points (n,3)")
-        kind = labels.dtype
-        if (kind.is_floating_point or kind == torch.bool) if torch.is_tensor(labels) else kind.kind not in "iu":
-            raise ValueError("labels: integers")
-    if classes is not None:
-        if labels is None:
-            raise ValueError("classes without labels")
-        classes = sorted({int(c) for c in classes})
-        if any(c < 0 for c in classes):
-            raise ValueError("classes: labels >= 0")
-    if n >= 2 ** 31:
-        raise ValueError("fewer than 2^31 points")
-    dev = _device_of(points, labels)
-    points = _on_device(points, torch.float32, dev)
-    if labels is not None:
-        labels = _on_device(labels, torch.int32, dev)
-        if classes is not None:
-            labels = torch.where(torch.isin(labels, torch.tensor(classes, dtype=torch.int32, device=dev)), labels,
-                                 torch.full_like(labels, -1))
+    n, classes = _check_cloud(points, labels, classes)
+    dev, points, labels = _device_cloud(points, labels, classes)
     ids = torch.full((n,), -1, dtype=torch.int32, device=dev)
     empty = Clusters(ids, 0, *(torch.empty((0,), dtype=torch.int32, device=dev) for _ in range(3)),
                      torch.empty((0, 6), dtype=torch.float32, device=dev))

@@ -44,7 +44,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "pn2_common.h"
-#include "pn2_wg.h"  // wg_excl_scan_flag, wg_sum, al256, WsCarver
+#include "pn2_wg.h"  // wg_excl_scan_flag, wg_sum, point_valid, al256, WsCarver, piece
 
 namespace {
 
@@ -68,14 +68,6 @@ struct Layout {
 };
 
 inline int scan_blocks(int n) { return (int)(((long long)n + kT - 1) / kT); }
-
-// the offset of the next piece of `count` elements of T
-template <typename T>
-inline size_t piece(WsCarver& c, size_t count) {
-    const size_t o = c.used;
-    c.take<T>(count);
-    return o;
-}
 
 // everything but the sort's share: known without asking the sort
 inline size_t fixed_layout(int n, Layout* L) {
@@ -114,13 +106,6 @@ __device__ __forceinline__ unsigned ord32(float f) {
 __device__ __forceinline__ float unord32(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }
-__device__ __forceinline__ bool finite32(float f) { return (__float_as_uint(f) & 0x7F800000u) != 0x7F800000u; }
-
-__device__ __forceinline__ bool point_valid(const float* __restrict__ points, const int* __restrict__ labels, long long i) {
-    const float* p = points + (size_t)i * 3;
-    return finite32(p[0]) && finite32(p[1]) && finite32(p[2]) && (!labels || labels[i] >= 0);
-}
-
 __device__ __forceinline__ unsigned wave_umin(unsigned v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {

@@ -8,6 +8,8 @@
 //   2^40 + 0, 1, 2       pn2_dataset.hip: scene, centre, angle of the sample
 //   [2^41, 2^45)         pn2_augment.hip (its own tags are listed there): a dataset and an augmenter that share a seed and a
 //                        counter value share no draw
+//   [2^45, 2^46)         pn2_plane.hip: 2^45 + 3t + j is the rank draw of sample point j of RANSAC trial t (stream
+//                        sample_stream(seed, 0, 0))
 #pragma once
 #include <hip/hip_runtime.h>
 

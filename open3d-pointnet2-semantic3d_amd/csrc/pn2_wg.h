@@ -110,6 +110,14 @@ __device__ __forceinline__ int lower_bound_x(const double* __restrict__ pts, int
 __device__ __forceinline__ bool finite64(double v) {
     return ((unsigned long long)__double_as_longlong(v) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
 }
+__device__ __forceinline__ bool finite32(float f) { return (__float_as_uint(f) & 0x7F800000u) != 0x7F800000u; }
+
+// the VALID point of pn2_cluster_points and of the plane entry points (include/pn2_abi.h): three finite coordinates and, with
+// labels, a label >= 0
+__device__ __forceinline__ bool point_valid(const float* __restrict__ points, const int* __restrict__ labels, long long i) {
+    const float* p = points + (size_t)i * 3;
+    return finite32(p[0]) && finite32(p[1]) && finite32(p[2]) && (!labels || labels[i] >= 0);
+}
 
 // ---- host: workspace carving ---------------------------------------------------------------------------------------------------
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -125,3 +133,11 @@ struct WsCarver {
         return p;
     }
 };
+
+// the offset of the next piece of `count` elements of T (a layout that is kept as offsets)
+template <typename T>
+inline size_t piece(WsCarver& c, size_t count) {
+    const size_t o = c.used;
+    c.take<T>(count);
+    return o;
+}

@@ -11,7 +11,8 @@ the Predictor is used as it is.  After the frame's construction nothing on this 
 """
 import torch
 
-from .cluster import euclidean_clusters
+from .cluster import _device_of, euclidean_clusters
+from .plane import segment_plane
 from .predict import Predictor, _on_device
 
 
@@ -46,9 +47,24 @@ class PredictInterpolator:
         out[file_data.source_index.long()] = dense_labels.to(torch.int32)
         return out
 
-    def objects_for_frame(self, file_data, dense_labels, eps, classes, min_points=1, max_points=None):
+    def objects_for_frame(self, file_data, dense_labels, eps, classes, min_points=1, max_points=None, exclude=None):
         """(extension) the labelled points of file_data.points grouped into objects: cluster.euclidean_clusters over the points
         whose dense label is one of `classes`, two points in one object when a chain of steps of at most eps joins them
-        -> cluster.Clusters (ids index file_data.points).  Eager: reads the number of objects back."""
+        -> cluster.Clusters (ids index file_data.points).  Eager: reads the number of objects back.
+        exclude: an optional (n,) bool mask of points to leave out, such as ground_for_frame(...).inliers: their label becomes -1
+        before clustering."""
+        if exclude is not None:
+            dense_labels = _on_device(dense_labels, torch.int32, _device_of(file_data.points, dense_labels))
+            exclude = _on_device(exclude, torch.bool, dense_labels.device)
+            if exclude.shape != dense_labels.shape:
+                raise ValueError("exclude: one bool per point")
+            dense_labels = torch.where(exclude, torch.full_like(dense_labels, -1), dense_labels)
         return euclidean_clusters(file_data.points, eps, labels=dense_labels, classes=classes, min_points=min_points,
                                   max_points=max_points)
+
+    def ground_for_frame(self, file_data, distance_threshold, trials=1024, seed=0, max_angle=15.0, dense_labels=None, classes=None):
+        """(extension) the ground of file_data.points: plane.segment_plane with the axis (0,0,1), the normal within max_angle
+        degrees of it and pointing up, over the points whose dense label is one of `classes` (every point without dense_labels)
+        -> plane.Plane; .inliers is the `exclude` of objects_for_frame, .distance(points) the height above ground.  Eager."""
+        return segment_plane(file_data.points, distance_threshold, trials=trials, seed=seed, labels=dense_labels, classes=classes,
+                             axis=(0.0, 0.0, 1.0), max_angle=max_angle)
