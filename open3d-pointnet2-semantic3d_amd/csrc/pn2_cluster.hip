@@ -41,10 +41,10 @@
 //   * parent[] is read with relaxed agent-scope atomic loads.  A stale value is an ancestor of an earlier time: it lengthens a walk
 //     or fails a swap, and no loop's exit rests on it -- find ends on its own decreasing index, unite on the swap's answer.
 // No kernel waits for another workgroup.
-#include <hipcub/hipcub.hpp>
-
-#include "pn2_common.h"
-#include "pn2_wg.h"  // wg_excl_scan_flag, wg_sum, point_valid, al256, WsCarver, piece
+#include "pn2_common.h"   // pn2_wave_umin
+#include "pn2_ordered.h"  // ordered_key32, ordered_to_float
+#include "pn2_sort.h"     // IndexSort
+#include "pn2_wg.h"       // wg_excl_scan_flag, wg_excl_scan_int, wg_sum, point_valid, WsCarver
 
 namespace {
 
@@ -63,56 +63,25 @@ struct Scal {
     int nkeptpts;         // points in kept clusters
 };
 
-struct Layout {
-    size_t scal, keys_in, keys_out, vals_in, vals_out, spts, parent, csize, root, number, bcount, cub, cub_bytes, total;
-};
-
 inline int scan_blocks(int n) { return (int)(((long long)n + kT - 1) / kT); }
 
-// everything but the sort's share: known without asking the sort
-inline size_t fixed_layout(int n, Layout* L) {
-    WsCarver c{nullptr};
+struct Ws {  // workspace carve-up
+    Scal* scal;
+    IndexSort<unsigned long long> sort;
+    float4* spts;
+    int *parent, *csize, *root, *number, *bcount;
+};
+inline int ws_layout(int n, WsCarver& c, Ws* w) {
     const size_t N = (size_t)n;
-    L->scal = piece<Scal>(c, 1);
-    L->keys_in = piece<unsigned long long>(c, N);
-    L->keys_out = piece<unsigned long long>(c, N);
-    L->vals_in = piece<int>(c, N);
-    L->vals_out = piece<int>(c, N);
-    L->spts = piece<float4>(c, N);
-    L->parent = piece<int>(c, N);
-    L->csize = piece<int>(c, N);
-    L->root = piece<int>(c, N);
-    L->number = piece<int>(c, N);
-    L->bcount = piece<int>(c, (size_t)scan_blocks(n));
-    return c.used;
-}
-
-inline hipError_t layout(int n, Layout* L) {
-    const size_t fixed = fixed_layout(n, L);
-    size_t cub = 0;
-    const hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, cub, (const unsigned long long*)nullptr,
-                                                            (unsigned long long*)nullptr, (const int*)nullptr, (int*)nullptr, n, 0, 64);
-    L->cub_bytes = cub;
-    L->cub = fixed;
-    L->total = fixed + al256(cub);
-    return e;
-}
-
-// the order-preserving uint32 image of a float (li_ord / li_unord of the dense-label grid, depth_key of the renderer)
-__device__ __forceinline__ unsigned ord32(float f) {
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float unord32(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-__device__ __forceinline__ unsigned wave_umin(unsigned v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned t = (unsigned)__shfl_xor((int)v, o);
-        v = t < v ? t : v;
-    }
-    return v;
+    w->scal = c.take<Scal>(1);
+    w->sort.carve(c, N);
+    w->spts = c.take<float4>(N);
+    w->parent = c.take<int>(N);
+    w->csize = c.take<int>(N);
+    w->root = c.take<int>(N);
+    w->number = c.take<int>(N);
+    w->bcount = c.take<int>((size_t)scan_blocks(n));
+    return w->sort.carve_tmp(c, n, 0, 64);
 }
 
 __global__ void cluster_init_kernel(Scal* __restrict__ s) {
@@ -129,14 +98,14 @@ cluster_min_kernel(int n, const float* __restrict__ points, const int* __restric
     unsigned k0 = 0xFFFFFFFFu, k1 = 0xFFFFFFFFu, k2 = 0xFFFFFFFFu;
     if (ok) {
         const float* p = points + (size_t)i * 3;
-        k0 = ord32(p[0]);
-        k1 = ord32(p[1]);
-        k2 = ord32(p[2]);
+        k0 = ordered_key32(p[0]);
+        k1 = ordered_key32(p[1]);
+        k2 = ordered_key32(p[2]);
     }
     const unsigned long long bal = __ballot(ok);
-    k0 = wave_umin(k0);
-    k1 = wave_umin(k1);
-    k2 = wave_umin(k2);
+    k0 = pn2_wave_umin(k0);
+    k1 = pn2_wave_umin(k1);
+    k2 = pn2_wave_umin(k2);
     if (bal != 0ull && (threadIdx.x & 63) == 0) {
         atomicMin(&s->min_key[0], k0);
         atomicMin(&s->min_key[1], k1);
@@ -158,7 +127,7 @@ cluster_key_kernel(int n, const float* __restrict__ points, const int* __restric
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             // >= 0: the minimum is the least of them and the subtraction is monotone
-            const double q = __builtin_floor(((double)p[a] - (double)unord32(s->min_key[a])) / h);
+            const double q = __builtin_floor(((double)p[a] - (double)ordered_to_float(s->min_key[a])) / h);
             const bool in = q < (double)kCellLimit;  // tested in floating point before the conversion
             far = far || !in;
             key |= (unsigned long long)(in ? (long long)q : (long long)(kCellLimit - 1)) << (kCellBits * a);
@@ -373,7 +342,7 @@ stats_points_kernel(int n, int nclusters, const float* __restrict__ points, cons
     unsigned* b = box + (size_t)c * 6;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const unsigned k = ord32(points[(size_t)i * 3 + a]);
+        const unsigned k = ordered_key32(points[(size_t)i * 3 + a]);
         if (k < __hip_atomic_load(b + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT)) atomicMin(b + a, k);
         if (k > __hip_atomic_load(b + 3 + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT)) atomicMax(b + 3 + a, k);
     }
@@ -389,7 +358,7 @@ stats_finish_kernel(int n, int nclusters, const int* __restrict__ labels, const 
 #pragma unroll
     for (int a = 0; a < 6; ++a) {
         unsigned* w = box + (size_t)c * 6 + a;
-        *w = __float_as_uint(unord32(*w));
+        *w = __float_as_uint(ordered_to_float(*w));
     }
 }
 
@@ -426,10 +395,11 @@ cluster_colors_kernel(int n, const int* __restrict__ ids, unsigned char* __restr
 extern "C" int pn2_cluster_workspace_size(int n, unsigned long long* bytes) {
     if (n <= 0) return PN2_EINVAL;
     if (!bytes) return PN2_ENULL;
-    Layout L;
-    const hipError_t e = layout(n, &L);
-    if (e != hipSuccess) return (int)e;
-    *bytes = (unsigned long long)L.total;
+    WsCarver c{nullptr};
+    Ws w;
+    const int rc = ws_layout(n, c, &w);
+    if (rc != PN2_OK) return rc;
+    *bytes = (unsigned long long)c.used;
     return PN2_OK;
 }
 
@@ -439,11 +409,10 @@ extern "C" int pn2_cluster_points(int n, const float* points, const int* labels,
     if (!points || !ids || !header || !workspace) return PN2_ENULL;
     if ((((uintptr_t)points | (uintptr_t)labels | (uintptr_t)ids | (uintptr_t)header) & 3) != 0 || ((uintptr_t)workspace & 255) != 0)
         return PN2_EINVAL;
-    Layout L;
-    if (workspace_bytes < fixed_layout(n, &L)) return PN2_EINVAL;  // refused before the sort is asked for its share
-    const hipError_t le = layout(n, &L);
-    if (le != hipSuccess) return (int)le;
-    if (workspace_bytes < L.total) return PN2_EINVAL;
+    WsCarver c{static_cast<unsigned char*>(workspace), workspace_bytes};
+    Ws w;
+    const int rc = ws_layout(n, c, &w);  // too small: refused before the sort is asked for its share
+    if (rc != PN2_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // eager by nature: the caller reads the header (the number of clusters sizes what follows).  Refused on a capturing stream.
     hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
@@ -451,36 +420,23 @@ extern "C" int pn2_cluster_points(int n, const float* points, const int* labels,
     if (e != hipSuccess) return (int)e;
     if (capturing != hipStreamCaptureStatusNone) return PN2_EUNSUP;
 
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    Scal* scal = reinterpret_cast<Scal*>(ws + L.scal);
-    unsigned long long* keys_in = reinterpret_cast<unsigned long long*>(ws + L.keys_in);
-    unsigned long long* keys_out = reinterpret_cast<unsigned long long*>(ws + L.keys_out);
-    int* vals_in = reinterpret_cast<int*>(ws + L.vals_in);
-    int* vals_out = reinterpret_cast<int*>(ws + L.vals_out);
-    float4* spts = reinterpret_cast<float4*>(ws + L.spts);
-    int* parent = reinterpret_cast<int*>(ws + L.parent);
-    int* csize = reinterpret_cast<int*>(ws + L.csize);
-    int* root = reinterpret_cast<int*>(ws + L.root);
-    int* number = reinterpret_cast<int*>(ws + L.number);
-    int* bcount = reinterpret_cast<int*>(ws + L.bcount);
     const double h = (double)eps * (1.0 + 1.0 / 1048576.0);
     const double eps2 = (double)eps * (double)eps;
     const int blocks = scan_blocks(n);
 
-    cluster_init_kernel<<<1, 64, 0, st>>>(scal);
-    cluster_min_kernel<<<blocks, kT, 0, st>>>(n, points, labels, scal);
-    cluster_key_kernel<<<blocks, kT, 0, st>>>(n, points, labels, h, scal, keys_in, vals_in);
+    cluster_init_kernel<<<1, 64, 0, st>>>(w.scal);
+    cluster_min_kernel<<<blocks, kT, 0, st>>>(n, points, labels, w.scal);
+    cluster_key_kernel<<<blocks, kT, 0, st>>>(n, points, labels, h, w.scal, w.sort.keys_in, w.sort.vals_in);
     PN2_RETURN_IF_LAUNCH_FAILED();
-    size_t cub = L.cub_bytes;
-    e = hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub, keys_in, keys_out, vals_in, vals_out, n, 0, 64, st);
+    e = w.sort.run(n, 0, 64, st);
     if (e != hipSuccess) return (int)e;
-    cluster_gather_kernel<<<blocks, kT, 0, st>>>(n, points, labels, vals_out, spts, parent, csize);
-    cluster_union_kernel<<<blocks, kT, 0, st>>>(n, keys_out, vals_out, spts, eps2, scal, parent);
-    cluster_flatten_kernel<<<blocks, kT, 0, st>>>(n, points, labels, parent, scal, root, csize);
-    cluster_flag_kernel<<<blocks, kT, 0, st>>>(n, root, csize, min_points, max_points, scal, bcount);
-    cluster_offsets_kernel<<<1, kT, 0, st>>>(blocks, bcount, scal, header);
-    cluster_number_kernel<<<blocks, kT, 0, st>>>(n, root, csize, min_points, max_points, bcount, number);
-    cluster_ids_kernel<<<blocks, kT, 0, st>>>(n, root, number, ids);
+    cluster_gather_kernel<<<blocks, kT, 0, st>>>(n, points, labels, w.sort.vals_out, w.spts, w.parent, w.csize);
+    cluster_union_kernel<<<blocks, kT, 0, st>>>(n, w.sort.keys_out, w.sort.vals_out, w.spts, eps2, w.scal, w.parent);
+    cluster_flatten_kernel<<<blocks, kT, 0, st>>>(n, points, labels, w.parent, w.scal, w.root, w.csize);
+    cluster_flag_kernel<<<blocks, kT, 0, st>>>(n, w.root, w.csize, min_points, max_points, w.scal, w.bcount);
+    cluster_offsets_kernel<<<1, kT, 0, st>>>(blocks, w.bcount, w.scal, header);
+    cluster_number_kernel<<<blocks, kT, 0, st>>>(n, w.root, w.csize, min_points, max_points, w.bcount, w.number);
+    cluster_ids_kernel<<<blocks, kT, 0, st>>>(n, w.root, w.number, ids);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

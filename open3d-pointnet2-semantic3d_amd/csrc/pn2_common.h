@@ -304,6 +304,7 @@ __device__ __forceinline__ unsigned pn2_wave_umax(unsigned v) {
     t = PN2_DPP_U32(v, 0x143, 0xC); v = v > t ? v : t;
     return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
+__device__ __forceinline__ unsigned pn2_wave_umin(unsigned v) { return ~pn2_wave_umax(~v); }
 
 // max of a 64-bit key over the 16 lanes of row 0; result (uniform) from lane 15.
 #define PN2_U64MAX_STEP(v, ctrl)                                        \

@@ -9,9 +9,11 @@
 // caches its best (td, tie-break) key and the coordinates of that point, so the global argmax is a reduction
 // over <= 2048 cached keys in LDS.  Same picks as the reference: first pick 0, winner = max td, ties -> lowest
 // (k mod 512, k) on the ORIGINAL indices.  One 1024-thread workgroup per cloud, ~2 us per round.
-#include <hipcub/hipcub.hpp>
-
+#include "pn2_bbox.h"  // bbox_init_kernel, bbox_kernel
 #include "pn2_fps_common.h"
+#include "pn2_ordered.h"  // ordered_to_float
+#include "pn2_sort.h"     // IndexSort
+#include "pn2_wg.h"       // WsCarver
 
 namespace {
 
@@ -23,71 +25,28 @@ constexpr int kFbMaxBuckets = 2048;  // n <= 131072
 constexpr int kFbBPT = kFbMaxBuckets / kFbThreads;  // buckets per thread (2)
 constexpr size_t kFbLds = (size_t)kFbMaxBuckets * (16 + 8 + 24 + 2);
 
-struct FbLayout {  // byte offsets into the caller's workspace (256-byte aligned)
-    size_t bbox, keys_in, keys_out, vals_in, vals_out, sorted, td, seg, cub, total, cub_bytes;
-    int npad;
+struct FbWs {  // workspace carve-up
+    int npad;  // n rounded up to whole buckets
+    unsigned* bbox;  // b x 6 ordered keys (pn2_bbox.h)
+    IndexSort<unsigned> sort;
+    float4* sorted;
+    float* td;
+    size_t total;
 };
-
-inline size_t fb_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-FbLayout fb_layout(int b, int n) {
-    FbLayout L{};
-    L.npad = (n + 63) & ~63;
-    size_t o = 0;
-    const size_t bn = (size_t)b * n, bp = (size_t)b * L.npad;
-    L.bbox = o; o = fb_align(o + (size_t)b * 6 * 4);
-    L.keys_in = o; o = fb_align(o + bn * 4);
-    L.keys_out = o; o = fb_align(o + bn * 4);
-    L.vals_in = o; o = fb_align(o + bn * 4);
-    L.vals_out = o; o = fb_align(o + bn * 4);
-    L.sorted = o; o = fb_align(o + bp * 16);
-    L.td = o; o = fb_align(o + bp * 4);
-    L.seg = o; o = fb_align(o + (size_t)(b + 1) * 4);
-    size_t cub = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cub, (const unsigned*)nullptr, (unsigned*)nullptr, (const int*)nullptr,
-                                             (int*)nullptr, b <= 32 ? b * n : n, 0, 32);
-    L.cub_bytes = cub;
-    L.cub = o; o = fb_align(o + cub);
-    L.total = o;
-    return L;
+inline void fb_ws_layout(int b, int n, unsigned char* base, FbWs* w) {
+    WsCarver c{base};
+    w->npad = (n + 63) & ~63;
+    const size_t bn = (size_t)b * n, bp = (size_t)b * w->npad;
+    w->bbox = c.take<unsigned>((size_t)b * 6);
+    w->sort.carve(c, bn);
+    w->sorted = c.take<float4>(bp);
+    w->td = c.take<float>(bp);
+    c.take<int>((size_t)b + 1);  // (a piece nothing reads: it stays in the size the query has always reported)
+    (void)w->sort.carve_tmp(c, b <= 32 ? b * n : n, 0, 32);  // one sort of the batch, or a sort per cloud: pn2_fps_large
+    w->total = c.used;
 }
 
-__device__ __forceinline__ unsigned fb_ord(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float fb_unord(unsigned u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
 __device__ __forceinline__ unsigned fb_tiekey(int k) { return (((unsigned)k & 511u) << 22) | ((unsigned)k >> 9); }
-
-__global__ void fb_init_kernel(int b, unsigned* bbox) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < b * 6) bbox[i] = (i % 6) < 3 ? 0xffffffffu : 0u;
-}
-
-__global__ void __launch_bounds__(256)
-fb_bbox_kernel(int n, const float* __restrict__ xyz_all, unsigned* __restrict__ bbox_all) {
-    const float* __restrict__ xyz = xyz_all + (size_t)blockIdx.y * n * 3;
-    unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const unsigned o = fb_ord(xyz[(size_t)i * 3 + a]);
-            mn[a] = o < mn[a] ? o : mn[a];
-            mx[a] = o > mx[a] ? o : mx[a];
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const unsigned wmn = ~pn2_wave_umax(~mn[a]);
-        const unsigned wmx = pn2_wave_umax(mx[a]);
-        if ((threadIdx.x & 63) == 0) {
-            atomicMin(&bbox_all[blockIdx.y * 6 + a], wmn);
-            atomicMax(&bbox_all[blockIdx.y * 6 + 3 + a], wmx);
-        }
-    }
-}
 
 __device__ __forceinline__ unsigned fb_spread10(unsigned v) {  // 10 bits -> every third bit
     v &= 0x3ffu;
@@ -111,8 +70,8 @@ fb_keys_kernel(int n, const float* __restrict__ xyz_all, const unsigned* __restr
     float lo[3], ext = 0.f;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        lo[a] = fb_unord(bbox_all[bi * 6 + a]);
-        ext = fmaxf(ext, fb_unord(bbox_all[bi * 6 + 3 + a]) - lo[a]);
+        lo[a] = ordered_to_float(bbox_all[bi * 6 + a]);
+        ext = fmaxf(ext, ordered_to_float(bbox_all[bi * 6 + 3 + a]) - lo[a]);
     }
     unsigned X[3];
 #pragma unroll
@@ -666,7 +625,9 @@ extern "C" int pn2_debug_set_fps_large(int what, int value) { if (what == 11) { 
 
 extern "C" size_t pn2_fps_large_workspace_bytes(int b, int n) {
     if (b <= 0 || n <= 0) return 0;
-    return fb_layout(b, n).total;
+    FbWs w;
+    fb_ws_layout(b, n, nullptr, &w);
+    return w.total;
 }
 
 extern "C" int pn2_fps_large(int b, int n, int m, const float* inp, void* workspace, size_t workspace_bytes, int* out,
@@ -675,40 +636,31 @@ extern "C" int pn2_fps_large(int b, int n, int m, const float* inp, void* worksp
     if (!inp || !out || !workspace) return PN2_ENULL;
     if (n > kFbMaxBuckets * 64 || b > 65535) return PN2_ERANGE;
     if (arith_mode < 0 || arith_mode > 2) return PN2_EINVAL;
-    const FbLayout L = fb_layout(b, n);
-    if (workspace_bytes < L.total || ((uintptr_t)workspace & 255) != 0) return PN2_EINVAL;
+    FbWs w;
+    fb_ws_layout(b, n, static_cast<unsigned char*>(workspace), &w);
+    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255) != 0) return PN2_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    unsigned* bbox = reinterpret_cast<unsigned*>(ws + L.bbox);
-    unsigned* keys_in = reinterpret_cast<unsigned*>(ws + L.keys_in);
-    unsigned* keys_out = reinterpret_cast<unsigned*>(ws + L.keys_out);
-    int* vals_in = reinterpret_cast<int*>(ws + L.vals_in);
-    int* vals_out = reinterpret_cast<int*>(ws + L.vals_out);
-    float4* sorted = reinterpret_cast<float4*>(ws + L.sorted);
-    float* td = reinterpret_cast<float*>(ws + L.td);
-    fb_init_kernel<<<(b * 6 + 255) / 256, 256, 0, st>>>(b, bbox);
+    float4* sorted = w.sorted;
+    float* td = w.td;
+    bbox_init_kernel<<<(b * 6 + 255) / 256, 256, 0, st>>>(b, w.bbox);
     const int gx = (n + 255) / 256;
-    fb_bbox_kernel<<<dim3(gx < 256 ? gx : 256, b), 256, 0, st>>>(n, inp, bbox);
-    fb_keys_kernel<<<dim3(gx, b), 256, 0, st>>>(n, inp, bbox, keys_in, vals_in, (b > 1 && b <= 32) ? 1 : 0);
+    bbox_kernel<<<dim3(gx < 256 ? gx : 256, b), 256, 0, st>>>(n, inp, w.bbox);
+    fb_keys_kernel<<<dim3(gx, b), 256, 0, st>>>(n, inp, w.bbox, w.sort.keys_in, w.sort.vals_in, (b > 1 && b <= 32) ? 1 : 0);
     PN2_RETURN_IF_LAUNCH_FAILED();
     if (b <= 32) {
         // ONE device-wide sort for the whole batch: key = cloud id above the curve index (27 bits of it when b > 1: the
         // index is hierarchical, its top bits are the index on a coarser grid), so cloud bi lands in [bi * n, (bi + 1) * n)
         int cbits = 0;
         while ((1 << cbits) < b) ++cbits;
-        size_t cub = L.cub_bytes;
-        hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub, keys_in, keys_out, vals_in, vals_out, b * n, 0,
-                                                         b == 1 ? 30 : 27 + cbits, st);
+        const hipError_t e = w.sort.run(b * n, 0, b == 1 ? 30 : 27 + cbits, st);
         if (e != hipSuccess) return (int)e;
     } else {
         for (int bi = 0; bi < b; ++bi) {
-            size_t cub = L.cub_bytes;
-            hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub, keys_in + (size_t)bi * n, keys_out + (size_t)bi * n,
-                                                             vals_in + (size_t)bi * n, vals_out + (size_t)bi * n, n, 0, 30, st);
+            const hipError_t e = w.sort.run(n, 0, 30, st, (size_t)bi * n);
             if (e != hipSuccess) return (int)e;
         }
     }
-    fb_gather_kernel<<<dim3((L.npad + 255) / 256, b), 256, 0, st>>>(n, L.npad, inp, vals_out, sorted, td);
+    fb_gather_kernel<<<dim3((w.npad + 255) / 256, b), 256, 0, st>>>(n, w.npad, inp, w.sort.vals_out, sorted, td);
 #define PN2_FB(KERN_, LDS_, ...)                                 \
     do {                                                         \
         if (int e = pn2_allow_lds<KERN_>((int)(LDS_))) return e; \
@@ -716,15 +668,15 @@ extern "C" int pn2_fps_large(int b, int n, int m, const float* inp, void* worksp
     } while (0)
     if (g_fb_variant == 1) {  // tuning builds: the one-pick-per-round kernel (2.5 us per pick at n = 65536)
         switch (arith_mode) {
-            case PN2_ARITH_STRICT: PN2_FB(fps_bucket_kernel<PN2_ARITH_STRICT>, kFbLds, n, L.npad, m, inp, sorted, td, out, new_xyz); break;
-            case PN2_ARITH_FMA: PN2_FB(fps_bucket_kernel<PN2_ARITH_FMA>, kFbLds, n, L.npad, m, inp, sorted, td, out, new_xyz); break;
-            default: PN2_FB(fps_bucket_kernel<PN2_ARITH_FMA_ALT>, kFbLds, n, L.npad, m, inp, sorted, td, out, new_xyz); break;
+            case PN2_ARITH_STRICT: PN2_FB(fps_bucket_kernel<PN2_ARITH_STRICT>, kFbLds, n, w.npad, m, inp, sorted, td, out, new_xyz); break;
+            case PN2_ARITH_FMA: PN2_FB(fps_bucket_kernel<PN2_ARITH_FMA>, kFbLds, n, w.npad, m, inp, sorted, td, out, new_xyz); break;
+            default: PN2_FB(fps_bucket_kernel<PN2_ARITH_FMA_ALT>, kFbLds, n, w.npad, m, inp, sorted, td, out, new_xyz); break;
         }
     } else {
         switch (arith_mode) {
-            case PN2_ARITH_STRICT: PN2_FB(fps_bucket_lazy_kernel<PN2_ARITH_STRICT>, kFlLds, n, L.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
-            case PN2_ARITH_FMA: PN2_FB(fps_bucket_lazy_kernel<PN2_ARITH_FMA>, kFlLds, n, L.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
-            default: PN2_FB(fps_bucket_lazy_kernel<PN2_ARITH_FMA_ALT>, kFlLds, n, L.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
+            case PN2_ARITH_STRICT: PN2_FB(fps_bucket_lazy_kernel<PN2_ARITH_STRICT>, kFlLds, n, w.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
+            case PN2_ARITH_FMA: PN2_FB(fps_bucket_lazy_kernel<PN2_ARITH_FMA>, kFlLds, n, w.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
+            default: PN2_FB(fps_bucket_lazy_kernel<PN2_ARITH_FMA_ALT>, kFlLds, n, w.npad, m, inp, sorted, td, out, new_xyz, g_fb_stats); break;
         }
     }
 #undef PN2_FB

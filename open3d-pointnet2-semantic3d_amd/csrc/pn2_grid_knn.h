@@ -5,11 +5,13 @@
 // index.  What a query does with its neighbours is a `Tail` (see li_query_kernel).  Everything here has internal linkage: each
 // translation unit that includes the header gets its own copy of the kernels.
 #pragma once
-#include <hipcub/hipcub.hpp>
-
 #include <math.h>
 
+#include "pn2_bbox.h"  // bbox_init_kernel, bbox_kernel
 #include "pn2_common.h"
+#include "pn2_ordered.h"  // ordered_to_float
+#include "pn2_sort.h"     // IndexSort
+#include "pn2_wg.h"       // WsCarver
 
 namespace {
 
@@ -22,77 +24,33 @@ struct LiParams {
     int n[3];
 };
 
-struct LiLayout {  // byte offsets into the caller's workspace (256-byte aligned)
-    size_t params, bbox, keys_in, keys_out, vals_in, vals_out, cell_start, cell_end, pts, cub, total;
-    size_t cub_bytes;
+struct LiWs {  // workspace carve-up
+    LiParams* prm;
+    unsigned* bbox;  // 6 ordered keys (pn2_bbox.h)
+    IndexSort<unsigned> sort;
+    int *cell_start, *cell_end;  // kLiMaxCells each
+    float4* sorted;
+    size_t total;
 };
-
-inline size_t li_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-LiLayout li_layout(int ns) {
-    LiLayout L{};
-    size_t o = 0;
+inline void li_ws_layout(int ns, unsigned char* base, LiWs* w) {
+    WsCarver c{base};
     const size_t n = ns > 0 ? (size_t)ns : 1;
-    L.params = o; o = li_align(o + sizeof(LiParams));
-    L.bbox = o; o = li_align(o + 6 * sizeof(unsigned));
-    L.keys_in = o; o = li_align(o + n * 4);
-    L.keys_out = o; o = li_align(o + n * 4);
-    L.vals_in = o; o = li_align(o + n * 4);
-    L.vals_out = o; o = li_align(o + n * 4);
-    L.cell_start = o; o = li_align(o + (size_t)kLiMaxCells * 4);
-    L.cell_end = o; o = li_align(o + (size_t)kLiMaxCells * 4);
-    L.pts = o; o = li_align(o + n * 16);
-    size_t cub = 0;
-    hipcub::DeviceRadixSort::SortPairs(nullptr, cub, (const unsigned*)nullptr, (unsigned*)nullptr, (const int*)nullptr,
-                                       (int*)nullptr, (int)n, 0, kLiCellBits);
-    L.cub_bytes = cub;
-    L.cub = o; o = li_align(o + cub);
-    L.total = o;
-    return L;
-}
-
-// float <-> unsigned with the same ordering (for atomicMin / atomicMax on coordinates)
-__device__ __forceinline__ unsigned li_ord(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float li_unord(unsigned u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
-__global__ void li_init_kernel(unsigned* bbox) {
-    if (threadIdx.x < 3) bbox[threadIdx.x] = 0xffffffffu;       // running minima
-    else if (threadIdx.x < 6) bbox[threadIdx.x] = 0u;           // running maxima
-}
-
-__global__ void __launch_bounds__(256)
-li_bbox_kernel(int ns, const float* __restrict__ pts, unsigned* __restrict__ bbox) {
-    unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += gridDim.x * blockDim.x) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const unsigned o = li_ord(pts[(size_t)i * 3 + a]);
-            mn[a] = o < mn[a] ? o : mn[a];
-            mx[a] = o > mx[a] ? o : mx[a];
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const unsigned wmn = ~pn2_wave_umax(~mn[a]);
-        const unsigned wmx = pn2_wave_umax(mx[a]);
-        if ((threadIdx.x & 63) == 0) {
-            atomicMin(&bbox[a], wmn);
-            atomicMax(&bbox[3 + a], wmx);
-        }
-    }
+    w->prm = c.take<LiParams>(1);
+    w->bbox = c.take<unsigned>(6);
+    w->sort.carve(c, n);
+    w->cell_start = c.take<int>((size_t)kLiMaxCells);
+    w->cell_end = c.take<int>((size_t)kLiMaxCells);
+    w->sorted = c.take<float4>(n);
+    (void)w->sort.carve_tmp(c, (int)n, 0, kLiCellBits);
+    w->total = c.used;
 }
 
 // one thread: cell size so that the grid has about ns/2 cells (<= kLiMaxCells)
 __global__ void li_params_kernel(int ns, const unsigned* __restrict__ bbox, LiParams* __restrict__ prm) {
     float lo[3], hi[3], ext[3], maxext = 0.f;
     for (int a = 0; a < 3; ++a) {
-        lo[a] = li_unord(bbox[a]);
-        hi[a] = li_unord(bbox[3 + a]);
+        lo[a] = ordered_to_float(bbox[a]);
+        hi[a] = ordered_to_float(bbox[3 + a]);
         ext[a] = hi[a] - lo[a];
         maxext = fmaxf(maxext, ext[a]);
     }
@@ -254,34 +212,22 @@ struct LiGrid {  // what the query kernels read, inside the caller's workspace
 };
 
 // The uniform grid over the sparse points, queued on `st`: shared by both entry points.  ns > 0, the workspace checked.
-int li_build_grid(int ns, const float* sparse_points, void* workspace, const LiLayout& L, hipStream_t st, LiGrid* g) {
-    char* ws = static_cast<char*>(workspace);
-    LiParams* prm = reinterpret_cast<LiParams*>(ws + L.params);
-    unsigned* bbox = reinterpret_cast<unsigned*>(ws + L.bbox);
-    unsigned* keys_in = reinterpret_cast<unsigned*>(ws + L.keys_in);
-    unsigned* keys_out = reinterpret_cast<unsigned*>(ws + L.keys_out);
-    int* vals_in = reinterpret_cast<int*>(ws + L.vals_in);
-    int* vals_out = reinterpret_cast<int*>(ws + L.vals_out);
-    int* cell_start = reinterpret_cast<int*>(ws + L.cell_start);
-    int* cell_end = reinterpret_cast<int*>(ws + L.cell_end);
-    float4* sorted = reinterpret_cast<float4*>(ws + L.pts);
+int li_build_grid(int ns, const float* sparse_points, const LiWs& w, hipStream_t st, LiGrid* g) {
     const int sgrid = (ns + 255) / 256;
 
-    li_init_kernel<<<1, 64, 0, st>>>(bbox);
-    li_bbox_kernel<<<sgrid < 1024 ? sgrid : 1024, 256, 0, st>>>(ns, sparse_points, bbox);
-    li_params_kernel<<<1, 1, 0, st>>>(ns, bbox, prm);
-    li_keys_kernel<<<sgrid, 256, 0, st>>>(ns, sparse_points, prm, keys_in, vals_in);
+    bbox_init_kernel<<<1, 64, 0, st>>>(1, w.bbox);
+    bbox_kernel<<<sgrid < 1024 ? sgrid : 1024, 256, 0, st>>>(ns, sparse_points, w.bbox);
+    li_params_kernel<<<1, 1, 0, st>>>(ns, w.bbox, w.prm);
+    li_keys_kernel<<<sgrid, 256, 0, st>>>(ns, sparse_points, w.prm, w.sort.keys_in, w.sort.vals_in);
     PN2_RETURN_IF_LAUNCH_FAILED();
-    size_t cub = L.cub_bytes;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub, keys_in, keys_out, vals_in, vals_out, ns, 0,
-                                                      kLiCellBits, st);
+    hipError_t e = w.sort.run(ns, 0, kLiCellBits, st);
     if (e != hipSuccess) return (int)e;
-    e = hipMemsetAsync(cell_start, 0, (size_t)kLiMaxCells * 4, st);
+    e = hipMemsetAsync(w.cell_start, 0, (size_t)kLiMaxCells * 4, st);
     if (e != hipSuccess) return (int)e;
-    e = hipMemsetAsync(cell_end, 0, (size_t)kLiMaxCells * 4, st);
+    e = hipMemsetAsync(w.cell_end, 0, (size_t)kLiMaxCells * 4, st);
     if (e != hipSuccess) return (int)e;
-    li_bounds_kernel<<<sgrid, 256, 0, st>>>(ns, sparse_points, keys_out, vals_out, cell_start, cell_end, sorted);
-    g->prm = prm; g->cell_start = cell_start; g->cell_end = cell_end; g->sorted = sorted;
+    li_bounds_kernel<<<sgrid, 256, 0, st>>>(ns, sparse_points, w.sort.keys_out, w.sort.vals_out, w.cell_start, w.cell_end, w.sorted);
+    g->prm = w.prm; g->cell_start = w.cell_start; g->cell_end = w.cell_end; g->sorted = w.sorted;
     return PN2_OK;
 }
 

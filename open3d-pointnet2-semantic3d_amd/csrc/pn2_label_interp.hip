@@ -86,7 +86,9 @@ li_fill_kernel(int nd, int* __restrict__ out_labels, uint8_t* __restrict__ out_c
 
 extern "C" size_t pn2_interpolate_label_workspace_bytes(int num_sparse_points) {
     if (num_sparse_points < 0) return 0;
-    return li_layout(num_sparse_points).total;
+    LiWs w;
+    li_ws_layout(num_sparse_points, nullptr, &w);
+    return w.total;
 }
 
 extern "C" int pn2_interpolate_label_with_color(int num_sparse_points, int num_dense_points,
@@ -107,10 +109,11 @@ extern "C" int pn2_interpolate_label_with_color(int num_sparse_points, int num_d
         return PN2_OK;
     }
     if (!sparse_points || !sparse_labels || !workspace) return PN2_ENULL;
-    const LiLayout L = li_layout(ns);
-    if (workspace_bytes < L.total || ((uintptr_t)workspace & 255) != 0) return PN2_EINVAL;
+    LiWs w;
+    li_ws_layout(ns, static_cast<unsigned char*>(workspace), &w);
+    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255) != 0) return PN2_EINVAL;
     LiGrid g;
-    const int rc = li_build_grid(ns, sparse_points, workspace, L, st, &g);
+    const int rc = li_build_grid(ns, sparse_points, w, st, &g);
     if (rc != PN2_OK) return rc;
     const int kf = knn < ns ? knn : ns;
     const LiLabelTail tail{sparse_labels, dense_labels, dense_colors};
@@ -141,10 +144,11 @@ extern "C" int pn2_interpolate_scores(int ns, int nd, int num_class, const float
         return PN2_OK;
     }
     if (((uintptr_t)workspace & 255) != 0) return PN2_EINVAL;
-    const LiLayout L = li_layout(ns);
-    if (workspace_bytes < L.total) return PN2_EINVAL;
+    LiWs w;
+    li_ws_layout(ns, static_cast<unsigned char*>(workspace), &w);
+    if (workspace_bytes < w.total) return PN2_EINVAL;
     LiGrid g;
-    const int rc = li_build_grid(ns, sparse_points, workspace, L, st, &g);
+    const int rc = li_build_grid(ns, sparse_points, w, st, &g);
     if (rc != PN2_OK) return rc;
     const int kf = knn < ns ? knn : ns;
     const LiScoreTail tail{num_class, sparse_scores, dense_labels, dense_colors, dense_confidence};

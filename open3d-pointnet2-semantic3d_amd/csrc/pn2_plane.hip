@@ -27,7 +27,7 @@
 // same launches and writes the outputs of its status.
 #include "pn2_common.h"
 #include "pn2_rng.h"
-#include "pn2_wg.h"  // wg_excl_scan_flag, wg_excl_scan_int, finite64, point_valid, al256, WsCarver, piece
+#include "pn2_wg.h"  // wg_excl_scan_flag, wg_excl_scan_int, finite64, point_valid, WsCarver
 
 namespace {
 
@@ -48,20 +48,22 @@ struct Scal {
     double win[6];            // the winner's plane as scored
 };
 
-struct Layout {
-    size_t scal, bcount, valid, planes, counts, total;
-};
-
 inline int scan_blocks(int n) { return (int)(((long long)n + kT - 1) / kT); }
 
-inline void layout(int n, int trials, Layout* L) {
-    WsCarver c{nullptr};
-    L->scal = piece<Scal>(c, 1);
-    L->bcount = piece<int>(c, (size_t)scan_blocks(n));
-    L->valid = piece<int>(c, (size_t)n);
-    L->planes = piece<double>(c, (size_t)trials * 6);
-    L->counts = piece<int>(c, (size_t)trials);
-    L->total = c.used;
+struct Ws {  // workspace carve-up
+    Scal* scal;
+    int *bcount, *valid;
+    double* planes;
+    int* counts;
+};
+inline size_t ws_layout(int n, int trials, unsigned char* base, Ws* w) {
+    WsCarver c{base};
+    w->scal = c.take<Scal>(1);
+    w->bcount = c.take<int>((size_t)scan_blocks(n));
+    w->valid = c.take<int>((size_t)n);
+    w->planes = c.take<double>((size_t)trials * 6);
+    w->counts = c.take<int>((size_t)trials);
+    return c.used;
 }
 
 // nn of a plane when it is not void, -1 otherwise
@@ -297,9 +299,8 @@ extern "C" int pn2_plane_score(int n, const float* points, const int* labels, in
 extern "C" int pn2_plane_workspace_size(int n, int trials, unsigned long long* bytes) {
     if (n < 1 || trials < 1 || trials > kMaxTrials) return PN2_EINVAL;
     if (!bytes) return PN2_ENULL;
-    Layout L;
-    layout(n, trials, &L);
-    *bytes = (unsigned long long)L.total;
+    Ws w;
+    *bytes = (unsigned long long)ws_layout(n, trials, nullptr, &w);
     return PN2_OK;
 }
 
@@ -320,30 +321,23 @@ extern "C" int pn2_plane_ransac(int n, const float* points, const int* labels, f
     if ((((uintptr_t)points | (uintptr_t)labels | (uintptr_t)header) & 3) != 0 || ((uintptr_t)plane & 7) != 0 ||
         ((uintptr_t)workspace & 255) != 0)
         return PN2_EINVAL;
-    Layout L;
-    layout(n, trials, &L);
-    if (workspace_bytes < L.total) return PN2_EINVAL;
+    Ws w;
+    if (workspace_bytes < ws_layout(n, trials, static_cast<unsigned char*>(workspace), &w)) return PN2_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int rc = refuse_capture(st);  // as pn2_plane_score
     if (rc != PN2_OK) return rc;
 
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    Scal* scal = reinterpret_cast<Scal*>(ws + L.scal);
-    int* bcount = reinterpret_cast<int*>(ws + L.bcount);
-    int* valid = reinterpret_cast<int*>(ws + L.valid);
-    double* planes = reinterpret_cast<double*>(ws + L.planes);
-    int* counts = reinterpret_cast<int*>(ws + L.counts);
     const int blocks = scan_blocks(n), tblocks = (trials + kT - 1) / kT;
 
-    plane_flag_kernel<<<blocks, kT, 0, st>>>(n, points, labels, bcount);
-    plane_offsets_kernel<<<1, kT, 0, st>>>(blocks, bcount, scal);
-    plane_compact_kernel<<<blocks, kT, 0, st>>>(n, points, labels, bcount, valid);
-    plane_hypo_kernel<<<tblocks, kT, 0, st>>>(trials, seed, points, valid, ax, scal, planes);
+    plane_flag_kernel<<<blocks, kT, 0, st>>>(n, points, labels, w.bcount);
+    plane_offsets_kernel<<<1, kT, 0, st>>>(blocks, w.bcount, w.scal);
+    plane_compact_kernel<<<blocks, kT, 0, st>>>(n, points, labels, w.bcount, w.valid);
+    plane_hypo_kernel<<<tblocks, kT, 0, st>>>(trials, seed, points, w.valid, ax, w.scal, w.planes);
     PN2_RETURN_IF_LAUNCH_FAILED();
-    launch_score(n, points, labels, trials, planes, thr, counts, st);
-    plane_select_kernel<<<tblocks, kT, 0, st>>>(trials, counts, scal);
-    plane_finish_kernel<<<1, 64, 0, st>>>(seed, valid, planes, ax, scal, plane, header);
-    plane_mask_kernel<<<blocks, kT, 0, st>>>(n, points, labels, (double)thr * (double)thr, scal, inlier);
+    launch_score(n, points, labels, trials, w.planes, thr, w.counts, st);
+    plane_select_kernel<<<tblocks, kT, 0, st>>>(trials, w.counts, w.scal);
+    plane_finish_kernel<<<1, 64, 0, st>>>(seed, w.valid, w.planes, ax, w.scal, plane, header);
+    plane_mask_kernel<<<blocks, kT, 0, st>>>(n, points, labels, (double)thr * (double)thr, w.scal, inlier);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "pn2_common.h"
+#include "pn2_ordered.h"  // ordered_key32, ordered_to_float
 
 namespace {
 
@@ -47,16 +48,6 @@ label_colors_kernel(int n, int num_class, const int* __restrict__ labels, const 
     }
     const unsigned long long b = __ballot(outside);
     if (bad && b != 0ull && (threadIdx.x & 63) == 0) atomicAdd(bad, (unsigned long long)__popcll(b));
-}
-
-// the order-preserving uint32 image of a float: all bits of a negative one flipped, the sign bit of a non-negative one set
-__device__ __forceinline__ unsigned depth_key(float f) {
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float key_depth(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }
 
 template <typename T>
@@ -95,7 +86,7 @@ render_splat_kernel(int n, int index0, const T* __restrict__ points, RenderView 
         out = !ok;
         if (ok) {
             const float f = (float)d + 0.0f;  // to nearest; -0 -> +0
-            const unsigned long long key = ((unsigned long long)depth_key(f) << 32) | (unsigned)(index0 + (int)i);
+            const unsigned long long key = ((unsigned long long)ordered_key32(f) << 32) | (unsigned)(index0 + (int)i);
             for (int py = y0; py < y1; ++py) {
                 unsigned long long* row = zbuf + (size_t)py * width;
                 for (int px = x0; px < x1; ++px) {
@@ -124,7 +115,7 @@ render_resolve_kernel(int npixels, const unsigned long long* __restrict__ zbuf, 
     const bool empty = key == kEmpty;
     const unsigned at = (unsigned)key;
     if (index) index[p] = empty ? -1 : (int)at;
-    if (depth) depth[p] = empty ? __builtin_inff() : key_depth((unsigned)(key >> 32));
+    if (depth) depth[p] = empty ? __builtin_inff() : ordered_to_float((unsigned)(key >> 32));
     if (image) {
         unsigned char r = background.c[0], g = background.c[1], b = background.c[2];
         if (!empty && at < (unsigned)npoints) {  // an index beyond the colours is never read

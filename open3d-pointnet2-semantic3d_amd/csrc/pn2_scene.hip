@@ -6,12 +6,11 @@
 // Everything the reference computes in float64 (Open3D point arrays are float64) is computed in float64 here with
 // the same operations in the same order, so results are bit-identical; random draws are INPUTS (the caller owns the
 // RNG), never generated inside a kernel.
-#include <hipcub/hipcub.hpp>
-
 #include "pn2_center.h"
 #include "pn2_common.h"
 #include "pn2_ordered.h"  // ordered_key, ordered_to_double
-#include "pn2_wg.h"
+#include "pn2_sort.h"     // IndexSort
+#include "pn2_wg.h"       // wg_excl_scan_flag, lower_bound_x, WsCarver
 
 namespace {
 
@@ -198,30 +197,26 @@ __global__ void voxel_reduce_kernel(const int* __restrict__ nvox_p, const int* _
     }
 }
 
-struct VoxLayout {
-    size_t keys_in, keys_out, vals_in, vals_out, flags, scan, starts, mm, misc, cub, total;
-    size_t cub_bytes;
+struct VoxWs {  // workspace carve-up
+    IndexSort<unsigned long long> sort;  // its temporary storage serves the scan as well: one piece, sized by the larger
+    int *flags, *scan, *starts;
+    double* mm;
+    size_t total;
 };
-inline VoxLayout vox_layout(int n) {
-    VoxLayout L;
-    size_t o = 0;
-    L.keys_in = o; o += al256((size_t)n * 8);
-    L.keys_out = o; o += al256((size_t)n * 8);
-    L.vals_in = o; o += al256((size_t)n * 4);
-    L.vals_out = o; o += al256((size_t)n * 4);
-    L.flags = o; o += al256((size_t)n * 4);
-    L.scan = o; o += al256((size_t)n * 4);
-    L.starts = o; o += al256((size_t)(n + 1) * 4);
-    L.mm = o; o += 256;
-    L.misc = o; o += 256;
+inline void vox_ws_layout(int n, unsigned char* base, VoxWs* w) {
+    WsCarver c{base};
+    w->sort.carve(c, (size_t)n);
+    w->flags = c.take<int>((size_t)n);
+    w->scan = c.take<int>((size_t)n);
+    w->starts = c.take<int>((size_t)n + 1);
+    w->mm = c.take<double>(6);
+    c.take<unsigned char>(256);  // (a piece nothing reads: it stays in the size the query has always reported)
     size_t c1 = 0, c2 = 0;
-    hipcub::DeviceRadixSort::SortPairs(nullptr, c1, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                       (const int*)nullptr, (int*)nullptr, n, 0, 63);
-    hipcub::DeviceScan::InclusiveSum(nullptr, c2, (const int*)nullptr, (int*)nullptr, n);
-    L.cub_bytes = c1 > c2 ? c1 : c2;
-    L.cub = o; o += al256(L.cub_bytes);
-    L.total = o;
-    return L;
+    (void)IndexSort<unsigned long long>::tmp_size(n, 0, 63, &c1);
+    (void)hipcub::DeviceScan::InclusiveSum(nullptr, c2, (const int*)nullptr, (int*)nullptr, n);
+    w->sort.tmp_bytes = c1 > c2 ? c1 : c2;
+    w->sort.tmp = c.take<unsigned char>(w->sort.tmp_bytes);
+    w->total = c.used;
 }
 
 }  // namespace
@@ -257,7 +252,12 @@ extern "C" int pn2_scene_sample(int b, int npts, int cap, const double* points, 
     return PN2_OK;
 }
 
-extern "C" size_t pn2_voxel_downsample_workspace_bytes(int n) { return n > 0 ? vox_layout(n).total : 0; }
+extern "C" size_t pn2_voxel_downsample_workspace_bytes(int n) {
+    if (n <= 0) return 0;
+    VoxWs w;
+    vox_ws_layout(n, nullptr, &w);
+    return w.total;
+}
 
 // downsample.py:46-67.  points/colors (n,3) float64, labels (n) int32 in [0,64) or NULL.  Outputs sized for n voxels:
 // out_points / out_colors (n,3) float64, out_labels (n); *out_count (device int) = number of voxels; voxels sorted by
@@ -268,35 +268,27 @@ extern "C" int pn2_voxel_downsample(int n, const double* points, const double* c
                                     void* workspace, size_t workspace_bytes, void* stream) {
     if (n <= 0 || !(voxel_size > 0)) return PN2_EINVAL;
     if (!points || !out_points || !out_count || !status || !workspace) return PN2_ENULL;
-    const VoxLayout L = vox_layout(n);
-    if (workspace_bytes < L.total || ((uintptr_t)workspace & 255) != 0) return PN2_EINVAL;
+    VoxWs w;
+    vox_ws_layout(n, static_cast<unsigned char*>(workspace), &w);
+    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255) != 0) return PN2_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    unsigned long long* keys_in = reinterpret_cast<unsigned long long*>(ws + L.keys_in);
-    unsigned long long* keys_out = reinterpret_cast<unsigned long long*>(ws + L.keys_out);
-    int* vals_in = reinterpret_cast<int*>(ws + L.vals_in);
-    int* vals_out = reinterpret_cast<int*>(ws + L.vals_out);
-    int* flags = reinterpret_cast<int*>(ws + L.flags);
-    int* scan = reinterpret_cast<int*>(ws + L.scan);
-    int* starts = reinterpret_cast<int*>(ws + L.starts);
-    double* mm = reinterpret_cast<double*>(ws + L.mm);
+    double* mm = w.mm;
     hipError_t e = hipMemsetAsync(mm, 0xFF, 24, st);  // min keys: all ones
     if (e == hipSuccess) e = hipMemsetAsync(mm + 3, 0, 24, st);  // max keys: zero
     if (e == hipSuccess) e = hipMemsetAsync(status, 0, sizeof(int), st);
     if (e != hipSuccess) return (int)e;
     const int blocks = (n + 255) / 256;
     voxel_minmax_kernel<<<blocks < 1024 ? blocks : 1024, 256, 0, st>>>(n, points, mm);
-    voxel_key_kernel<<<blocks, 256, 0, st>>>(n, points, mm, voxel_size, keys_in, vals_in, status);
-    size_t cub = L.cub_bytes;
-    e = hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub, keys_in, keys_out, vals_in, vals_out, n, 0, 63, st);
+    voxel_key_kernel<<<blocks, 256, 0, st>>>(n, points, mm, voxel_size, w.sort.keys_in, w.sort.vals_in, status);
+    e = w.sort.run(n, 0, 63, st);
     if (e != hipSuccess) return (int)e;
-    voxel_heads_kernel<<<blocks, 256, 0, st>>>(n, keys_out, flags);
-    cub = L.cub_bytes;
-    e = hipcub::DeviceScan::InclusiveSum(ws + L.cub, cub, flags, scan, n, st);
+    voxel_heads_kernel<<<blocks, 256, 0, st>>>(n, w.sort.keys_out, w.flags);
+    size_t scan_bytes = w.sort.tmp_bytes;
+    e = hipcub::DeviceScan::InclusiveSum(w.sort.tmp, scan_bytes, w.flags, w.scan, n, st);
     if (e != hipSuccess) return (int)e;
-    voxel_starts_kernel<<<blocks, 256, 0, st>>>(n, flags, scan, starts, out_count);
-    voxel_reduce_kernel<<<blocks, 256, 0, st>>>(out_count, starts, vals_out, points, colors, labels, out_points, out_colors,
-                                                out_labels, status);
+    voxel_starts_kernel<<<blocks, 256, 0, st>>>(n, w.flags, w.scan, w.starts, out_count);
+    voxel_reduce_kernel<<<blocks, 256, 0, st>>>(out_count, w.starts, w.sort.vals_out, points, colors, labels, out_points,
+                                                out_colors, out_labels, status);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

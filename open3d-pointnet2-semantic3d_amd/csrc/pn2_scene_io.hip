@@ -10,7 +10,7 @@
 #include "pn2_color.h"  // unit_to_byte
 #include "pn2_common.h"
 #include "pn2_itoa.h"
-#include "pn2_wg.h"  // al256
+#include "pn2_wg.h"  // WsCarver
 
 namespace {
 
@@ -92,19 +92,21 @@ format_emit_kernel(const int* __restrict__ values, int nrows, int ncols, const i
     if (blockIdx.x == gridDim.x - 1 && tid == 0) *out_bytes = (unsigned long long)end;
 }
 
-struct FormatLayout {
-    size_t total_at, base_at, cub_at, bytes, cub_bytes;
+struct FormatWs {  // workspace carve-up
     int nwg;
+    int *wg_total, *wg_base;  // per workgroup
+    void* scan_tmp;
+    size_t scan_bytes, bytes;
 };
-inline hipError_t format_layout(int nrows, FormatLayout& L) {
-    L.nwg = (nrows + kFmtT - 1) / kFmtT;
-    size_t o = 0;
-    L.total_at = o; o += al256((size_t)L.nwg * 4);
-    L.base_at = o; o += al256((size_t)L.nwg * 4);
-    L.cub_bytes = 0;
-    const hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, L.cub_bytes, (const int*)nullptr, (int*)nullptr, L.nwg);
-    L.cub_at = o; o += al256(L.cub_bytes);
-    L.bytes = o;
+inline hipError_t format_ws_layout(int nrows, unsigned char* base, FormatWs* w) {
+    WsCarver c{base};
+    w->nwg = (nrows + kFmtT - 1) / kFmtT;
+    w->wg_total = c.take<int>((size_t)w->nwg);
+    w->wg_base = c.take<int>((size_t)w->nwg);
+    w->scan_bytes = 0;
+    const hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, w->scan_bytes, (const int*)nullptr, (int*)nullptr, w->nwg);
+    w->scan_tmp = c.take<unsigned char>(w->scan_bytes);
+    w->bytes = c.used;
     return e;
 }
 
@@ -172,10 +174,10 @@ extern "C" int pn2_text_format_workspace_bytes(int nrows, unsigned long long* by
     if (nrows <= 0) return PN2_EINVAL;
     if (!bytes) return PN2_ENULL;
     if ((long long)nrows * PN2_TEXT_I32_CHARS > PN2_TEXT_MAX_BYTES) return PN2_ERANGE;
-    FormatLayout L;
-    const hipError_t e = format_layout(nrows, L);
+    FormatWs w;
+    const hipError_t e = format_ws_layout(nrows, nullptr, &w);
     if (e != hipSuccess) return (int)e;
-    *bytes = L.bytes;
+    *bytes = w.bytes;
     return PN2_OK;
 }
 
@@ -186,20 +188,16 @@ extern "C" int pn2_text_format_i32(const int* values, int nrows, int ncols, unsi
     const long long worst = (long long)nrows * ncols * PN2_TEXT_I32_CHARS;
     if (worst > PN2_TEXT_MAX_BYTES) return PN2_ERANGE;
     if (((uintptr_t)text & 15) != 0 || ((uintptr_t)workspace & 255) != 0 || ((uintptr_t)values & 3) != 0) return PN2_EINVAL;
-    FormatLayout L;
-    hipError_t e = format_layout(nrows, L);
+    FormatWs w;
+    hipError_t e = format_ws_layout(nrows, static_cast<unsigned char*>(workspace), &w);
     if (e != hipSuccess) return (int)e;
-    if (workspace_bytes < L.bytes) return PN2_EINVAL;
+    if (workspace_bytes < w.bytes) return PN2_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    int* wg_total = reinterpret_cast<int*>(ws + L.total_at);
-    int* wg_base = reinterpret_cast<int*>(ws + L.base_at);
     const int cap = text_cap < (size_t)worst ? (int)text_cap : (int)worst;  // no row ends past `worst`
-    format_count_kernel<<<L.nwg, kFmtT, 0, st>>>(values, nrows, ncols, wg_total);
-    size_t cub = L.cub_bytes;
-    e = hipcub::DeviceScan::ExclusiveSum(ws + L.cub_at, cub, wg_total, wg_base, L.nwg, st);
+    format_count_kernel<<<w.nwg, kFmtT, 0, st>>>(values, nrows, ncols, w.wg_total);
+    e = hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, w.scan_bytes, w.wg_total, w.wg_base, w.nwg, st);
     if (e != hipSuccess) return (int)e;
-    format_emit_kernel<<<L.nwg, kFmtT, 0, st>>>(values, nrows, ncols, wg_base, text, cap, out_bytes);
+    format_emit_kernel<<<w.nwg, kFmtT, 0, st>>>(values, nrows, ncols, w.wg_base, text, cap, out_bytes);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

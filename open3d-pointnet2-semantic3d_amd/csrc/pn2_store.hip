@@ -19,11 +19,10 @@
 // in 16 * 3).  The input of a scene (tens of MB) sits in the Infinity Cache after the key kernel's pass, so the kernel runs at
 // the rate the memory system turns random 64-byte requests around, not at the HBM byte rate; nine independent loads per lane
 // and eight waves per SIMD are what hides their latency.
-#include <hipcub/hipcub.hpp>
-
 #include "pn2_common.h"
 #include "pn2_ordered.h"  // ordered_key, ordered_to_double
-#include "pn2_wg.h"          // finite64, al256
+#include "pn2_sort.h"     // IndexSort
+#include "pn2_wg.h"       // finite64, WsCarver
 
 namespace {
 
@@ -37,29 +36,14 @@ struct Scal {  // the scalars the kernels reduce into (workspace)
     unsigned flags;
 };
 
-struct Layout {
-    size_t keys_in, keys_out, vals_in, vals_out, scal, cub, total;
-    size_t cub_bytes;
+struct Ws {  // workspace carve-up
+    IndexSort<unsigned long long> sort;
+    Scal* scal;
 };
-// the part in front of the sort's own temporary storage: known without asking the sort
-inline size_t fixed_layout(int n, Layout* L) {
-    size_t o = 0;
-    L->keys_in = o; o += al256((size_t)n * 8);
-    L->keys_out = o; o += al256((size_t)n * 8);
-    L->vals_in = o; o += al256((size_t)n * 4);
-    L->vals_out = o; o += al256((size_t)n * 4);
-    L->scal = o; o += 256;
-    return o;
-}
-inline hipError_t layout(int n, Layout* L) {
-    size_t o = fixed_layout(n, L);
-    size_t cub = 0;
-    const hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, cub, (const unsigned long long*)nullptr,
-                                                            (unsigned long long*)nullptr, (const int*)nullptr, (int*)nullptr, n, 0, 64);
-    L->cub_bytes = cub;
-    L->cub = o; o += al256(cub);
-    L->total = o;
-    return e;
+inline int ws_layout(int n, WsCarver& c, Ws* w) {
+    w->sort.carve(c, (size_t)n);
+    w->scal = c.take<Scal>(1);
+    return w->sort.carve_tmp(c, n, 0, 64);
 }
 
 __global__ void __launch_bounds__(kT)
@@ -144,10 +128,11 @@ __global__ void ingest_finish_kernel(const Scal* __restrict__ scal, double* __re
 extern "C" int pn2_scene_ingest_workspace_size(int n, unsigned long long* bytes) {
     if (n <= 0) return PN2_EINVAL;
     if (!bytes) return PN2_ENULL;
-    Layout L;
-    const hipError_t e = layout(n, &L);
-    if (e != hipSuccess) return (int)e;
-    *bytes = (unsigned long long)L.total;
+    WsCarver c{nullptr};
+    Ws w;
+    const int rc = ws_layout(n, c, &w);
+    if (rc != PN2_OK) return rc;
+    *bytes = (unsigned long long)c.used;
     return PN2_OK;
 }
 
@@ -161,28 +146,21 @@ extern "C" int pn2_scene_ingest(int n, const double* points, const double* color
         (((uintptr_t)labels | (uintptr_t)out_colors | (uintptr_t)out_perm | (uintptr_t)status) & 3) != 0 ||
         ((uintptr_t)workspace & 255) != 0)
         return PN2_EINVAL;
-    Layout L;
-    if (workspace_bytes < fixed_layout(n, &L)) return PN2_EINVAL;  // refused before the sort is asked for its share
-    const hipError_t le = layout(n, &L);
-    if (le != hipSuccess) return (int)le;
-    if (workspace_bytes < L.total) return PN2_EINVAL;
+    WsCarver c{static_cast<unsigned char*>(workspace), workspace_bytes};
+    Ws w;
+    const int rc = ws_layout(n, c, &w);  // too small: refused before the sort is asked for its share
+    if (rc != PN2_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    unsigned long long* keys_in = reinterpret_cast<unsigned long long*>(ws + L.keys_in);
-    unsigned long long* keys_out = reinterpret_cast<unsigned long long*>(ws + L.keys_out);
-    int* vals_in = reinterpret_cast<int*>(ws + L.vals_in);
-    int* vals_out = reinterpret_cast<int*>(ws + L.vals_out);
-    Scal* scal = reinterpret_cast<Scal*>(ws + L.scal);
+    Scal* scal = w.scal;
     hipError_t e = hipMemsetAsync(&scal->zmin, 0xFF, sizeof(unsigned long long), st);  // running minimum: all ones
     if (e == hipSuccess) e = hipMemsetAsync(&scal->zmax, 0, sizeof(Scal) - offsetof(Scal, zmax), st);  // maximum, flags
     if (e == hipSuccess) e = hipMemsetAsync(out_hist, 0, kHistBins * sizeof(long long), st);
     if (e != hipSuccess) return (int)e;
     const int blocks = (int)(((long long)n + kT - 1) / kT);
-    ingest_key_kernel<<<blocks, kT, 0, st>>>(n, points, keys_in, vals_in, scal);
-    size_t cub = L.cub_bytes;
-    e = hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub, keys_in, keys_out, vals_in, vals_out, n, 0, 64, st);
+    ingest_key_kernel<<<blocks, kT, 0, st>>>(n, points, w.sort.keys_in, w.sort.vals_in, scal);
+    e = w.sort.run(n, 0, 64, st);
     if (e != hipSuccess) return (int)e;
-    ingest_gather_kernel<<<blocks, kT, 0, st>>>(n, vals_out, points, colors, labels, out_points, colors ? out_colors : nullptr,
+    ingest_gather_kernel<<<blocks, kT, 0, st>>>(n, w.sort.vals_out, points, colors, labels, out_points, colors ? out_colors : nullptr,
                                                 out_labels, out_perm, reinterpret_cast<unsigned long long*>(out_hist), scal);
     ingest_finish_kernel<<<1, 64, 0, st>>>(scal, out_zrange, status);
     PN2_RETURN_IF_LAUNCH_FAILED();

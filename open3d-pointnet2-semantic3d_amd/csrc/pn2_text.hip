@@ -9,7 +9,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "pn2_common.h"
-#include "pn2_wg.h"  // al256
+#include "pn2_wg.h"  // WsCarver
 
 namespace {
 
@@ -94,19 +94,21 @@ text_starts_kernel(const unsigned char* __restrict__ text, int nbytes, const int
     }
 }
 
-struct IndexLayout {
-    size_t count, base, cub, total, cub_bytes;
+struct IndexWs {  // workspace carve-up
     int ntiles;
+    int *count, *base;  // per tile
+    void* scan_tmp;
+    size_t scan_bytes, total;
 };
-inline hipError_t index_layout(int nbytes, IndexLayout& L) {
-    L.ntiles = (nbytes + kTile - 1) / kTile;
-    size_t o = 0;
-    L.count = o; o += al256((size_t)L.ntiles * 4);
-    L.base = o; o += al256((size_t)L.ntiles * 4);
-    L.cub_bytes = 0;
-    const hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, L.cub_bytes, (const int*)nullptr, (int*)nullptr, L.ntiles);
-    L.cub = o; o += al256(L.cub_bytes);
-    L.total = o;
+inline hipError_t index_ws_layout(int nbytes, unsigned char* base, IndexWs* w) {
+    WsCarver c{base};
+    w->ntiles = (nbytes + kTile - 1) / kTile;
+    w->count = c.take<int>((size_t)w->ntiles);
+    w->base = c.take<int>((size_t)w->ntiles);
+    w->scan_bytes = 0;
+    const hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, w->scan_bytes, (const int*)nullptr, (int*)nullptr, w->ntiles);
+    w->scan_tmp = c.take<unsigned char>(w->scan_bytes);
+    w->total = c.used;
     return e;
 }
 
@@ -305,10 +307,10 @@ extern "C" int pn2_text_index_workspace_bytes(int nbytes, unsigned long long* by
     if (nbytes <= 0) return PN2_EINVAL;
     if (!bytes) return PN2_ENULL;
     if (nbytes > PN2_TEXT_MAX_BYTES) return PN2_ERANGE;
-    IndexLayout L;
-    const hipError_t e = index_layout(nbytes, L);
+    IndexWs w;
+    const hipError_t e = index_ws_layout(nbytes, nullptr, &w);
     if (e != hipSuccess) return (int)e;
-    *bytes = L.total;
+    *bytes = w.total;
     return PN2_OK;
 }
 
@@ -318,19 +320,15 @@ extern "C" int pn2_text_index_lines(const unsigned char* text, int nbytes, int* 
     if (!text || !line_start || !out_count || !workspace) return PN2_ENULL;
     if (nbytes > PN2_TEXT_MAX_BYTES) return PN2_ERANGE;
     if (((uintptr_t)text & 15) != 0 || ((uintptr_t)workspace & 255) != 0) return PN2_EINVAL;
-    IndexLayout L;
-    hipError_t e = index_layout(nbytes, L);
+    IndexWs w;
+    hipError_t e = index_ws_layout(nbytes, static_cast<unsigned char*>(workspace), &w);
     if (e != hipSuccess) return (int)e;
-    if (workspace_bytes < L.total) return PN2_EINVAL;
+    if (workspace_bytes < w.total) return PN2_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    int* tile_count = reinterpret_cast<int*>(ws + L.count);
-    int* tile_base = reinterpret_cast<int*>(ws + L.base);
-    text_count_kernel<<<L.ntiles, kIdxT, 0, st>>>(text, nbytes, tile_count);
-    size_t cub = L.cub_bytes;
-    e = hipcub::DeviceScan::ExclusiveSum(ws + L.cub, cub, tile_count, tile_base, L.ntiles, st);
+    text_count_kernel<<<w.ntiles, kIdxT, 0, st>>>(text, nbytes, w.count);
+    e = hipcub::DeviceScan::ExclusiveSum(w.scan_tmp, w.scan_bytes, w.count, w.base, w.ntiles, st);
     if (e != hipSuccess) return (int)e;
-    text_starts_kernel<<<L.ntiles, kIdxT, 0, st>>>(text, nbytes, tile_base, line_start, line_cap, out_count);
+    text_starts_kernel<<<w.ntiles, kIdxT, 0, st>>>(text, nbytes, w.base, line_start, line_cap, out_count);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

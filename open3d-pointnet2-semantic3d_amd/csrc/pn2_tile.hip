@@ -26,11 +26,10 @@
 // tiles, so a sample's rows come from a few MB that the key and sort passes of the plan left in the Infinity Cache; the kernel
 // runs at the rate the memory system turns those small requests around.  Rows go through registers: a row is far shorter than
 // the 1 KiB pieces for which staging an indexed gather in LDS pays, and nothing reads a row twice.
-#include <hipcub/hipcub.hpp>
-
 #include "pn2_common.h"
 #include "pn2_ordered.h"  // ordered_key, ordered_to_double
-#include "pn2_wg.h"
+#include "pn2_sort.h"     // IndexSort
+#include "pn2_wg.h"       // wg_sum, wg_excl_scan_flag, wg_excl_scan_int, finite64, WsCarver
 
 namespace {
 
@@ -49,32 +48,20 @@ struct Scal {  // the scalars the kernels reduce into (workspace; cleared by the
     int n_tiles, n_samples, skipped;
 };
 
-struct Layout {
-    size_t keys_in, keys_out, vals_in, tile_start, chunk_a, chunk_b, scal, cub, total;
-    size_t cub_bytes;
-};
 inline int chunks_of(int n) { return (n + kChunk - 1) / kChunk; }
-// the part in front of the sort's own temporary storage: known without asking the sort
-inline size_t fixed_layout(int n, Layout* L) {
-    size_t o = 0;
-    L->keys_in = o; o += al256((size_t)n * 8);
-    L->keys_out = o; o += al256((size_t)n * 8);
-    L->vals_in = o; o += al256((size_t)n * 4);
-    L->tile_start = o; o += al256((size_t)n * 4);
-    L->chunk_a = o; o += al256((size_t)chunks_of(n) * 4);
-    L->chunk_b = o; o += al256((size_t)chunks_of(n) * 4);
-    L->scal = o; o += 256;
-    return o;
-}
-inline hipError_t layout(int n, Layout* L) {
-    size_t o = fixed_layout(n, L);
-    size_t cub = 0;
-    const hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, cub, (const unsigned long long*)nullptr,
-                                                            (unsigned long long*)nullptr, (const int*)nullptr, (int*)nullptr, n, 0, 64);
-    L->cub_bytes = cub;
-    L->cub = o; o += al256(cub);
-    L->total = o;
-    return e;
+
+struct Ws {  // workspace carve-up
+    IndexSort<unsigned long long> sort;  // its sorted row indices are the caller's `order`
+    int *tile_start, *chunk_a, *chunk_b;
+    Scal* scal;
+};
+inline int ws_layout(int n, int* order, WsCarver& c, Ws* w) {
+    w->sort.carve_into(c, (size_t)n, order);
+    w->tile_start = c.take<int>((size_t)n);
+    w->chunk_a = c.take<int>((size_t)chunks_of(n));
+    w->chunk_b = c.take<int>((size_t)chunks_of(n));
+    w->scal = c.take<Scal>(1);
+    return w->sort.carve_tmp(c, n, 0, 64);
 }
 
 // ---- plan ------------------------------------------------------------------------------------------------------------------
@@ -342,10 +329,11 @@ extern "C" int pn2_tile_plan_workspace_size(int n, unsigned long long* bytes) {
     if (n <= 0) return PN2_EINVAL;
     if (n > PN2_FRAME_MAX_ROWS) return PN2_ERANGE;
     if (!bytes) return PN2_ENULL;
-    Layout L;
-    const hipError_t e = layout(n, &L);
-    if (e != hipSuccess) return (int)e;
-    *bytes = (unsigned long long)L.total;
+    WsCarver c{nullptr};
+    Ws w;
+    const int rc = ws_layout(n, nullptr, c, &w);
+    if (rc != PN2_OK) return rc;
+    *bytes = (unsigned long long)c.used;
     return PN2_OK;
 }
 
@@ -360,36 +348,28 @@ extern "C" int pn2_tile_plan(int n, const double* points, double box_size_x, dou
     if (((uintptr_t)points & 7) != 0 || (((uintptr_t)order | (uintptr_t)header) & 3) != 0 || ((uintptr_t)samples & 15) != 0 ||
         ((uintptr_t)workspace & 255) != 0)
         return PN2_EINVAL;
-    Layout L;
-    if (workspace_bytes < fixed_layout(n, &L)) return PN2_EINVAL;  // refused before the sort is asked for its share
-    const hipError_t le = layout(n, &L);
-    if (le != hipSuccess) return (int)le;
-    if (workspace_bytes < L.total) return PN2_EINVAL;
+    WsCarver c{static_cast<unsigned char*>(workspace), workspace_bytes};
+    Ws w;
+    const int rc = ws_layout(n, order, c, &w);  // too small: refused before the sort is asked for its share
+    if (rc != PN2_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    unsigned long long* keys_in = reinterpret_cast<unsigned long long*>(ws + L.keys_in);
-    unsigned long long* keys_out = reinterpret_cast<unsigned long long*>(ws + L.keys_out);
-    int* vals_in = reinterpret_cast<int*>(ws + L.vals_in);
-    int* tile_start = reinterpret_cast<int*>(ws + L.tile_start);
-    int* chunk_a = reinterpret_cast<int*>(ws + L.chunk_a);
-    int* chunk_b = reinterpret_cast<int*>(ws + L.chunk_b);
-    Scal* scal = reinterpret_cast<Scal*>(ws + L.scal);
+    Scal* scal = w.scal;
     hipError_t e = hipMemsetAsync(&scal->ymin, 0xFF, sizeof(unsigned long long), st);  // running minimum: all ones
     if (e == hipSuccess) e = hipMemsetAsync(&scal->flags, 0, sizeof(Scal) - offsetof(Scal, flags), st);
     if (e != hipSuccess) return (int)e;
     const int blocks = (int)(((long long)n + kT - 1) / kT);
     const int nch = chunks_of(n);  // chunks of positions; tiles number at most n, so it bounds their chunks as well
     tp_ymin_kernel<<<blocks, kT, 0, st>>>(n, points, scal);
-    tp_key_kernel<<<blocks, kT, 0, st>>>(n, points, box_size_x, box_size_y, phase_x, phase_y, keys_in, vals_in, scal);
-    size_t cub = L.cub_bytes;
-    e = hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub, keys_in, keys_out, vals_in, order, n, 0, 64, st);
+    tp_key_kernel<<<blocks, kT, 0, st>>>(n, points, box_size_x, box_size_y, phase_x, phase_y, w.sort.keys_in,
+                                         w.sort.vals_in, scal);
+    e = w.sort.run(n, 0, 64, st);
     if (e != hipSuccess) return (int)e;
-    tp_head_count_kernel<<<nch, kT, 0, st>>>(n, keys_out, chunk_a);
-    tp_scan_kernel<<<1, kScanT, 0, st>>>(nch, chunk_a, &scal->n_tiles);
-    tp_head_emit_kernel<<<nch, kT, 0, st>>>(n, keys_out, chunk_a, tile_start);
-    tp_tile_count_kernel<<<nch, kT, 0, st>>>(n, npts, min_points, tile_start, chunk_b, scal);
-    tp_scan_kernel<<<1, kScanT, 0, st>>>(nch, chunk_b, &scal->n_samples);
-    tp_rows_emit_kernel<<<nch, kT, 0, st>>>(n, npts, min_points, sample_cap, tile_start, chunk_b, scal, samples, header);
+    tp_head_count_kernel<<<nch, kT, 0, st>>>(n, w.sort.keys_out, w.chunk_a);
+    tp_scan_kernel<<<1, kScanT, 0, st>>>(nch, w.chunk_a, &scal->n_tiles);
+    tp_head_emit_kernel<<<nch, kT, 0, st>>>(n, w.sort.keys_out, w.chunk_a, w.tile_start);
+    tp_tile_count_kernel<<<nch, kT, 0, st>>>(n, npts, min_points, w.tile_start, w.chunk_b, scal);
+    tp_scan_kernel<<<1, kScanT, 0, st>>>(nch, w.chunk_b, &scal->n_samples);
+    tp_rows_emit_kernel<<<nch, kT, 0, st>>>(n, npts, min_points, sample_cap, w.tile_start, w.chunk_b, scal, samples, header);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

@@ -1,5 +1,7 @@
 // pn2_wg.h -- the workgroup primitives of the data-path kernels (pn2_scene.hip, pn2_dataset.hip, pn2_frame.hip, pn2_tile.hip,
-// pn2_store.hip) and the workspace carving of their host halves.  One copy of each.
+// pn2_store.hip, pn2_cluster.hip, pn2_plane.hip) and the workspace carving of every host half that takes a workspace (those, and
+// pn2_text.hip, pn2_scene_io.hip, pn2_grid_knn.h, pn2_fps_bucket.hip, pn2_augment.hip; pn2_sort.h carves the radix sort's share).
+// One copy of each.
 //
 // W is the number of waves of the CALLING workgroup (its threads / 64): a template parameter, because every file names its own
 // thread count.  Every thread of the workgroup must reach a call (they hold barriers).
@@ -122,9 +124,12 @@ __device__ __forceinline__ bool point_valid(const float* __restrict__ points, co
 // ---- host: workspace carving ---------------------------------------------------------------------------------------------------
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// consecutive 256-byte-aligned pieces of a workspace.  base == nullptr measures: every piece comes back NULL, `used` still grows
+// consecutive 256-byte-aligned pieces of a workspace.  base == nullptr measures: every piece comes back NULL, `used` still grows.
+// Each file has ONE function that runs a carver over a struct of typed pointers; its size query calls it with a null base, its
+// entry point with the caller's workspace and `limit` = the caller's workspace_bytes, and then asks fits().
 struct WsCarver {
     unsigned char* base;
+    size_t limit = ~(size_t)0;
     size_t used = 0;
     template <typename T>
     T* take(size_t count) {
@@ -132,12 +137,5 @@ struct WsCarver {
         used += al256(count * sizeof(T));
         return p;
     }
+    bool fits() const { return used <= limit; }
 };
-
-// the offset of the next piece of `count` elements of T (a layout that is kept as offsets)
-template <typename T>
-inline size_t piece(WsCarver& c, size_t count) {
-    const size_t o = c.used;
-    c.take<T>(count);
-    return o;
-}
