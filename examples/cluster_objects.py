@@ -11,6 +11,11 @@ chain of points of their label joins them in steps of at most --eps -- and the r
     <out>/objects.png   the scene from above, every object in a colour of its own, everything else grey (pn2.render)
 with one line per class and its object count on the terminal.  --synthetic N makes N points in tight blobs of known sizes on a
 lattice (synthetic(N) below), so the expected output is known.
+--boxes describes every object as well (pn2.describe_clusters, upright: the box turns about the z axis only): each object's line
+gains nine columns, center_x center_y center_z (the box centre) length width height (the box edges along its axes) yaw (radians,
+the heading of the long axis) centroid_x centroid_y (repr-exact floats), and
+    <out>/boxes.png     objects.png with every object's box drawn around it in the object's colour (pn2.box_wireframe)
+is written too.
 --ground THR takes the ground out first: pn2.segment_plane with the axis (0,0,1) and a normal within 15 degrees of it
 (--ground-trials hypotheses), its inliers are left out of the clustering, and objects.txt begins with the line
     ground count a b c d                        the exact, unnormalised plane a*x + b*y + c*z + d = 0 (repr-exact floats)
@@ -53,6 +58,12 @@ def object_lines(clusters):
     return ["%d %d %d %s" % (i, label, size, " ".join(repr(float(v)) for v in box)) for i, (label, size, box) in enumerate(rows)]
 
 
+def box_columns(boxes):
+    """-> per object the columns --boxes appends to its line of objects.txt"""
+    rows = torch.cat([boxes.center, boxes.extent, boxes.yaw()[:, None], boxes.centroid[:, :2]], 1).cpu().numpy()
+    return [" ".join(repr(float(v)) for v in row) for row in rows]
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--points", default="", help="scene.pcd or scene.ply")
@@ -64,6 +75,7 @@ def main():
     parser.add_argument("--max_points", type=int, default=0, help="0: no upper bound")
     parser.add_argument("--ground", type=float, default=0.0, help="remove the ground first: points within this distance of it")
     parser.add_argument("--ground-trials", type=int, default=1024, help="RANSAC hypotheses for --ground")
+    parser.add_argument("--boxes", action="store_true", help="describe every object: oriented box columns and boxes.png")
     parser.add_argument("--out", default="result/objects")
     parser.add_argument("--width", type=int, default=1280)
     parser.add_argument("--height", type=int, default=960)
@@ -96,11 +108,25 @@ def main():
         print("class %d: %d objects" % (c, per_class[c] if c < len(per_class) else 0))
     print("%d objects, %d of %d points in one" % (clusters.count, int((clusters.ids >= 0).sum()), len(points)))
 
+    lines = object_lines(clusters)
+    boxes = None
+    if flags.boxes:
+        boxes = pn2.describe_clusters(points, clusters, upright=True)
+        lines = [line + " " + more for line, more in zip(lines, box_columns(boxes))]
+
     os.makedirs(flags.out, exist_ok=True)
     with open(os.path.join(flags.out, "objects.txt"), "w") as f:
-        f.writelines(line + "\n" for line in ground_lines + object_lines(clusters))
-    image = pn2.render.render_colors(points, pn2.cluster_colors(clusters.ids), "top", flags.width, flags.height, size=2)
+        f.writelines(line + "\n" for line in ground_lines + lines)
+    colors = pn2.cluster_colors(clusters.ids)
+    renderer = pn2.render.Renderer(flags.width, flags.height, 2, device=points.device)
+    view = pn2.render.fit_view(points, "top", flags.width, flags.height)
+    image = pn2.render.render_colors(points, colors, view, renderer=renderer)
     pn2.render.write_png(os.path.join(flags.out, "objects.png"), image)
+    if boxes is not None:  # the same z-buffer: the edges go in behind the cloud's indices, in their objects' colours
+        edges, owner = pn2.box_wireframe(boxes)
+        renderer.splat(edges, view, index0=len(points))
+        image = renderer.image(torch.cat([colors, pn2.cluster_colors(owner)]))
+        pn2.render.write_png(os.path.join(flags.out, "boxes.png"), image)
     print("Output written to", flags.out)
 
 

@@ -1284,6 +1284,68 @@ int pn2_cluster_stats(int n, int nclusters, const float *points, const int *labe
                       int *label, float *bbox, void *stream);
 int pn2_cluster_colors(int n, const int *ids, uint8_t *rgb, void *stream);
 
+/* Object description (csrc/pn2_describe.hip): per cluster its member count, centroid, principal axes, variances and the oriented
+ * box around its members (what Open3D calls get_oriented_bounding_box), and the boxes drawn as points.  tests/describe_ref.py is
+ * the numpy model of the rules and is compared for equality: every accumulation is an integer sum or an integer minimum / maximum,
+ * and everything else is float64 in the written association (the library is built without contraction; sqrt and / are correctly
+ * rounded), so nothing in a result depends on the order in which threads arrive.
+ *
+ *   points (n,3) float32; ids (n) int32.  Point i is a MEMBER of cluster c when ids[i] == c, 0 <= c < nclusters, and its three
+ *   coordinates are finite.  Every other point is ignored.  pn2_cluster_describe computes its own box from the members: it does
+ *   not depend on pn2_cluster_stats.
+ *
+ * Per cluster with m >= 1 members:
+ *   BOX AND LATTICE.  o = the per-axis minimum of the members' coordinates, widened to float64.  E = the maximum over the axes
+ *     of (double)max - (double)min.  Q = min(20, (62 - bitlen(m)) >> 1), bitlen = the number of bits of m.  If E > 0:
+ *     E = f * 2^x with f in [0.5, 1) (frexp) and h = 2^(x-Q); if E == 0: x = Q, h = 1.  Per member and axis
+ *     q = (long long)rint(((double)p - o) / h), ties to even; the division is exact (h is a power of two); 0 <= q <= 2^Q.
+ *   MOMENTS (int64).  S_a = sum q_a, S_ab = sum q_a * q_b for ab in xx, xy, xz, yy, yz, zz; by the choice of Q every sum is below
+ *     2^62.  Integer adds only.
+ *   CENTROID.  centroid_a = o_a + ((double)S_a / (double)m) * h.
+ *   COVARIANCE in lattice units.  A_ab = (double)S_ab / (double)m - ((double)S_a / (double)m) * ((double)S_b / (double)m).
+ *   AXES, upright = 0.  Eight cyclic Jacobi sweeps over the pairs (p,r) = (0,1), (0,2), (1,2), k the third index, V = identity at
+ *     the start.  A pair with A_pr == 0 is skipped.  Otherwise
+ *       theta = (A_rr - A_pp) / (2 * A_pr);  t = sigma / (|theta| + sqrt(theta * theta + 1)), sigma = +1 if theta >= 0 else -1;
+ *       c = 1 / sqrt(t * t + 1);  s = t * c;
+ *       A_pp -= t * A_pr;  A_rr += t * A_pr;  A_pr = 0;
+ *       A_kp' = c * A_kp - s * A_kr;  A_kr' = s * A_kp + c * A_kr;
+ *       for each row i of V:  V_ip' = c * V_ip - s * V_ir;  V_ir' = s * V_ip + c * V_ir.
+ *     (A theta * theta that overflows gives t = +-0 by IEEE rules: intended.)  The eigenpairs (diagonal entry, column of V) are
+ *     sorted by descending diagonal, equal values keep the lower column first.  a0 and a1 are the first two columns, each negated
+ *     if its component of largest magnitude (the first among equals) is negative.  a2 = a0 x a1, each component as u*v - w*z.
+ *   AXES, upright = 1.  The same single rotation on the pair (0,1) only; the two in-plane eigenpairs sorted the same way; a0 takes
+ *     the sign rule; a1 = (-a0_y, a0_x, 0); a2 = (0,0,1); lambda_2 = A_zz.
+ *   VARIANCES.  variance_k = lambda_k * (h * h).
+ *   EXTENTS (a second pass over the points).  Per member d = (double)p - centroid and t_k = (a_k0 * d_x + a_k1 * d_y) + a_k2 * d_z;
+ *     lo_k, hi_k = the minimum and maximum over the members, taken as unsigned 64-bit atomic min / max on the order-preserving
+ *     image of the double (-0.0 sorts below +0.0).
+ *   BOX CENTRE.  center_a = centroid_a + ((a_0a * g_0 + a_1a * g_1) + a_2a * g_2), g_k = 0.5 * (lo_k + hi_k).
+ *
+ * pn2_cluster_describe: moments (nclusters,12) int64: [0] m, [1..3] S_x S_y S_z, [4..9] S_xx S_xy S_xz S_yy S_yz S_zz, [10] Q,
+ *   [11] x; desc (nclusters,24) float64: [0..2] centroid, [3..5] variances, [6..14] a0, a1, a2, [15..17] lo, [18..20] hi, [21..23]
+ *   box centre.  A cluster without members gets a zero moments row and a desc row of NaNs.
+ *   workspace: *bytes of pn2_cluster_describe_workspace_size(nclusters, bytes) (a host query like pn2_cluster_workspace_size:
+ *   PN2_EINVAL for nclusters <= 0, PN2_ENULL without bytes), 256-byte aligned; it need not be cleared.  Seven launches: three
+ *   passes over the points (box and count, moments, extents), each of which reduces inside the wave before it issues an atomic,
+ *   and one thread per cluster in between.  No allocation, no host read, no synchronisation.
+ *   Refusals, nothing launched, in this order: PN2_EINVAL (n or nclusters <= 0, upright not 0 or 1), PN2_ERANGE (nclusters > n),
+ *   PN2_ENULL (any pointer NULL), PN2_EINVAL (points or ids not 4-byte aligned, moments or desc not 8-byte aligned, a workspace
+ *   not 256-byte aligned or too small), PN2_EUNSUP (a capturing stream: it would be capturable, but nothing in the project
+ *   captures it yet, so the refusal stands until a later change lifts it together with a capture test).
+ *
+ * pn2_box_wireframe: the 12 edges of every box of desc as per_edge points each: points (nclusters*12*per_edge, 3) float32, owner
+ *   (nclusters*12*per_edge) int32 = the cluster index, in the order cluster, edge, sample.  Corner j (bits j0 j1 j2) is
+ *   centroid + ((a_0 * e_0 + a_1 * e_1) + a_2 * e_2), e_k = hi_k if bit k of j is set, else lo_k.  The edges join corners that
+ *   differ in one bit: for k = 0, 1, 2 and for the four values of the other two bits in ascending order, from the corner A without
+ *   bit k to the corner B with it.  Sample s is A + (B - A) * ((double)s / (double)(per_edge - 1)), rounded to float32.  A row of
+ *   NaNs gives NaN points, which the renderer culls.  One launch, capturable.  PN2_EINVAL: nclusters <= 0, per_edge < 2;
+ *   PN2_ERANGE: nclusters * 12 * per_edge >= 2^31; PN2_ENULL: a NULL pointer; PN2_EINVAL: desc not 8-byte, points or owner not
+ *   4-byte aligned. */
+int pn2_cluster_describe_workspace_size(int nclusters, unsigned long long *bytes);
+int pn2_cluster_describe(int n, int nclusters, const float *points, const int *ids, int upright, long long *moments, double *desc,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int pn2_box_wireframe(int nclusters, const double *desc, int per_edge, float *points, int *owner, void *stream);
+
 /* Plane segmentation (csrc/pn2_plane.hip): the dominant plane of a cloud by random sample consensus (RANSAC) -- the ground of a
  * LiDAR frame, a road, a floor, a facade.  tests/plane_ref.py is the numpy model of the rules and is compared for equality: the
  * decisions are float64 comparisons in a fixed order (the library is built without contraction) and everything after them is

@@ -1,7 +1,7 @@
 // pn2_ordered.h -- float <-> unsigned key with the same order: k(a) < k(b) <=> a < b for every pair of non-NaN values (-0.0 sorts
 // directly below +0.0).  Minima / maxima go through integer atomics on it, and a radix sort on it is a sort by value.  One copy:
-//   float64 <-> 64 bits: pn2_dataset.hip, pn2_scene.hip, pn2_store.hip, pn2_tile.hip;
-//   float32 <-> 32 bits: pn2_bbox.h (pn2_grid_knn.h, pn2_fps_bucket.hip), pn2_cluster.hip, pn2_render.hip.
+//   float64 <-> 64 bits: pn2_dataset.hip, pn2_scene.hip, pn2_store.hip, pn2_tile.hip, pn2_describe.hip;
+//   float32 <-> 32 bits: pn2_bbox.h (pn2_grid_knn.h, pn2_fps_bucket.hip), pn2_cluster.hip, pn2_render.hip, pn2_describe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

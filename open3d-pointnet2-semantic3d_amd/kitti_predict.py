@@ -11,7 +11,7 @@ the Predictor is used as it is.  After the frame's construction nothing on this 
 """
 import torch
 
-from .cluster import _device_of, euclidean_clusters
+from .cluster import _device_of, describe_clusters, euclidean_clusters
 from .plane import segment_plane
 from .predict import Predictor, _on_device
 
@@ -61,6 +61,12 @@ class PredictInterpolator:
             dense_labels = torch.where(exclude, torch.full_like(dense_labels, -1), dense_labels)
         return euclidean_clusters(file_data.points, eps, labels=dense_labels, classes=classes, min_points=min_points,
                                   max_points=max_points)
+
+    def describe_objects(self, file_data, clusters, upright=True):
+        """(extension) what each object of objects_for_frame looks like: cluster.describe_clusters over file_data.points
+        -> cluster.Boxes: centroid, axes, oriented box and size per object.  upright (the default here): a vehicle stands on the
+        road, so the box turns about the z axis only and Boxes.yaw() is its heading."""
+        return describe_clusters(file_data.points, clusters, upright=upright)
 
     def ground_for_frame(self, file_data, distance_threshold, trials=1024, seed=0, max_angle=15.0, dense_labels=None, classes=None):
         """(extension) the ground of file_data.points: plane.segment_plane with the axis (0,0,1), the normal within max_angle
