@@ -106,31 +106,6 @@ __device__ __forceinline__ bool wave_peel(bool in, int c, Peel peel, F&& reduce)
 }
 
 template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T wave_min(T v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const T t = __shfl_xor(v, o);
-        v = t < v ? t : v;
-    }
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T wave_max(T v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const T t = __shfl_xor(v, o);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-
-template <typename T>
 __device__ __forceinline__ void atomic_add(T* p, T v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 template <typename T>
 __device__ __forceinline__ void atomic_min(T* p, T v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -178,9 +153,9 @@ describe_box_kernel(int n, int nclusters, Peel peel, const float* __restrict__ p
     const bool in = c >= 0;
     const unsigned k0 = ordered_key32(p[0]), k1 = ordered_key32(p[1]), k2 = ordered_key32(p[2]);
     const bool self = wave_peel(in, c, peel, [&](int v, bool mine) {
-        const unsigned l0 = wave_min(mine ? k0 : 0xFFFFFFFFu), l1 = wave_min(mine ? k1 : 0xFFFFFFFFu),
-                       l2 = wave_min(mine ? k2 : 0xFFFFFFFFu);
-        const unsigned h0 = wave_max(mine ? k0 : 0u), h1 = wave_max(mine ? k1 : 0u), h2 = wave_max(mine ? k2 : 0u);
+        const unsigned l0 = pn2_wave_all_min(mine ? k0 : 0xFFFFFFFFu), l1 = pn2_wave_all_min(mine ? k1 : 0xFFFFFFFFu),
+                       l2 = pn2_wave_all_min(mine ? k2 : 0xFFFFFFFFu);
+        const unsigned h0 = pn2_wave_all_max(mine ? k0 : 0u), h1 = pn2_wave_all_max(mine ? k1 : 0u), h2 = pn2_wave_all_max(mine ? k2 : 0u);
         const int count = (int)__popcll(__ballot(mine));
         Acc* a = acc + v;
         // lanes 0 .. 5: the six consecutive box words; lane 6: the count
@@ -249,7 +224,7 @@ describe_moments_kernel(int n, int nclusters, Peel peel, const float* __restrict
         long long out = 0;
 #pragma unroll
         for (int j = 0; j < 9; ++j) {
-            const long long r = wave_sum(mine ? s[j] : 0ll);
+            const long long r = pn2_wave_all_sum(mine ? s[j] : 0ll);
             out = lane == j ? r : out;
         }
         if (lane < 9) atomic_add(&acc[v].s[lane], out);  // one wave-instruction, nine consecutive words of one row
@@ -385,7 +360,7 @@ describe_extent_kernel(int n, int nclusters, Peel peel, const float* __restrict_
         unsigned long long out = 0ull;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const unsigned long long lo = wave_min(mine ? k[j] : ~0ull), hi = wave_max(mine ? k[j] : 0ull);
+            const unsigned long long lo = pn2_wave_all_min(mine ? k[j] : ~0ull), hi = pn2_wave_all_max(mine ? k[j] : 0ull);
             out = lane == j ? lo : (lane == 3 + j ? hi : out);
         }
         Ext* e = ext + v;

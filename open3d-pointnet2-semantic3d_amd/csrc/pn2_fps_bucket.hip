@@ -46,8 +46,6 @@ inline void fb_ws_layout(int b, int n, unsigned char* base, FbWs* w) {
     w->total = c.used;
 }
 
-__device__ __forceinline__ unsigned fb_tiekey(int k) { return (((unsigned)k & 511u) << 22) | ((unsigned)k >> 9); }
-
 __device__ __forceinline__ unsigned fb_spread10(unsigned v) {  // 10 bits -> every third bit
     v &= 0x3ffu;
     v = (v | (v << 16)) & 0x030000ffu;
@@ -112,17 +110,6 @@ fb_gather_kernel(int n, int npad, const float* __restrict__ xyz_all, const int* 
     td[(size_t)bi * npad + j] = 1e38f;
 }
 
-// 64-bit max over the wave (uniform result)
-__device__ __forceinline__ unsigned long long fb_wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
-        const unsigned long long t = ((unsigned long long)hi << 32) | lo;
-        v = t > v ? t : v;
-    }
-    return v;
-}
-
 template <int MODE>
 __global__ void __launch_bounds__(kFbThreads)
 fps_bucket_kernel(int n, int npad, int m, const float* __restrict__ xyz_all, const float4* __restrict__ sorted_all,
@@ -150,13 +137,7 @@ fps_bucket_kernel(int n, int npad, int m, const float* __restrict__ xyz_all, con
     for (int bk = wave; bk < nb; bk += kFbWaves) {
         const float4 p = sorted[bk * 64 + lane];
         float lo[3] = {p.x, p.y, p.z}, hi[3] = {p.x, p.y, p.z};
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                lo[a] = fminf(lo[a], __shfl_xor(lo[a], o));
-                hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o));
-            }
+        pn2_wave_all_box(lo, hi);
         if (lane == 0) {
             bb[0][bk] = lo[0]; bb[1][bk] = lo[1]; bb[2][bk] = lo[2];
             bb[3][bk] = hi[0]; bb[4][bk] = hi[1]; bb[5][bk] = hi[2];
@@ -207,8 +188,8 @@ fps_bucket_kernel(int n, int npad, int m, const float* __restrict__ xyz_all, con
             const float tn = fminf(d, told);  // min(d, td) tf_sampling.cu:151 (both >= +0, never NaN by contract)
             td[bk * 64 + lane] = tn;
             const unsigned long long key =
-                ((unsigned long long)__float_as_uint(tn) << 32) | (unsigned)(~fb_tiekey(__float_as_int(p.w)));
-            const unsigned long long best = fb_wave_max_u64(key);
+                ((unsigned long long)__float_as_uint(tn) << 32) | (unsigned)(~pn2_fps_tiekey(__float_as_int(p.w)));
+            const unsigned long long best = pn2_wave_all_max(key);
             if (key == best) {  // one lane (padding copies share a key: identical writes)
                 bkey[bk] = best;
                 bwin[bk] = p;
@@ -227,7 +208,7 @@ fps_bucket_kernel(int n, int npad, int m, const float* __restrict__ xyz_all, con
                 tbest = mykey[u] > tbest ? mykey[u] : tbest;
             }
         }
-        const unsigned long long wbest = fb_wave_max_u64(tbest);
+        const unsigned long long wbest = pn2_wave_all_max(tbest);
         if (lane == 0) atomicMax(&slots[slot], wbest);
         __syncthreads();
         const unsigned long long win = slots[slot];
@@ -322,13 +303,7 @@ fps_bucket_lazy_kernel(int n, int npad, int m, const float* __restrict__ xyz_all
     for (int bk = wave; bk < nb; bk += kFbWaves) {
         const float4 p = sorted[bk * 64 + lane];
         float lo[3] = {p.x, p.y, p.z}, hi[3] = {p.x, p.y, p.z};
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                lo[a] = fminf(lo[a], __shfl_xor(lo[a], o));
-                hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o));
-            }
+        pn2_wave_all_box(lo, hi);
         if (lane == 0) {
             bb[0][bk] = lo[0]; bb[1][bk] = lo[1]; bb[2][bk] = lo[2];
             bb[3][bk] = hi[0]; bb[4][bk] = hi[1]; bb[5][bk] = hi[2];
@@ -389,14 +364,7 @@ fps_bucket_lazy_kernel(int n, int npad, int m, const float* __restrict__ xyz_all
             if (kFbThreads * u >= nb) break;  // uniform
             const int bk = tid + kFbThreads * u;
             bmh[u] = bk < nb ? bmaxhi[bk] : -1;
-            int r = bmh[u];
-            asm volatile(
-                "s_nop 1\n"
-                "v_max_i32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-                "v_max_i32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-                "v_max_i32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-                "v_max_i32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-                : "+v"(r));
+            const int r = pn2_row_imax(bmh[u]);
             if ((lane & 15) == 15) sbmax[bk >> 4] = r;
         }
         if (tid < kFlSupers) smask[tid] = 0ull;
@@ -489,7 +457,7 @@ fps_bucket_lazy_kernel(int n, int npad, int m, const float* __restrict__ xyz_all
                     }
                     if (B.msk[u] != 0ull) {  // (a bucket listed only because it holds candidates keeps its td and its maximum)
                         if (hi != hi0) td[B.bks[u] * 64 + lane] = __int_as_float(hi);
-                        const int wh = pn2fps::wave_imax_from(hi);
+                        const int wh = pn2_wave_imax_from(hi);
                         if (lane == 0) bmaxhi[B.bks[u]] = wh;
                     }
                     if (hi >= tau_hi) {  // candidates of this phase (rare lanes)
@@ -497,7 +465,7 @@ fps_bucket_lazy_kernel(int n, int npad, int m, const float* __restrict__ xyz_all
                         const unsigned one = 1u;
                         asm volatile("ds_add_rtn_u32 %0, %1, %2\n s_waitcnt lgkmcnt(0)" : "=v"(slot_i) : "v"(laddr), "v"(one) : "memory");
                         if (slot_i < (unsigned)pn2fps::kLazyCap) {
-                            cand_key[slot_i] = ((unsigned long long)(unsigned)hi << 32) | (unsigned)(~fb_tiekey(__float_as_int(B.pt[u].w)));
+                            cand_key[slot_i] = ((unsigned long long)(unsigned)hi << 32) | (unsigned)(~pn2_fps_tiekey(__float_as_int(B.pt[u].w)));
                             cand_xyz[slot_i] = B.pt[u];
                         }
                     }
@@ -538,7 +506,7 @@ fps_bucket_lazy_kernel(int n, int npad, int m, const float* __restrict__ xyz_all
                     const int bk = tid + kFbThreads * u;
                     if (bk < nb) { const int v = bmaxhi[bk]; mx = v > mx ? v : mx; }
                 }
-                mx = pn2fps::wave_imax_from(mx);
+                mx = pn2_wave_imax_from(mx);
                 if (lane == 0) atomicMax(&ctrl[3], mx);
             }
             __syncthreads();
@@ -560,8 +528,8 @@ fps_bucket_lazy_kernel(int n, int npad, int m, const float* __restrict__ xyz_all
                     const int bk = __builtin_amdgcn_readfirstlane((int)wl_bk[e]);
                     const float4 p = sorted[bk * 64 + lane];
                     const int hi = __float_as_int(td[bk * 64 + lane]);
-                    const unsigned lo = hi == G ? (unsigned)(~fb_tiekey(__float_as_int(p.w))) : 0u;
-                    const unsigned wl = pn2fps::wave_umax_all(lo);
+                    const unsigned lo = hi == G ? (unsigned)(~pn2_fps_tiekey(__float_as_int(p.w))) : 0u;
+                    const unsigned wl = pn2_wave_all_max(lo);
                     if (lane == 0) {
                         const unsigned long long comp = ((unsigned long long)(unsigned)G << 32) | wl;
                         const unsigned saddr = (unsigned)(size_t)(fl_smem) + 32u;  // fslot
@@ -586,7 +554,7 @@ fps_bucket_lazy_kernel(int n, int npad, int m, const float* __restrict__ xyz_all
             } else if (lane == 0) {
                 const unsigned long long key = *fslot;
                 chi = (int)(unsigned)(key >> 32); clo = (unsigned)key;
-                const int k = pn2fps::untiekey(~clo);
+                const int k = pn2_fps_untiekey(~clo);
                 cx = xyz[k * 3 + 0]; cy = xyz[k * 3 + 1]; cz = xyz[k * 3 + 2];
             }
             int maxp = use_list ? pn2fps::kLazyCap : 1;

@@ -4,48 +4,6 @@
 
 namespace pn2fps {
 
-// Tie-break of the reference (tf_sampling.cu:153-170: 512-thread strided scan with a strict '>', left-biased tree):
-// among equal distances the lowest (k mod 512, k) wins.  Every point carries ~tiekey(k) in the low word of its 64-bit
-// key (td bits : ~tiekey), so a plain 64-bit max reproduces the reference's order.
-__device__ __forceinline__ unsigned tiekey(int k) { return (((unsigned)k & 511u) << 22) | ((unsigned)k >> 9); }
-__device__ __forceinline__ int untiekey(unsigned key) { return (int)(((key & 0x3FFFFFu) << 9) | (key >> 22)); }
-
-// wave64 max of a 32-bit signed key by fused DPP (one VALU per step; s_nop 1 = the 2 wait states a DPP read needs after
-// a VALU write of the same VGPR), reading the source register in place; uniform result.
-__device__ __forceinline__ int wave_imax_from(int src) {
-    int v;
-    asm volatile(
-        "s_nop 1\n"
-        "v_max_i32_dpp %0, %1, %1 row_shr:1 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n"
-        : "=&v"(v) : "v"(src));
-    return __builtin_amdgcn_readlane(v, 63);
-}
-// wave64 max of an unsigned key by fused DPP (uniform result); the tie paths use it, so clouds with many duplicated rows
-// (every pick of a row that has a twin is a tie) pay 6 VALU instead of 6 cross-lane shuffles per tied pick
-__device__ __forceinline__ unsigned wave_umax_dpp(unsigned src) {
-    unsigned v;
-    asm volatile(
-        "s_nop 1\n"
-        "v_max_u32_dpp %0, %1, %1 row_shr:1 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n s_nop 1\n"
-        "v_max_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n"
-        : "=&v"(v) : "v"(src));
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ unsigned wave_umax_all(unsigned v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)v, o); v = t > v ? t : v; }
-    return v;
-}
-
 constexpr int kLazyCap = 64;  // candidates per phase = lanes of the picking wave
 
 // PHASE B of the lazy multi-pick scheme (see pn2_sampling.hip, fps_lazy_kernel): ONE wave, lane = candidate
@@ -84,9 +42,9 @@ __device__ __forceinline__ int pick_phase(int chi, unsigned clo, float cx, float
     int npick = 0;
     g_first = -1; d_last = 0;
     pk_k = 0; pk_x = pk_y = pk_z = 0.f;
-    const int ck = untiekey(~clo);
+    const int ck = pn2_fps_untiekey(~clo);
     while (npick < maxp) {
-        const int bh = wave_imax_from(chi);
+        const int bh = pn2_wave_imax_from(chi);
         if (bh < lim) break;
         unsigned long long bal = __builtin_amdgcn_ballot_w64(chi == bh);
         if (__builtin_expect(__popcll(bal) != 1, 0)) {
@@ -100,7 +58,7 @@ __device__ __forceinline__ int pick_phase(int chi, unsigned clo, float cx, float
                 const unsigned long long other = __builtin_amdgcn_ballot_w64(chi == bh && (cx != rx || cy != ry || cz != rz));
                 if (lane == 0) tie_note(tt, jbase + npick, bh == 0 || other != 0ull, bh == 0);
             }
-            const unsigned lm = wave_umax_dpp(chi == bh ? clo : 0u);
+            const unsigned lm = pn2_wave_umax_dpp(chi == bh ? clo : 0u);
             bal = __builtin_amdgcn_ballot_w64(chi == bh && clo == lm);
         }
         const int L = __builtin_ctzll(bal);

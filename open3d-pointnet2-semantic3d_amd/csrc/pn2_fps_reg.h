@@ -9,35 +9,6 @@ namespace pn2fpsreg {
 constexpr int kFpsSlotsMax = 16;  // waves per workgroup <= 16
 constexpr int kFpsRegHead = 48;   // fps_reg_kernel: bytes of LDS in front of the cloud copy (key slots + tie record)
 
-__device__ __forceinline__ unsigned fps_tiekey(int k) {
-    return (((unsigned)k & 511u) << 22) | ((unsigned)k >> 9);
-}
-__device__ __forceinline__ int fps_untiekey(unsigned key) {
-    return (int)(((key & 0x3FFFFFu) << 9) | (key >> 22));
-}
-
-// Fused-DPP wave64 reductions on 32-bit keys (one VALU op per step; the s_nop 1
-// are the 2 wait states a DPP read needs after a VALU write of the same VGPR).
-// All distances are >= +0, so their bit patterns order like signed/unsigned ints;
-// the sentinel -1.0f (threads without points) is a negative int.
-__device__ __forceinline__ int wave_imax(int v) {
-    asm volatile(
-        "s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n s_nop 1\n"
-        : "+v"(v));
-    return __builtin_amdgcn_readlane(v, 63);
-}
-__device__ __forceinline__ unsigned wave_umin_all(unsigned v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)v, o); v = t < v ? t : v; }
-    return v;
-}
-
 // Exact 64-bit max of two (td bits : ~tiekey) pairs read as doubles.  The high word is an fp32 pattern in [0, bits(1e38f)]
 // (or bits(-1.0f) for "no point"), so the doubles are finite; pairs with td < 2^-126-ish map to fp64 DENORMALS (high word
 // < 0x00100000), which v_max_f64 orders correctly only because the kernel runs with fp64 denormals enabled -- the
@@ -134,7 +105,7 @@ __device__ __forceinline__ void fps_reg_body(int n, int m, const float* __restri
             px[i] = py[i] = pz[i] = 0.f;
             hi = __float_as_int(-1.0f);  // never selected: a negative double, below every real pair
         }
-        mk[i] = __hiloint2double(hi, (int)~fps_tiekey(k));
+        mk[i] = __hiloint2double(hi, (int)~pn2_fps_tiekey(k));
     }
     if (tid < 4) slots[tid] = 0ull;
     if (TRACK && tid == 0) pn2fps::tie_init(ttl);
@@ -189,7 +160,7 @@ __device__ __forceinline__ void fps_reg_body(int n, int m, const float* __restri
             for (int g = 0; g < w / 2; ++g) tr[g] = fps_dmax(tr[g], tr[w - 1 - g]);
         }
         const int best = __double2hiint(tr[0]);
-        const int wmax = wave_imax(best);
+        const int wmax = pn2_wave_imax(best);
         if constexpr (NT == 64) {
             // one wave: the winner is resolved with a ballot (equal td across lanes: lowest tie key = largest low
             // word); no LDS atomic, no barrier in the round
@@ -197,8 +168,8 @@ __device__ __forceinline__ void fps_reg_body(int n, int m, const float* __restri
             const unsigned lo = (unsigned)__double2loint(tr[0]);
             unsigned wl;
             if (__popcll(bal) == 1) wl = (unsigned)__builtin_amdgcn_readlane((int)lo, __ffsll((long long)bal) - 1);
-            else wl = ~wave_umin_all(best == wmax ? ~lo : 0xFFFFFFFFu);
-            old = fps_untiekey(~wl);
+            else wl = ~pn2_wave_all_min(best == wmax ? ~lo : 0xFFFFFFFFu);
+            old = pn2_fps_untiekey(~wl);
             if (tid == 0) spick[j] = old;
             if constexpr (TRACK) { pw_hi = wmax; pw_lo = wl; }
             continue;
@@ -212,7 +183,7 @@ __device__ __forceinline__ void fps_reg_body(int n, int m, const float* __restri
         }
         __syncthreads();
         const unsigned long long win = slots[slot];
-        old = fps_untiekey(~(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)win));
+        old = pn2_fps_untiekey(~(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)win));
         if constexpr (TRACK) { pw_hi = (int)(unsigned)(win >> 32); pw_lo = (unsigned)win; }
         const int nxt = slot == 2 ? 0 : slot + 1;          // (j+1) % 3
         if (tid == 0) {

@@ -529,7 +529,7 @@ __device__ __forceinline__ void bqg_build(const BqgLds& L, int n, float radius, 
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
+        for (int o = 32; o > 0; o >>= 1) {  // pn2_wave_all_box in place: the helper reschedules the ball-query kernels
             mn[a] = fminf(mn[a], __shfl_xor(mn[a], o));
             mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o));
         }

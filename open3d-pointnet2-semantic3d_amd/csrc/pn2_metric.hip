@@ -124,8 +124,7 @@ label_confusion_kernel(long long n, int C, const LabelT* __restrict__ gt, const 
         }
     }
     if (dropped) {
-#pragma unroll
-        for (int o = PN2_WAVE / 2; o >= 1; o >>= 1) my_dropped += __shfl_xor(my_dropped, o);
+        my_dropped = pn2_wave_all_sum(my_dropped);
         if ((threadIdx.x & (PN2_WAVE - 1)) == 0 && my_dropped) atomicAdd(&s_dropped, my_dropped);
     }
     __syncthreads();

@@ -25,68 +25,34 @@ namespace {
 using namespace pn2fpsreg;
 
 using pn2fps::kLazyCap;
-using pn2fps::wave_imax_from;
-using pn2fps::wave_umax_all;
-
-// max over lanes 0..15 (row 0), result from lane 15
-__device__ __forceinline__ int row0_imax(int v) {
-    asm volatile(
-        "s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        : "+v"(v));
-    return __builtin_amdgcn_readlane(v, 15);
-}
-__device__ __forceinline__ unsigned row0_umin(unsigned v) {
-    asm volatile(
-        "s_nop 1\n"
-        "v_min_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_min_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_min_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_min_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        : "+v"(v));
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 15);
-}
 
 // Merge the per-wave candidates {dist bits, tiekey}; returns the winning index (uniform).
 // Value-only max first; the 64-bit order (dist desc, tiekey asc) is only resolved on ties.
 __device__ __forceinline__ int fps_merge_waves(const uint2* slots, int nwaves, int lane) {
     uint2 sv = make_uint2(0x80000000u, 0xFFFFFFFFu);  // "no candidate": negative as int
     if (lane < nwaves) sv = slots[lane];
-    const int vmax = row0_imax((int)sv.x);
+    const int vmax = pn2_row0_imax((int)sv.x);
     const unsigned long long tie = __ballot((int)sv.x == vmax) & 0xFFFFull;
     unsigned key;
     if (__popcll(tie) == 1) {
         key = (unsigned)__builtin_amdgcn_readlane((int)sv.y, __ffsll((long long)tie) - 1);
     } else {
-        key = row0_umin((int)sv.x == vmax ? sv.y : 0xFFFFFFFFu);
+        key = pn2_row0_umin((int)sv.x == vmax ? sv.y : 0xFFFFFFFFu);
     }
-    return fps_untiekey(key);
+    return pn2_fps_untiekey(key);
 }
 
 // Generic per-wave candidate from a per-thread (best, bestk) pair (used by the streaming kernel).
 __device__ __forceinline__ uint2 fps_wave_candidate(float best, int bestk) {
     const int bits = __float_as_int(best);  // -1.0f sentinel is negative
-    const int wmax = wave_imax(bits);
+    const int wmax = pn2_wave_imax(bits);
     if (wmax < 0) return make_uint2(0x80000000u, 0xFFFFFFFFu);
     const unsigned long long mask = __ballot(bits == wmax);
     const int src = __ffsll((long long)mask) - 1;  // lowest lane = lowest residue (NT % 512 == 0)
     const int kw = __builtin_amdgcn_readlane(bestk, src);
-    return make_uint2((unsigned)wmax, fps_tiekey(kw));
+    return make_uint2((unsigned)wmax, pn2_fps_tiekey(kw));
 }
 
-__device__ __forceinline__ float wave_fmin_all(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_fmax_all(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 // fps_reg_kernel: pn2fpsreg::fps_reg_body on cloud blockIdx.x, after the nested-sampling shortcut
 template <int NT, int PPT, int MODE, bool LDS_XYZ, bool TRACK>
 __global__ void __launch_bounds__(NT)
@@ -190,7 +156,7 @@ __device__ __forceinline__ void fps_lazy_setup(int n, int wi, const float* __res
         }
     }
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { lo[a] = wave_fmin_all(lo[a]); hi[a] = wave_fmax_all(hi[a]); }
+    for (int a = 0; a < 3; ++a) { lo[a] = pn2_wave_all(lo[a], Pn2OpFmin()); hi[a] = pn2_wave_all(hi[a], Pn2OpFmax()); }
     if (lane == 0) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) { bbw[wave * 6 + a] = lo[a]; bbw[wave * 6 + 3 + a] = hi[a]; }
@@ -274,14 +240,14 @@ __device__ __forceinline__ void fps_lazy_setup(int n, int wi, const float* __res
             const int k = perm[p];
             const float4 q = sxyz[k];
             px[i] = q.x; py[i] = q.y; pz[i] = q.z;
-            mk[i] = __hiloint2double(__float_as_int(1e38f), (int)~fps_tiekey(k));  // tf_sampling.cu:124-126
+            mk[i] = __hiloint2double(__float_as_int(1e38f), (int)~pn2_fps_tiekey(k));  // tf_sampling.cu:124-126
             l0 = h0 = q.x; l1 = h1 = q.y; l2 = h2 = q.z;
         } else {
             px[i] = py[i] = pz[i] = 0.f;
             mk[i] = __hiloint2double(__float_as_int(-1.0f), 0);  // no point: a negative high word, below every real key
         }
-        l0 = wave_fmin_all(l0); l1 = wave_fmin_all(l1); l2 = wave_fmin_all(l2);
-        h0 = wave_fmax_all(h0); h1 = wave_fmax_all(h1); h2 = wave_fmax_all(h2);
+        l0 = pn2_wave_all(l0, Pn2OpFmin()); l1 = pn2_wave_all(l1, Pn2OpFmin()); l2 = pn2_wave_all(l2, Pn2OpFmin());
+        h0 = pn2_wave_all(h0, Pn2OpFmax()); h1 = pn2_wave_all(h1, Pn2OpFmax()); h2 = pn2_wave_all(h2, Pn2OpFmax());
         if (lane / PP == i) { bx0 = l0; by0 = l1; bz0 = l2; bx1 = h0; by1 = h1; bz1 = h2; }
     }
     __syncthreads();  // perm is dead from here
@@ -410,18 +376,18 @@ fps_lazy_kernel(int n, int m, const float* __restrict__ xyz_all, int ld, int* __
         if (!use_list) {
             // empty or overflowing list (~1 phase in 8): ONE pick from the NW per-wave maxima instead (the global maximum is
             // one of them).  Every wave publishes its own maximum key; one more barrier.
-            const int wh = wave_imax(best);
+            const int wh = pn2_wave_imax(best);
             const unsigned long long bal = __ballot(best == wh);
             unsigned wl;
             if (__popcll(bal) == 1) wl = (unsigned)__builtin_amdgcn_readlane((int)bl, __ffsll((long long)bal) - 1);
-            else wl = wave_umax_all(best == wh ? bl : 0u);  // equal td across lanes: lowest tie key = largest low word
+            else wl = pn2_wave_all_max(best == wh ? bl : 0u);  // equal td across lanes: lowest tie key = largest low word
             if (lane == 0) wcand[wave] = ((unsigned long long)(unsigned)wh << 32) | wl;
             if (track) {
                 // ties INSIDE the wave are invisible in its published maximum: class 0 = my maximum is unique in my rows,
                 // 1 = shared only by points coinciding with my winner, 2 = shared by a point elsewhere
                 int cls = 0;
                 if (wh >= 0) {
-                    const float4 wq = sxyz[fps_untiekey(~wl)];
+                    const float4 wq = sxyz[pn2_fps_untiekey(~wl)];
                     int ct = 0;
                     unsigned long long oth = 0ull;
 #pragma unroll
@@ -444,7 +410,7 @@ fps_lazy_kernel(int n, int m, const float* __restrict__ xyz_all, int ld, int* __
             else if (lane < NW) key = wcand[lane];
             int chi = (int)(unsigned)(key >> 32);
             const unsigned clo = (unsigned)key;
-            int ck = fps_untiekey(~clo);
+            int ck = pn2_fps_untiekey(~clo);
             if (chi < 0) ck = 0;
             const float4 cq = sxyz[ck];
             const int limit = use_list ? tau_hi : (int)0x80000000;

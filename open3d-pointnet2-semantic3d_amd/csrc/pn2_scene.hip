@@ -106,10 +106,7 @@ __global__ void voxel_minmax_kernel(int n, const double* __restrict__ pts, doubl
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
 #pragma unroll
         for (int a = 0; a < 3; ++a) { const double v = pts[i * 3 + a]; lo[a] = fmin(lo[a], v); hi[a] = fmax(hi[a], v); }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { lo[a] = fmin(lo[a], __shfl_xor(lo[a], o)); hi[a] = fmax(hi[a], __shfl_xor(hi[a], o)); }
+    pn2_wave_all_box(lo, hi);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0)
 #pragma unroll

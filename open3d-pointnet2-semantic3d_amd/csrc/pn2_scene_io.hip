@@ -32,8 +32,7 @@ format_count_kernel(const int* __restrict__ values, int nrows, int ncols, int* _
     __shared__ int wsum[kFmtT / 64];
     const int row = blockIdx.x * kFmtT + threadIdx.x;
     int c = row < nrows ? row_chars(values + (size_t)row * ncols, ncols) : 0;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o);
+    c = pn2_wave_all_sum(c);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) wg_total[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];

@@ -98,12 +98,7 @@ ingest_gather_kernel(int n, const int* __restrict__ perm, const double* __restri
     const unsigned long long anybad = __ballot(bad_label);
     if (lane == 0 && anybad != 0ull) atomicOr(&scal->flags, (unsigned)FLAG_LABEL);
     // z range
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned long long a = __shfl_xor(kmin, o), b = __shfl_xor(kmax, o);
-        kmin = a < kmin ? a : kmin;
-        kmax = b > kmax ? b : kmax;
-    }
+    kmin = pn2_wave_all_min(kmin); kmax = pn2_wave_all_max(kmax);
     if (lane == 0) { s_min[wave] = kmin; s_max[wave] = kmax; }
     __syncthreads();
     if (tid == 0) {  // every workgroup holds at least one live row

@@ -44,8 +44,7 @@ text_count_kernel(const unsigned char* __restrict__ text, int nbytes, int* __res
     __shared__ int wsum[kIdxT / 64];
     const int p = blockIdx.x * kTile + threadIdx.x * 16;
     int c = __popc(newline_mask(text, p, nbytes));
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o);
+    c = pn2_wave_all_sum(c);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) tile_count[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];

@@ -16,20 +16,6 @@ constexpr int kNnList = 32;    // per-query candidate list (LDS)
 
 struct NnPoint { float x, y, z; };
 
-// wave64 maximum of non-negative floats (as int bits), uniform result
-__device__ __forceinline__ int nn_wave_imax(int v) {
-    asm volatile(
-        "s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n s_nop 1\n"
-        "v_max_i32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n s_nop 1\n"
-        : "+v"(v));
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
 // v_min_f32 without the canonicalising v_max the compiler adds for llvm.minnum (operands are FMA results /
 // +inf, never signalling NaNs)
 __device__ __forceinline__ float nn_fmin(float a, float b) {
@@ -215,7 +201,7 @@ __device__ __forceinline__ void three_nn_wave(int n, int m, const float* __restr
         continue;
     }
     // E = 64 u R^2 (rounded up)
-    const float R = fmaxf(__int_as_float(nn_wave_imax(__float_as_int(rc))), rq);
+    const float R = fmaxf(__int_as_float(pn2_wave_imax(__float_as_int(rc))), rq);
     const float E3 = R * R * (3.0f * 64.0f * 5.9604645e-8f * 1.001f);
     // transposed selection: lane (g = lane>>3, part = lane&7) takes 8 of query g's 64 lane minima
 #pragma unroll

@@ -78,11 +78,7 @@ tp_ymin_kernel(int n, const double* __restrict__ pts, Scal* __restrict__ scal) {
         kmin = ordered_key(y);  // -0.0 directly below +0.0
     }
     if (__ballot(bad) != 0ull && lane == 0) atomicOr(&scal->flags, (unsigned)FLAG_NONFINITE);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned long long a = __shfl_xor(kmin, o);
-        kmin = a < kmin ? a : kmin;
-    }
+    kmin = pn2_wave_all_min(kmin);
     if (lane == 0) s_min[wave] = kmin;
     __syncthreads();
     if (tid == 0) {  // every workgroup holds at least one live row
@@ -266,11 +262,7 @@ tg_gather_kernel(int npts, int q0, int use_color, const double* __restrict__ pts
         const unsigned long long x = ordered_key(pts[pos * 3]), y = ordered_key(pts[pos * 3 + 1]), z = ordered_key(pts[pos * 3 + 2]);
         k0 = x < k0 ? x : k0; k1 = y < k1 ? y : k1; k2 = z < k2 ? z : k2;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned long long x = __shfl_xor(k0, o), y = __shfl_xor(k1, o), z = __shfl_xor(k2, o);
-        k0 = x < k0 ? x : k0; k1 = y < k1 ? y : k1; k2 = z < k2 ? z : k2;
-    }
+    k0 = pn2_wave_all_min(k0); k1 = pn2_wave_all_min(k1); k2 = pn2_wave_all_min(k2);
     if (lane == 0) { s_min[0][wave] = k0; s_min[1][wave] = k1; s_min[2][wave] = k2; }
     __syncthreads();
 #pragma unroll

@@ -41,8 +41,7 @@ ce_forward_kernel(int rows, int C, const float* __restrict__ logits, const Label
             nz = wr != 0.f ? 1.0 : 0.0;
         }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { loss += __shfl_xor(loss, o); nz += __shfl_xor(nz, o); }
+    loss = pn2_wave_all_sum(loss); nz = pn2_wave_all_sum(nz);
     if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = loss; s_cnt[threadIdx.x >> 6] = nz; }
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -16,6 +16,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "pn2_wave.h"
+
 // ---- scans and sums ----------------------------------------------------------------------------------------------------------
 // exclusive prefix of per-thread flags over the workgroup (thread order); `total` = workgroup sum.  wsum: W ints.
 // The flag is an int on purpose (non-zero = set): taken as a bool, a flag formed inside a divergent branch stays a lane mask that
@@ -67,8 +69,7 @@ __device__ __forceinline__ int wg_excl_scan_int(int v, int* wsum, int& total) {
 // workgroup sum of a per-thread value, returned to every thread; red: W elements
 template <int W, typename T>
 __device__ __forceinline__ T wg_sum(T v, T* red) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    v = pn2_wave_all_sum(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     T t = 0;
@@ -85,10 +86,7 @@ __device__ __forceinline__ T wg_sum(T v, T* red) {
 // the wave's minimum in every lane (xor-shuffle tree, 32 down to 1); lane 0 of each wave leaves it in smin[axis][wave]; a barrier
 template <int W>
 __device__ __forceinline__ void wg_min3_stage(double& m0, double& m1, double& m2, double (*smin)[W]) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        m0 = fmin(m0, __shfl_xor(m0, o)); m1 = fmin(m1, __shfl_xor(m1, o)); m2 = fmin(m2, __shfl_xor(m2, o));
-    }
+    m0 = pn2_wave_all(m0, Pn2OpFmin()); m1 = pn2_wave_all(m1, Pn2OpFmin()); m2 = pn2_wave_all(m2, Pn2OpFmin());
     if ((threadIdx.x & 63) == 0) { smin[0][threadIdx.x >> 6] = m0; smin[1][threadIdx.x >> 6] = m1; smin[2][threadIdx.x >> 6] = m2; }
     __syncthreads();
 }
