@@ -1401,6 +1401,56 @@ int pn2_plane_ransac(int n, const float *points, const int *labels, float thr, i
                      const double *axis, double cos2, unsigned char *inlier, double *plane, int *header, void *workspace,
                      size_t workspace_bytes, void *stream);
 
+/* Fixed-radius neighbourhoods (csrc/pn2_neighbors.hip): per point the number of points within `radius` of it, the integer moments
+ * of that neighbourhood, the surface normal and the surface variation there -- what Open3D offers as estimate_normals with
+ * KDTreeSearchParamRadius and as remove_radius_outlier.  tests/neighbors_ref.py is the numpy model of the rules and is compared
+ * for equality: a neighbourhood is decided by a float64 comparison, its sums are integer adds, and everything after them is
+ * float64 in the written association (no contraction; sqrt and / correctly rounded), so nothing in a result depends on the order
+ * in which threads arrive or on which candidates a thread looks at.
+ *
+ *   points (n,3) float32; labels (n) int32 or NULL; radius float32, finite and > 0; min_neighbors >= 1; viewpoint (3) float64 ON
+ *   THE HOST (read before the call returns) or NULL.
+ *   VALID.  The rule of pn2_cluster_points: three finite coordinates and, with labels, a label >= 0.
+ *   NEIGHBOUR.  For a valid point i every valid point j, i ITSELF INCLUDED (labels need not be equal), with, in float64,
+ *       (dx*dx + dy*dy) + dz*dz <= r*r,   r = (double)radius,   dx = (double)x_j - (double)x_i (exact), dy and dz likewise.
+ *     count[i] = the number of neighbours, at least 1 for a valid point; 0 for an invalid one.
+ *   LATTICE, one per call.  Q = min(20, (60 - bitlen(n)) >> 1), bitlen = the number of bits of n.  r = f * 2^x with f in [0.5, 1)
+ *     (frexp) and h = 2^(x-Q).  Per neighbour and axis q = (long long)rint(d / h), ties to even, d the difference above.  The
+ *     division is exact (h is a power of two), and |q| <= 2^Q: the test bounds |d| by r * (1 + 2^-51), and r <= (1 - 2^-24) * 2^x.
+ *   MOMENTS (int64).  S_x S_y S_z S_xx S_xy S_xz S_yy S_yz S_zz = the sums of q_a and of q_a * q_b over the neighbours.  Every sum
+ *     is at most n * 2^(2Q) <= 2^60 in magnitude.  Integer adds only, so no order of arrival shows.
+ *   COVARIANCE AND AXES.  Exactly the rules of pn2_cluster_describe with m = count and upright = 0:
+ *     A_ab = (double)S_ab / (double)m - ((double)S_a / (double)m) * ((double)S_b / (double)m); eight cyclic Jacobi sweeps; the
+ *     eigenpairs sorted by descending diagonal, equal values keeping the lower column first; a0 and a1 sign-fixed; a2 = a0 x a1.
+ *   NORMAL.  It starts from a2, negated when its component of largest magnitude (the first among equals) is negative.  With a
+ *     viewpoint v:  w = ((v_x - p_x) * n_x + (v_y - p_y) * n_y) + (v_z - p_z) * n_z  in float64, p the point widened; the normal
+ *     is negated when w < 0.  A zero or NaN w changes nothing.  The output is float32, each component rounded once.
+ *   CURVATURE (surface variation).  t = (lambda_0 + lambda_1) + lambda_2;  c = lambda_2 / t;  c = 0 unless c > 0 (so 0 / 0 and a
+ *     negative rounding residue give 0).  The output is float32.
+ *   VARIANCE.  variance_k = lambda_k * (h * h), float64.
+ *   POINTS WITHOUT A RESULT.  A valid point with count < min_neighbors keeps its count and its moments; its normal, curvature and
+ *     variance are NaN.  An invalid point has count 0, a zero moments row and NaNs.
+ *
+ * pn2_radius_neighborhoods: count (n) int32; moments (n,9) int64 or NULL; normals (n,3) float32; curvature (n) float32; variance
+ *   (n,3) float64 or NULL; header (8) int32 on the device: [0] status, [1] valid points, [2] points with count >= min_neighbors,
+ *   [3] the largest count, [4] Q, [5] x, [6..7] zero.  Status 0 = ok; 1 = more than 2^21 cells of edge radius on an axis of the
+ *   valid points' box (the convention of pn2_cluster_points): then every count is 0, the moments are zero, normals, curvature and
+ *   variance are NaN and header[1..7] are zero.  moments and variance are written only when given; the other outputs are the
+ *   same bits either way.
+ *   workspace: *bytes of pn2_radius_workspace_size(n, bytes) (a host query like pn2_cluster_workspace_size: PN2_EINVAL for
+ *   n <= 0, PN2_ENULL without bytes), 256-byte aligned; it need not be cleared.  The call queues the sorted-key grid of
+ *   pn2_cluster_points (cell edge radius * (1 + 2^-20), its launches and one radix sort) and one scan in which a lane owns a
+ *   point and keeps its count and sums in registers: no atomic on a sum, no memset node, no allocation, no synchronisation.
+ *   Refusals, nothing launched and nothing written, in this order: PN2_EINVAL (n < 1, radius not finite or <= 0, min_neighbors
+ *   < 1, a non-finite viewpoint), PN2_ENULL (points, count, normals, curvature, header or workspace NULL), PN2_EINVAL (points,
+ *   labels, count, normals, curvature or header not 4-byte aligned, moments or variance not 8-byte aligned, a workspace not
+ *   256-byte aligned or too small), PN2_EUNSUP (a capturing stream: it allocates nothing and would be capturable, but nothing in
+ *   the project captures it, so the refusal stands until a later change lifts it together with a capture test). */
+int pn2_radius_workspace_size(int n, unsigned long long *bytes);
+int pn2_radius_neighborhoods(int n, const float *points, const int *labels, float radius, int min_neighbors,
+                             const double *viewpoint, int *count, long long *moments, float *normals, float *curvature,
+                             double *variance, int *header, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

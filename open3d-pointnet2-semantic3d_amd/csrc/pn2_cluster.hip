@@ -20,14 +20,7 @@
 //  10 cluster_number_kernel  : number[i] of a kept root = block offset + its place in the block (pn2_wg.h's scan), -1 otherwise.
 //  11 cluster_ids_kernel     : ids[i] = number[root[i]], -1 without a root.
 //
-// THE GRID.  h = eps * (1 + 2^-20) in float64, cell = floor(((double)x - (double)min_x) / h) per axis.  Why two points that pass
-// the link test are never two cells apart on an axis: the test (dx*dx + dy*dy) + dz*dz <= eps*eps in float64 bounds |dx| by
-// eps * (1 + 2^-51) (three roundings of 2^-53 each on the left, one on the right).  With a = x - min_x exact, the computed
-// quotient q carries two roundings (the subtraction, the division): |q - a/h| <= 2.01 * 2^-53 * a/h, and a/h < 2^21 for every
-// point that is not refused with status 1, so the error of a quotient is below 2^-31.  Then
-//     q_i - q_j <= (a_i - a_j)/h + 2^-30 <= (1 + 2^-51) / (1 + 2^-20) + 2^-30 < 1 - 2^-21 < 1,
-// and two numbers less than 1 apart have floors at most 1 apart.  (The hair is 2^-20, nine orders of magnitude above what the
-// roundings need, and costs a 27-cell volume one part in 350 000.)
+// THE GRID: pn2_cell_grid.h (the cell edge eps * (1 + 2^-20) and why the 27 cells around a point hold every linked partner).
 //
 // THE UNION-FIND.  parent[] over point indices; parent[i] <= i always, and a link always points from the higher root to the lower:
 // a root is the lowest index of its tree, hence at the end the component's `first`.
@@ -41,24 +34,16 @@
 //   * parent[] is read with relaxed agent-scope atomic loads.  A stale value is an ancestor of an earlier time: it lengthens a walk
 //     or fails a swap, and no loop's exit rests on it -- find ends on its own decreasing index, unite on the swap's answer.
 // No kernel waits for another workgroup.
-#include "pn2_common.h"   // pn2_wave_umin
+#include "pn2_cell_grid.h"  // kT, kW, kCellBits, kCellLimit, kInvalidKey, GridScal, cluster_min_kernel, cluster_key_kernel, lower_bound_key
+#include "pn2_common.h"
 #include "pn2_ordered.h"  // ordered_key32, ordered_to_float
 #include "pn2_sort.h"     // IndexSort
 #include "pn2_wg.h"       // wg_excl_scan_flag, wg_excl_scan_int, wg_sum, point_valid, WsCarver
 
 namespace {
 
-constexpr int kT = 256;            // threads of every workgroup here; also the scan block (points per block count)
-constexpr int kW = kT / 64;
-constexpr int kCellBits = 21;
-constexpr int kCellLimit = 1 << kCellBits;
-constexpr unsigned long long kInvalidKey = ~0ull;
-
-// the scalars of one call, at the head of the workspace
-struct Scal {
-    unsigned min_key[3];  // ordered uint32 of the minimum x, y, z over the valid points
-    int status;
-    int nvalid;
+// the scalars of one call, at the head of the workspace: the grid's, then
+struct Scal : GridScal {
     int ncomp;            // components before the size filter
     int nkeptpts;         // points in kept clusters
 };
@@ -89,53 +74,6 @@ __global__ void cluster_init_kernel(Scal* __restrict__ s) {
         s->min_key[0] = s->min_key[1] = s->min_key[2] = 0xFFFFFFFFu;
         s->status = s->nvalid = s->ncomp = s->nkeptpts = 0;
     }
-}
-
-__global__ void __launch_bounds__(kT)
-cluster_min_kernel(int n, const float* __restrict__ points, const int* __restrict__ labels, Scal* __restrict__ s) {
-    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
-    const bool ok = i < n && point_valid(points, labels, i);
-    unsigned k0 = 0xFFFFFFFFu, k1 = 0xFFFFFFFFu, k2 = 0xFFFFFFFFu;
-    if (ok) {
-        const float* p = points + (size_t)i * 3;
-        k0 = ordered_key32(p[0]);
-        k1 = ordered_key32(p[1]);
-        k2 = ordered_key32(p[2]);
-    }
-    const unsigned long long bal = __ballot(ok);
-    k0 = pn2_wave_umin(k0);
-    k1 = pn2_wave_umin(k1);
-    k2 = pn2_wave_umin(k2);
-    if (bal != 0ull && (threadIdx.x & 63) == 0) {
-        atomicMin(&s->min_key[0], k0);
-        atomicMin(&s->min_key[1], k1);
-        atomicMin(&s->min_key[2], k2);
-        atomicAdd(&s->nvalid, __popcll(bal));
-    }
-}
-
-__global__ void __launch_bounds__(kT)
-cluster_key_kernel(int n, const float* __restrict__ points, const int* __restrict__ labels, double h, Scal* __restrict__ s,
-                   unsigned long long* __restrict__ keys, int* __restrict__ vals) {
-    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
-    if (i >= n) return;
-    unsigned long long key = kInvalidKey;
-    if (point_valid(points, labels, i)) {
-        const float* p = points + (size_t)i * 3;
-        key = 0ull;
-        bool far = false;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            // >= 0: the minimum is the least of them and the subtraction is monotone
-            const double q = __builtin_floor(((double)p[a] - (double)ordered_to_float(s->min_key[a])) / h);
-            const bool in = q < (double)kCellLimit;  // tested in floating point before the conversion
-            far = far || !in;
-            key |= (unsigned long long)(in ? (long long)q : (long long)(kCellLimit - 1)) << (kCellBits * a);
-        }
-        if (far) atomicMax(&s->status, 1);
-    }
-    keys[i] = key;
-    vals[i] = (int)i;
 }
 
 __global__ void __launch_bounds__(kT)
@@ -179,16 +117,6 @@ __device__ __forceinline__ void uf_unite(int* parent, int a, int b) {
         a = seen;  // hi was hooked by somebody else meanwhile: its new parent is united with lo instead
         b = lo;
     }
-}
-
-// first t in [0, hi) with keys[t] >= k
-__device__ __forceinline__ int lower_bound_key(const unsigned long long* __restrict__ keys, int hi, unsigned long long k) {
-    int lo = 0;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < k) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 __global__ void __launch_bounds__(kT)

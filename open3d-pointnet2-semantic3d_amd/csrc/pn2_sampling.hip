@@ -733,6 +733,7 @@ extern "C" int pn2_debug_set_fps_large(int what, int value);
 extern "C" int pn2_debug_set_interp(int what, int value);
 extern "C" int pn2_debug_set_coarse(int what, int value);
 extern "C" int pn2_debug_set_describe(int what, int value);
+extern "C" int pn2_debug_set_neighbors(int what, int value);
 extern "C" int pn2_debug_set_fps_stats(long long* dev_ptr) { g_fps_stats = dev_ptr; return 0; }
 extern "C" int pn2_debug_set(int what, int value) {
     if (what == 0) { g_fps_variant = value; return 0; }
@@ -742,6 +743,7 @@ extern "C" int pn2_debug_set(int what, int value) {
     if (what == 12) return pn2_debug_set_interp(what, value);
     if (what == 15) return pn2_debug_set_coarse(what, value);
     if (what == 19 || what == 20) return pn2_debug_set_describe(what, value);
+    if (what == 21 || what == 22) return pn2_debug_set_neighbors(what, value);
     if (what == 6 || what == 7 || what == 13 || what == 14 || what == 16) return pn2_debug_set_fused(what, value);
     return pn2_debug_set_grouping(what, value);
 }

@@ -12,6 +12,7 @@ the Predictor is used as it is.  After the frame's construction nothing on this 
 import torch
 
 from .cluster import _device_of, describe_clusters, euclidean_clusters
+from .neighbors import estimate_normals
 from .plane import segment_plane
 from .predict import Predictor, _on_device
 
@@ -67,6 +68,12 @@ class PredictInterpolator:
         -> cluster.Boxes: centroid, axes, oriented box and size per object.  upright (the default here): a vehicle stands on the
         road, so the box turns about the z axis only and Boxes.yaw() is its heading."""
         return describe_clusters(file_data.points, clusters, upright=upright)
+
+    def normals_for_frame(self, file_data, radius, min_neighbors=3):
+        """(extension) the surface normal at every point of file_data.points from the points within `radius` of it:
+        neighbors.estimate_normals with the viewpoint at the sensor, (0,0,0), so every normal faces it -> (n,3) float32, NaN
+        where fewer than min_neighbors points lie within the radius.  Eager."""
+        return estimate_normals(file_data.points, radius, viewpoint=(0.0, 0.0, 0.0), min_neighbors=min_neighbors)
 
     def ground_for_frame(self, file_data, distance_threshold, trials=1024, seed=0, max_angle=15.0, dense_labels=None, classes=None):
         """(extension) the ground of file_data.points: plane.segment_plane with the axis (0,0,1), the normal within max_angle
