@@ -73,6 +73,9 @@ def kernel_model(name, a):
     if name == "pn2_linear":
         rows, cin, cout = a[:3]
         return "mfma", 2 * rows * cin * cout
+    if name == "pn2_linear_pool_packed":  # ints: groups, nsample, cin, cout, relu.  The layer's flops over all rows, as for the
+        groups, ns, cin, cout = a[:4]     # other row-packed kernels: how many rows are live depends on the data
+        return "mfma", 2 * groups * ns * cin * cout
     if name == "pn2_mlp_chain":
         rows, cin, L = a[0], a[1], a[2]
         widths = a[4:4 + L]

@@ -663,6 +663,21 @@ int pn2_fp_mlp_fused_pre_schedule(int b, int n, int m, int c1, const float *dist
  * A/B timing and the parity tests. */
 int pn2_set_sa_row_packing(int on);
 
+/* pn2_linear(groups * 32, cin, cout, x, w, bias, relu = 1, pool = 32, y) on the LIVE rows only, for a pooled layer whose input
+ * rows sit behind a ball query (the last layer of SA3: pointnet_util.py:150-170 on the un-pooled output of the fused chain):
+ *   y[g] = relu( max_{j < 32} ( x[32 g + j] . w ) + bias )        x (groups * 32, cin)   idx (groups, 32)   y (groups, cout)
+ * PRECONDITION, relied on for exactness: for every group g, the rows j >= live(g) of x equal row 0 of that group bit for bit,
+ * live(g) = 1 + the last position of idx[g] that differs from position 0.  It holds for any x computed row by row by
+ * deterministic kernels from rows gathered through idx (those rows gather the same source row).  The kernel classifies and
+ * packs the groups as the row-packed set-abstraction kernels do and contracts each row in the k order of pn2_linear's LDS-tiled
+ * kernel: y has the bits of pn2_linear(..., relu = 1, pool = 32) wherever that runs without a k split (from 4096 rows on for
+ * cout = 256, from 8192 on for cout = 128).
+ * Takes nsample = 32, relu = 1, a bias, cin % 4 == 0, cout % 128 == 0, x and w 16-byte aligned, and a 64-column slice of w
+ * that fits the LDS (cin <= 576); with pn2_set_sa_row_packing(0), or anything else: PN2_EUNSUP, nothing launched (callers fall
+ * back to pn2_linear). */
+int pn2_linear_pool_packed(int groups, int nsample, int cin, int cout, const float *x, const int *idx, const float *w,
+                           const float *bias, int relu, float *y, void *stream);
+
 /* pn2_sa_mlp_max_fused / pn2_sa_mlp_rows_fused with the FEATURE part of the first layer hoisted by linearity:
  * [xyz - centre | features] @ W1 = (xyz - centre) @ W1[:3] + (features @ W1[3:])[idx], and zf = features @ W1[3:] has one
  * row per source point (b*n) instead of one per grouped neighbour (b*m*nsample).  zf (b*n, widths[0]) replaces `points`,

@@ -26,6 +26,7 @@
 #include "pn2_mfma_stats.h"
 #include "pn2_fwd_narrow.h"
 #include "pn2_dgrad_wide.h"
+#include "pn2_row_packing.h"
 
 namespace {
 
@@ -755,6 +756,122 @@ int launch_linear_splitk(int rows, int cin, int cout, const float* x, const floa
     return PN2_OK;
 }
 
+// ---- the pooled layer behind a ball query (SA3's last layer: 32768 x 128 -> 256 + max over K = 32), live rows only ----------
+// y[g] = relu(max_j(x[32 g + j] . w) + bias) where the rows j >= live(g) of x are bit-for-bit copies of row 32 g (the caller's
+// precondition: x came from a deterministic row-wise chain behind the index rows idx, pn2_row_packing.h).  A workgroup of NW
+// waves takes a block of `blk` consecutive groups and one BN-column slice of w: it stages the slice in LDS once (k-major, the
+// B tile layout of linear_kernel for all of cin; the loads fly under the classifier's index loads), classifies the block and
+// packs its live rows into 32-row tiles.  A task = one tile x 32 NTW columns; wave v runs tasks v, v + NW, ... with no barrier
+// between them: the A operand goes straight from global memory to the MFMA (lane (row = l & 31, half) loads k = 32 c + 8 t +
+// 4 half + {0..3} with one 16-byte load, the next 32 k in flight under the MFMAs).  No workgroup waits for another.
+// Every output element contracts k in linear_kernel's order -- step (c, t, q) feeds k = 32 c + 8 t + q (lanes 0-31) and + 4
+// (lanes 32-63), zero-filled up to a multiple of 32 -- so the maximum is taken over the same fp32 values, each once or more:
+// the bits of pn2_linear(..., relu = 1, pool = 32) wherever that runs linear_kernel without a k split.
+// Shipped as <64, 2, 8>: 76 VGPRs, 0 AGPRs, no scratch (build log, -Rpass-analysis=kernel-resource-usage); 34 KB of LDS at
+// cin = 128.  Measured on SA3's geometry (tools/sa3_pool_packing_ab.py, 32768 rows, S-scene): 64-column slices and 8 waves 19.0
+// us, 128 columns and 8 waves 20.3, 64 columns and 4 waves 23.1, 128 columns and 4 waves 23.9, against 23.1 for
+// linear_kernel<4,1,4> on all rows; staging w chunk by chunk under the first task's MFMAs changed nothing (20.2).
+template <int BN, int NTW, int NW>
+__global__ void __launch_bounds__(64 * NW)
+linear_pool_packed_kernel(int groups, int cin, int cout, int blk, const float* __restrict__ x, const int* __restrict__ idx,
+                          const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ y) {
+    constexpr int BS = BN + 4, NSUB = BN / (32 * NTW), NTH = 64 * NW;
+    extern __shared__ __attribute__((aligned(16))) float pk_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nkc = (cin + kBK - 1) / kBK;  // contraction chunks of 32; the rows [cin, 32 nkc) of the staged slice are zero
+    float* Bs = pk_lds;
+    int* s_cls = reinterpret_cast<int*>(Bs + (size_t)nkc * kBK * BS);
+    int* s_desc = s_cls + kPn2PackBlockMax;
+    const int col0 = blockIdx.y * BN;
+    const int base = blockIdx.x * blk;
+    const int cnt = min(blk, groups - base);
+
+    // the slice of w, 8 independent 16-byte loads per thread and round; the first round flies under the classifier's index loads
+    const int nf4 = nkc * kBK * (BN / 4);
+    auto w_load = [&](int e0, f32x4 (&v)[8]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int e = e0 + u * NTH + tid;
+            const int k = e / (BN / 4), n4 = e % (BN / 4);
+            const f32x4 t = *reinterpret_cast<const f32x4*>(w + (size_t)(k < cin ? k : cin - 1) * cout + col0 + n4 * 4);
+            v[u] = k < cin ? t : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    auto w_store = [&](int e0, const f32x4 (&v)[8]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int e = e0 + u * NTH + tid;
+            if (e < nf4) *reinterpret_cast<f32x4*>(Bs + (e / (BN / 4)) * BS + (e % (BN / 4)) * 4) = v[u];
+        }
+    };
+    f32x4 wv[8];
+    w_load(0, wv);
+    const Pn2PackBlock pk = pn2_pack_classify<NW>(idx, base, cnt, wave, lane, s_cls, s_desc);
+    w_store(0, wv);
+    for (int e0 = NTH * 8; e0 < nf4; e0 += NTH * 8) {
+        w_load(e0, wv);
+        w_store(e0, wv);
+    }
+    __syncthreads();
+
+    const int ntasks = pk.tiles() * NSUB;
+    for (int task = wave; task < ntasks; task += NW) {
+        const int tile = task / NSUB, sub = task % NSUB;
+        int sshift, nvalid, gq[4];
+        pn2_pack_tile(pk, tile, s_desc, sshift, nvalid, gq);
+        const int q = l31 >> sshift;
+        const int grp = q == 1 ? gq[1] : (q == 2 ? gq[2] : (q == 3 ? gq[3] : gq[0]));
+        const float* __restrict__ xr = x + ((size_t)grp * 32 + (l31 & ((1 << sshift) - 1))) * cin + 4 * half;
+        auto fetch = [&](int c, f32x4 (&a)[4]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {  // unconditional clamped loads; cin % 4 == 0: four k are all in or all out
+                const int k = c * kBK + 8 * t + 4 * half;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(xr + (k < cin ? c * kBK + 8 * t : cin - 4 - 4 * half));
+                a[t] = k < cin ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        };
+        f32x16 acc[NTW];
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
+        // both operands of chunk c + 1 are on their way (A from global memory, B from LDS) under the MFMAs of chunk c: a wave has
+        // its SIMD to itself or shares it with one other, so nothing else would hide an LDS round trip in front of every MFMA
+        const float* bs0 = Bs + (4 * half) * BS + sub * (NTW * 32) + l31;
+        auto b_read = [&](int c, float (&b)[16][NTW]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt) b[s][nt] = bs0[(c * kBK + 8 * (s >> 2) + (s & 3)) * BS + nt * 32];
+        };
+        f32x4 a_cur[4], a_nxt[4];
+        float b_cur[16][NTW], b_nxt[16][NTW];
+        fetch(0, a_cur);
+        b_read(0, b_cur);
+        for (int c = 0; c < nkc; ++c) {
+            const int cn = c + 1 < nkc ? c + 1 : c;
+            fetch(cn, a_nxt);
+            b_read(cn, b_nxt);
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+                    for (int nt = 0; nt < NTW; ++nt)
+                        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_cur[t][qq], b_cur[4 * t + qq][nt], acc[nt], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) a_cur[t] = a_nxt[t];
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt) b_cur[s][nt] = b_nxt[s][nt];
+        }
+        const int cofs = col0 + sub * (NTW * 32);
+        pool_store_packed<NTW>(acc, bias + cofs, y + cofs, cout, sshift, nvalid, gq, half, l31);
+    }
+}
+
 // Weight gradient of a dense layer (training): dW (cin, cout) = x^T (cin, rows) . dy (rows, cout), the reduction over
 // ALL rows (524288 for SA1) that hipBLASLt runs at ~10 % of the memory roofline on these tall-skinny shapes.  One
 // wave owns a (32*TM x 32*TN) tile of dW for a chunk of rows and streams x and dy straight from HBM into the MFMA
@@ -1046,6 +1163,32 @@ static int linear_impl(int rows, int cin, int cout, const float* x, const float*
 extern "C" int pn2_linear(int rows, int cin, int cout, const float* x, const float* w,
                           const float* bias, int relu, int pool, float* y, void* stream) {
     return linear_impl(rows, cin, cout, x, w, bias, relu, pool, y, stream, nullptr);
+}
+
+// pn2_linear(groups * 32, ..., relu = 1, pool = 32) on the live rows of a ball query's groups only (linear_pool_packed_kernel)
+extern "C" int pn2_linear_pool_packed(int groups, int nsample, int cin, int cout, const float* x, const int* idx, const float* w,
+                                      const float* bias, int relu, float* y, void* stream) {
+    if (groups <= 0 || nsample <= 0 || cin <= 0 || cout <= 0) return PN2_EINVAL;
+    if (!x || !idx || !w || !y) return PN2_ENULL;
+    if (!pn2_sa_row_packing_enabled() || nsample != 32 || !relu || !bias || cin % 4 != 0 || cout % 128 != 0 ||
+        ((uintptr_t)x % 16) != 0 || ((uintptr_t)w % 16) != 0)
+        return PN2_EUNSUP;
+    if ((long long)groups * 32 + 128 > 0x7fffffffLL) return PN2_ERANGE;
+    const int nkc = (cin + kBK - 1) / kBK;
+    constexpr int kPackedBN = 64;  // columns of w per workgroup
+    const size_t lds = sizeof(float) * (size_t)nkc * kBK * (kPackedBN + 4) + kPn2PackLdsBytes;  // the slice of w + the tile list
+    if (lds > (size_t)kPn2CuLdsBytes) return PN2_EUNSUP;
+    // blocks of consecutive groups: about one workgroup of 8 waves per CU over both grid axes, 8 groups at least (a class-8 tile
+    // holds four), 16 at SA3's 1024 groups x 256 columns
+    const int cb = cout / kPackedBN;
+    int blk = (int)(((long long)groups * cb + 255) / 256);
+    blk = blk < 8 ? 8 : (blk > kPn2PackBlockMax ? kPn2PackBlockMax : blk);
+    constexpr auto kern = linear_pool_packed_kernel<kPackedBN, 2, 8>;
+    const int e = pn2_allow_lds<kern>(kPn2CuLdsBytes);
+    if (e) return e;
+    kern<<<dim3((groups + blk - 1) / blk, cb), 512, lds, static_cast<hipStream_t>(stream)>>>(groups, cin, cout, blk, x, idx, w, bias, y);
+    PN2_RETURN_IF_LAUNCH_FAILED();
+    return PN2_OK;
 }
 
 // y (rows, cout) = x (rows, cin) . w (cin, cout) + bias for 1 <= cout <= 16 (no activation): the class head of the network

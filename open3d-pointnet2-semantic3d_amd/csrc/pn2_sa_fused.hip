@@ -31,6 +31,7 @@
 // refused call has not touched `out`.
 #include "pn2_common.h"
 #include "pn2_layer_stack.h"
+#include "pn2_row_packing.h"
 #include <atomic>
 #include <type_traits>
 #include <utility>
@@ -259,42 +260,6 @@ __device__ __forceinline__ void pool_store_k(const f32x16 (&acc)[NT], const floa
     }
 }
 
-// pooled epilogue of a PACKED tile (K = 32, see sa_fused_kernel's PACK): the tile holds 32 >> sshift slots of 1 << sshift rows,
-// slot q = rows [q << sshift, (q + 1) << sshift) = accumulator registers [q << (sshift - 1), (q + 1) << (sshift - 1)) of both
-// half-waves, and belongs to centre gq[q].  One maximum per slot, the same half-wave exchange, bias and ReLU as pool_store;
-// slots >= nvalid repeat slot 0's rows and store nothing.  A maximum does not depend on the order it is taken in, nor on how
-// often a value occurs: same bits as pool_store over the centre's 32 rows when the dropped rows are copies of row 0.
-template <int NT>
-__device__ __forceinline__ void pool_store_packed(const f32x16 (&acc)[NT], const float* __restrict__ sbias, float* __restrict__ out,
-                                                  int wout, int sshift, int nvalid, const int (&gq)[4], int half, int l31) {
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const float bv = sbias[nt * 32 + l31];
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            v[q] = fmaxf(fmaxf(acc[nt][4 * q], acc[nt][4 * q + 1]), fmaxf(acc[nt][4 * q + 2], acc[nt][4 * q + 3]));
-        if (sshift == 3) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float u = fmaxf(v[q], __shfl_xor(v[q], 32));
-                if (half == 0 && q < nvalid) out[(size_t)gq[q] * wout + nt * 32 + l31] = fmaxf(u + bv, 0.f);
-            }
-        } else if (sshift == 4) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                float u = fmaxf(v[2 * q], v[2 * q + 1]);
-                u = fmaxf(u, __shfl_xor(u, 32));
-                if (half == 0 && q < nvalid) out[(size_t)gq[q] * wout + nt * 32 + l31] = fmaxf(u + bv, 0.f);
-            }
-        } else {
-            float u = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-            u = fmaxf(u, __shfl_xor(u, 32));
-            if (half == 0) out[(size_t)gq[0] * wout + nt * 32 + l31] = fmaxf(u + bv, 0.f);
-        }
-    }
-}
-
 // last-layer epilogue without pooling: relu(acc + bias) for all 32 rows of the tile
 template <int NT>
 __device__ __forceinline__ void rows_store(const f32x16 (&acc)[NT], const float* __restrict__ sbias,
@@ -491,45 +456,16 @@ sa_fused_kernel(SaFusedParams p) {
         pk_nb = (pk_hi - pk_lo + p.blk - 1) / p.blk;
     }
     for (bool pk_first = true;; pk_b += pk_bstep, pk_first = false) {  // !PACK: one pass
-    int pk_base = 0, pk_n32 = 0, pk_t16 = 0, pk_n16 = 0, pk_n8 = 0;
+    int pk_base = 0;
+    Pn2PackBlock pk = {0, 0, 0, 0};
+    (void)pk;
     if constexpr (PACK) {
         if (pk_b >= pk_nb) break;
         if (!pk_first) __syncthreads();  // the previous block's tile list is still being read
         pk_base = pk_lo + pk_b * p.blk;
         const int cnt = min(p.blk, pk_hi - pk_base);
-        // classify: a half-wave reads one centre's 32 indices (128 bytes); live slots = 1 + the last position that differs from
-        // position 0 (NOT the number of distinct values: equal entries need not be contiguous)
-        for (int c0 = 2 * wave; c0 < cnt; c0 += 2 * NW) {
-            const int cl = c0 + half;
-            const int v = p.idx[(size_t)(pk_base + (cl < cnt ? cl : c0)) * 32 + l31];
-            const int first = __shfl(v, lane & 32);
-            const unsigned long long diff = __ballot(v != first);
-            const unsigned mine = (unsigned)(diff >> (lane & 32));
-            const int live = 32 - __clz(mine | 1u);  // highest differing position + 1 (>= 1)
-            if (l31 == 0 && cl < cnt) s_cls[cl] = live <= 8 ? 8 : (live <= 16 ? 16 : 32);
-        }
-        __syncthreads();
-        const int cls = lane < cnt ? s_cls[lane] : 0;
-        const unsigned long long m32 = __ballot(cls == 32), m16 = __ballot(cls == 16), m8 = __ballot(cls == 8);
-        const int n16 = __popcll(m16), n8 = __popcll(m8);
-        // an odd class-16 centre shares its tile with the last class-8 centre when that saves the class-8 tile it would open
-        const int promote = ((n16 & 1) && (n8 & 3) == 1) ? 1 : 0;
-        pk_n32 = __popcll(m32); pk_n16 = n16 + promote; pk_n8 = n8 - promote;
-        pk_t16 = (pk_n16 + 1) >> 1;
-        if (wave == 0 && lane < cnt) {
-            const unsigned long long below = (1ull << lane) - 1ull;
-            int tile, slot;
-            if (cls == 32) { tile = __popcll(m32 & below); slot = 0; }
-            else {
-                int c = cls, r = __popcll((cls == 16 ? m16 : m8) & below);
-                if (promote && c == 8 && r == n8 - 1) { c = 16; r = n16; }
-                if (c == 16) { tile = pk_n32 + (r >> 1); slot = r & 1; }
-                else { tile = pk_n32 + pk_t16 + (r >> 2); slot = r & 3; }
-            }
-            s_desc[tile * 4 + slot] = pk_base + lane;
-        }
-        __syncthreads();
-        g_lo = wave; g_hi = pk_n32 + pk_t16 + ((pk_n8 + 3) >> 2); g_step = NW;
+        pk = pn2_pack_classify<NW>(p.idx, pk_base, cnt, wave, lane, s_cls, s_desc);  // pn2_row_packing.h
+        g_lo = wave; g_hi = pk.tiles(); g_step = NW;
     }
     for (int g = g_lo; g < g_hi; g += g_step, ++tile_no) {
         PN2_CHAIN_STAMP(2);
@@ -550,11 +486,7 @@ sa_fused_kernel(SaFusedParams p) {
             int grp, ii;
             if constexpr (PACK) {
                 // tile g of the block: 32-row slots first, then 16, then 8; the last tile of a class may be short
-                if (g < pk_n32) { pk_sshift = 5; pk_nvalid = 1; }
-                else if (g < pk_n32 + pk_t16) { pk_sshift = 4; pk_nvalid = min(2, pk_n16 - 2 * (g - pk_n32)); }
-                else { pk_sshift = 3; pk_nvalid = min(4, pk_n8 - 4 * (g - pk_n32 - pk_t16)); }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) pk_gq[q] = __builtin_amdgcn_readfirstlane(s_desc[g * 4 + (q < pk_nvalid ? q : 0)]);
+                pn2_pack_tile(pk, g, s_desc, pk_sshift, pk_nvalid, pk_gq);
                 const int q = l31 >> pk_sshift;
                 grp = q == 1 ? pk_gq[1] : (q == 2 ? pk_gq[2] : (q == 3 ? pk_gq[3] : pk_gq[0]));
                 ii = p.idx[(size_t)grp * 32 + (l31 & ((1 << pk_sshift) - 1))];
@@ -1048,7 +980,6 @@ PN2_TUNABLE(int, g_chain_tag, 0)     // tuning hook (pn2_debug_set(16, v)): grap
 // Row packing of the pooled K = 32 gather kernels (sa_fused_kernel's PACK): process-wide, on by default.  The choice is read when
 // a launch is issued, so a captured graph keeps the one it was captured with.
 std::atomic<int> g_sa_row_packing{1};
-constexpr size_t kPackLdsBytes = (64 + 64 * 4) * sizeof(int);  // classes + tile list of one block
 
 // the chain kernel with or without row packing, its LDS limit raised on the current device (err = pn2_allow_lds's result)
 template <int L, int NT1, int NT2, int NT3, bool VEC8, bool DENSE, bool POOL, int NW, bool INTERP, bool PREZ>
@@ -1156,7 +1087,7 @@ int launch_chain(const SaFusedParams& p_in, hipStream_t st) {
         const int need8 = (p.groups + 7) / 8;
         if (grid > need8) grid = need8;
         p.blk = pack_block(p.groups, grid);
-        kern<<<grid, 512, bytes + (pack ? kPackLdsBytes : 0), st>>>(p);
+        kern<<<grid, 512, bytes + (pack ? kPn2PackLdsBytes : 0), st>>>(p);
     } else {
         int e = 0;
         auto kern = chain_kernel<L, NT1, NT2, NT3, VEC8, DENSE, POOL, 4, INTERP, PREZ>(pack, e);
@@ -1164,7 +1095,7 @@ int launch_chain(const SaFusedParams& p_in, hipStream_t st) {
         int grid = bytes > 78 * 1024 ? g_chain_grid : g_chain_grid * 2;  // 4-wave workgroups: as many as LDS lets co-reside per CU
         if (grid > need4) grid = need4;
         p.blk = pack_block(p.groups, grid);
-        kern<<<grid, 256, bytes + (pack ? kPackLdsBytes : 0), st>>>(p);
+        kern<<<grid, 256, bytes + (pack ? kPn2PackLdsBytes : 0), st>>>(p);
     }
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;

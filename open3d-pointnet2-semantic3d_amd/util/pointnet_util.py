@@ -31,6 +31,11 @@ USE_HOISTED_SA = True  # A/B: feature part of the first SA layer computed on the
 # was last told.  A captured graph keeps the choice it was captured with.
 USE_SA_ROW_PACKING = True
 _sa_row_packing_told = True
+# rows (B * npoint * 32) from which the pooled last layer of a [128, 128, wide] SA level runs on pn2_linear_pool_packed.  On
+# S-scene's level-3 geometry it beat pn2_linear in every interleaved pair at 16384 rows (13.1 against 13.2 us) and at 32768 rows
+# (19.0 against 23.1), not at 8192 (12.7 against 8.7): a tenth of a microsecond is no gain, and balls that are all full (S-randn)
+# lose there, so the route starts where the gain is decided (tools/sa3_pool_packing_ab.py, EXPERIMENTS.md r12)
+POOL_PACKED_MIN_ROWS = 32768
 USE_HOISTED_FP = True  # A/B: first FP layer's product with the interpolated channels computed on the known points (linearity)
 USE_FUSED_TRAIN_FRONT = True  # set False: the training path's SA / FP front ends as separate ops (tests / A-B)
 USE_MLP_CHAIN = True  # set False to force one pn2_linear launch per layer (tests/bench)
@@ -402,8 +407,12 @@ def _sa_route_mlp_rows_fused(a):
     h = _sa_fused_inference(a.xyz, a.new_xyz, a.points, a.idx, mlp[:2], a.bn, "conv%d", pool=False)
     if h is None:
         return None
+    # the pooled last layer on the live ball-query rows only (pn2_linear_pool_packed: same bits), from POOL_PACKED_MIN_ROWS on
+    packed = USE_SA_ROW_PACKING and a.nsample == 32 and mlp[2] % 128 == 0 and h.shape[0] * h.shape[1] * 32 >= POOL_PACKED_MIN_ROWS
+    if packed:
+        _sync_sa_row_packing(a.xyz)
     h = tf_util.conv2d(h, mlp[2], [1, 1], padding="VALID", stride=[1, 1], bn=a.bn, is_training=False,
-                       scope="conv2", bn_decay=a.bn_decay, pool=a.nsample)
+                       scope="conv2", bn_decay=a.bn_decay, pool=a.nsample, pool_idx=a.idx if packed else None)
     return h.squeeze(2)
 
 

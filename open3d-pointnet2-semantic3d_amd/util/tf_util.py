@@ -254,6 +254,21 @@ def hip_linear(x2d, w, b, relu=True, pool=0):
     return y
 
 
+def hip_linear_pool_packed(x2d, idx, w, b):
+    """relu(max over each group of 32 rows of x2d @ w + b) on the live rows of the ball query `idx` (b, m, 32) only
+    (pn2_linear_pool_packed): x2d's rows behind a padded index entry must be copies of the group's first row, which holds for the
+    output of the fused gather chain on `idx`.  Same bits as hip_linear(..., relu=True, pool=32).
+    -> (b * m, cout), or None when the library refuses the configuration (caller falls back to hip_linear)."""
+    require_cuda(x2d, idx, w, b)
+    groups, nsample = idx.shape[0] * idx.shape[1], idx.shape[2]
+    cin, cout = w.shape
+    x2d, idx = x2d.contiguous(), idx.contiguous()
+    y = torch.empty((groups, cout), dtype=torch.float32, device=x2d.device)
+    ok = launch("pn2_linear_pool_packed", x2d, groups, nsample, cin, cout, ptr(x2d), ptr(idx), ptr(w), ptr(b), 1, ptr(y),
+                may_refuse=True)
+    return y if ok else None
+
+
 _SAME = object()
 
 
@@ -1448,11 +1463,13 @@ def _train_layer(inputs, w2d, b, bnv, bn_decay, relu, pool=0, defer=False):
 
 def conv2d(inputs, num_output_channels, kernel_size, scope, stride=(1, 1), padding="SAME", data_format="NHWC",
            use_xavier=True, stddev=1e-3, weight_decay=None, activation_fn=torch.relu, bn=False, bn_decay=None,
-           is_training=None, pool=0, defer_bn=False):
+           is_training=None, pool=0, defer_bn=False, pool_idx=None):
     """1x1 conv over an NHWC tensor (B,H,W,C) = matmul over C (tf_util.py:128-204).
     Only the configuration the SA/FP stack uses is implemented: kernel [1,1],
     stride [1,1], NHWC.  `pool` (extension): max over groups of `pool` rows of W,
-    fused in the HIP epilogue on the inference path."""
+    fused in the HIP epilogue on the inference path.  `pool_idx` (extension, inference, pool = 32): the ball query (B,H,32)
+    whose rows `inputs` was computed behind -- the layer then runs on the live rows only (hip_linear_pool_packed: same bits),
+    on all rows where the library refuses."""
     if list(kernel_size) != [1, 1] or list(stride) != [1, 1] or data_format != "NHWC":
         raise NotImplementedError("only 1x1 / stride 1 / NHWC conv2d is on the SA/FP path")
     if activation_fn not in (torch.relu, None):
@@ -1462,7 +1479,11 @@ def conv2d(inputs, num_output_channels, kernel_size, scope, stride=(1, 1), paddi
     with variable_scope(scope):
         if not is_training:
             w2, b2 = folded_dense(cin, cout, bn, (1, 1, cin, cout), pad_to=32)
-            y = hip_linear(inputs.reshape(-1, cin), w2, b2, relu=activation_fn is not None, pool=pool)
+            y = None
+            if pool_idx is not None and pool == 32 and activation_fn is not None:
+                y = hip_linear_pool_packed(inputs.reshape(-1, cin), pool_idx, w2, b2)
+            if y is None:
+                y = hip_linear(inputs.reshape(-1, cin), w2, b2, relu=activation_fn is not None, pool=pool)
             if y.shape[1] != cout:
                 y = y[:, :cout]
             lead = list(inputs.shape[:-1])
