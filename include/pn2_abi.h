@@ -1466,6 +1466,108 @@ int pn2_radius_neighborhoods(int n, const float *points, const int *labels, floa
                              const double *viewpoint, int *count, long long *moments, float *normals, float *curvature,
                              double *variance, int *header, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Rigid registration (ICP) (csrc/pn2_icp.hip): the rigid motion that lays a SOURCE cloud onto a TARGET cloud by iterative closest
+ * point -- what Open3D offers as registration_icp (TransformationEstimationPointToPoint / PointToPlane), evaluate_registration
+ * and PointCloud.transform.  tests/icp_ref.py is the numpy model of the rules and is compared for equality.  A partner is decided
+ * by float64 comparisons; everything after the sums is float64 in the written association (no contraction; sqrt and / correctly
+ * rounded).  THE SUMS ARE FLOAT64 TOO, and here this section departs from its siblings' integer sums: the point-to-plane products
+ * are squares of (coordinate x normal component) terms, which do not fit 2^62 on any lattice fine enough to be useful.  They are
+ * added in ONE FIXED TREE over the source index instead (SUMS), so a result is the same on every run and for every order in
+ * which threads arrive -- but it is a function of the ORDER of the source points: a permuted source gives the same partners and,
+ * in its last bits, another transformation.
+ *
+ *   source (ns,3), target (nt,3) float32; source_labels (ns), target_labels (nt) int32 or NULL; target_normals (nt,3) float32,
+ *   needed for estimation 1; max_distance float32, finite and > 0; init: 16 doubles, row-major 4x4, ON THE HOST (read before the
+ *   call returns), or NULL = the identity; max_iteration >= 0; relative_fitness, relative_rmse >= 0.
+ *   VALID.  The rule of pn2_cluster_points: three finite coordinates and, with labels, a label >= 0.  With estimation 1 a target
+ *     point also needs three finite normal components.
+ *   TRANSFORMED SOURCE POINT.  With T the current 4x4 (float64) and (x, y, z) the float32 point widened, per axis a = 0, 1, 2
+ *       s'_a = (float)(((T_a0*x + T_a1*y) + T_a2*z) + T_a3):  float64 without contraction, rounded to float32 once.
+ *     Row 3 of T is carried along and never read.  A source point with a non-finite s' has no partner.
+ *   PARTNER.  Of a valid source point: the valid target point with the smallest d2 = (dx*dx + dy*dy) + dz*dz in float64,
+ *     dx = (double)t_x - (double)s'_x, dy and dz likewise, among those with d2 <= r*r, r = (double)max_distance; equal d2 go to
+ *     the lowest target index.  correspondence[i] = that index; -1 without a partner and for an invalid source point.
+ *   GRID.  The target's, built once per call: the minimum, keys and one radix sort of csrc/pn2_cell_grid.h at cell edge
+ *     h = r * (1 + 2^-20).  o = the per-axis minimum of the valid target points, widened to float64 (-0.0 below +0.0).  The
+ *     cell of a source point is c_a = floor(((double)s'_a - o_a) / h), against the TARGET's minimum, so it may be negative.  A
+ *     point with c_a < -1 or c_a > 2^21 on an axis (decided in floating point before any conversion; a NaN quotient -- no valid
+ *     target point -- likewise) has no partner; otherwise the cells c-1 .. c+1 clipped to [0, 2^21) are searched, as nine key
+ *     ranges.  Why that finds every partner: pn2_cell_grid.h's proof bounds the error of a computed quotient by 2^-31 from
+ *     |a/h| < 2^21 alone, not from a >= 0; here |a/h| <= 2^21 + 1, the bound doubles at the most, and with it
+ *     q_i - q_j < 1 - 2^-21 + 2^-29 < 1 still holds for a pair that passes the distance test, whatever the signs -- and two
+ *     numbers less than 1 apart have floors at most 1 apart.  So a source point whose floor is below -1 or above 2^21 would need
+ *     a partner with a floor below 0 or of 2^21 and more, and no valid target point of a status-0 call has one.
+ *   SUMS.  Float64.  Source point i is lane i % 64 of wave (i / 64) % 4 of workgroup i / 256; the source is not sorted.  A lane
+ *     without a partner (and a lane beyond ns) contributes +0.0 to every sum.  Per sum: inside the wave v = v + v[lane ^ o] for
+ *     o = 32, 16, 8, 4, 2, 1 (every lane ends with the same value); the workgroup's value is ((w0 + w1) + w2) + w3; the
+ *     call's value is 0.0 + g_0 + g_1 + ..., the workgroups added in ascending order.  Coordinates enter relative to o:
+ *     p_a = (double)s'_a - o_a and u_a = (double)t_a - o_a for the partner t.
+ *   EVALUATION k (k = 0, 1, ...) matches under T_k (T_0 = init) and gives m_k = the number of pairs (a sum of 1.0s),
+ *     D_k = the sum of d2, fitness_k = m_k / (the number of valid source points), 0 when there is none, and
+ *     rmse_k = sqrt(D_k / m_k), 0 when m_k == 0.
+ *   STOP after evaluation k, the first that applies:  the status is 1 (GRID, below);  k >= 1 and |fitness_k - fitness_(k-1)| <
+ *     relative_fitness and |rmse_k - rmse_(k-1)| < relative_rmse (Open3D's test: absolute differences despite the names; it sets
+ *     "converged");  k == max_iteration;  the update cannot be formed: status 2, T stays T_k.  Otherwise T_(k+1) = U_k * T_k:
+ *     row a < 3, column b:  ((R_a0*T_0b + R_a1*T_1b) + R_a2*T_2b) + t_a*T_3b;  row 3 is kept.  max_iteration = 0 evaluates init
+ *     and changes nothing (evaluate_registration).
+ *   POINT-TO-POINT (estimation 0).  Sums: m, D, P_a = sum p_a, U_a = sum u_a, C_ab = sum p_a * u_b.  m < 3: status 2.
+ *     pm_a = P_a / m, um_a = U_a / m, M_ab = C_ab / m - pm_a * um_b.  Horn's symmetric 4x4:
+ *       N00 = (Mxx + Myy) + Mzz   N11 = (Mxx - Myy) - Mzz   N22 = (Myy - Mxx) - Mzz   N33 = (Mzz - Mxx) - Myy
+ *       N01 = Myz - Mzy   N02 = Mzx - Mxz   N03 = Mxy - Myx   N12 = Mxy + Myx   N13 = Mzx + Mxz   N23 = Myz + Mzy.
+ *     It is diagonalised by ten cyclic Jacobi sweeps over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) from V = identity, each
+ *     rotation that of pn2_cluster_describe (AXES) with its "third index" step applied to both other indices k.  The quaternion
+ *     (w, x, y, z) is the column of V under the largest diagonal entry, the first among equals.  ROTATION OF A QUATERNION:
+ *       nn = ((w*w + x*x) + y*y) + z*z
+ *       R00 = (((w*w + x*x) - y*y) - z*z) / nn   R01 = (2 * (x*y - w*z)) / nn             R02 = (2 * (x*z + w*y)) / nn
+ *       R10 = (2 * (x*y + w*z)) / nn             R11 = (((w*w - x*x) + y*y) - z*z) / nn   R12 = (2 * (y*z - w*x)) / nn
+ *       R20 = (2 * (x*z - w*y)) / nn             R21 = (2 * (y*z + w*x)) / nn             R22 = (((w*w - x*x) - y*y) + z*z) / nn
+ *     (no trigonometry anywhere).  t_a = (um_a + o_a) - ((R_a0*c_0 + R_a1*c_1) + R_a2*c_2), c_a = pm_a + o_a.
+ *   POINT-TO-PLANE (estimation 1).  Per pair, n = the partner's normal widened: e_a = (double)s'_a - (double)t_a,
+ *     rho = (e_x*n_x + e_y*n_y) + e_z*n_z, J = (p_y*n_z - p_z*n_y, p_z*n_x - p_x*n_z, p_x*n_y - p_y*n_x, n_x, n_y, n_z).  Sums: m,
+ *     D, the 21 products J_a * J_b (a <= b) = A, the 6 products J_a * rho = g.  m < 6: status 2.  A = L * L^T by Cholesky, for
+ *     j = 0 .. 5:  d = A_jj, then d -= L_jk * L_jk for k = 0 .. j-1;  a d that is not > 0: status 2;  L_jj = sqrt(d);  for
+ *     i = j+1 .. 5:  v = A_ij, then v -= L_ik * L_jk for k = 0 .. j-1;  L_ij = v / L_jj.  Forward, i = 0 .. 5:  v = -g_i, then
+ *     v -= L_ik * y_k for k = 0 .. i-1;  y_i = v / L_ii.  Backward, i = 5 .. 0:  v = y_i, then v -= L_ki * x_k for
+ *     k = i+1 .. 5;  x_i = v / L_ii.  R = the rotation of the quaternion (1, x_0 / 2, x_1 / 2, x_2 / 2);
+ *     t_a = (o_a + x_(3+a)) - ((R_a0*o_0 + R_a1*o_1) + R_a2*o_2).
+ *
+ * pn2_icp: correspondence (ns) int32 = that of the last evaluation; result (20) float64: [0..15] the final T, [16] fitness,
+ *   [17] inlier rmse, [18] D of the last evaluation, [19] 0; header (8) int32: [0] status, [1] valid source points, [2] valid
+ *   target points, [3] m of the last evaluation, [4] updates applied (= the index of the last evaluation), [5] 1 when the
+ *   criterion stopped it, [6..7] 0; trace (max_iteration + 1, 20) float64 or NULL: row k = [0] m_k, [1] fitness_k, [2] rmse_k,
+ *   [3] 0, [4..19] T_k; the rows behind the last evaluation are zero.  All on the device.  The other outputs are the same bits
+ *   with and without a trace.  Status 0 = ok; 1 = more than 2^21 cells of edge max_distance on an axis of the valid target
+ *   points' box (the convention of pn2_cluster_points): then every correspondence is -1, result = init followed by four zeros,
+ *   header[1..7] are zero and trace row 0 is (0, 0, 0, 0, init); 2 = too few pairs or a pivot that is not positive.
+ *   workspace: *bytes of pn2_icp_workspace_size(ns, nt, max_iteration, bytes) (a host query like pn2_cluster_workspace_size:
+ *   PN2_EINVAL for ns or nt < 1 or max_iteration < 0, PN2_ENULL without bytes; it does not decrease when an argument grows),
+ *   256-byte aligned; it need not be cleared.  The call queues an init kernel (the scalars, the trace zeroed: no memset node), the
+ *   target's grid, and max_iteration + 1 pairs of launches: icp_match_kernel, in which a lane owns a source point -- transform,
+ *   search, its row of the sums in registers, the tree; no atomic on a sum, one row of partials per workgroup in the workspace
+ *   -- and the one-workgroup icp_step_kernel, which adds the rows, decides and updates T.  The whole loop runs without the host:
+ *   the step that stops sets a `done` word, and every later launch reads it and returns without writing anything.  No
+ *   allocation, no synchronisation, no dynamic-LDS limit raised.
+ *   Refusals, nothing launched and nothing written, in this order: PN2_EINVAL (ns or nt < 1, max_distance not finite or <= 0,
+ *   estimation not 0 or 1, max_iteration < 0, a tolerance that is NaN or negative, a non-finite init), PN2_ENULL (source,
+ *   target, correspondence, result, header or workspace NULL; target_normals NULL with estimation 1), PN2_EINVAL (source,
+ *   target, the labels, target_normals, correspondence or header not 4-byte aligned, result or trace not 8-byte aligned, a
+ *   workspace not 256-byte aligned or too small), PN2_EUNSUP (a capturing stream: the loop's length is data, a capture would
+ *   record every round).
+ *
+ * pn2_transform_points: out (n,3) float32 = the TRANSFORMED SOURCE POINT of every row of points under transform (16 doubles on
+ *   the HOST, copied by value); a row with a non-finite coordinate is copied as it is.  out may be points.  One launch,
+ *   capturable.  PN2_EINVAL: n < 1; PN2_ENULL: a NULL pointer; PN2_EINVAL: a non-finite transform, points or out not 4-byte
+ *   aligned. */
+int pn2_icp_workspace_size(int ns, int nt, int max_iteration, unsigned long long *bytes);
+int pn2_icp(int ns, const float *source, const int *source_labels,
+            int nt, const float *target, const int *target_labels, const float *target_normals,
+            float max_distance, int estimation /* 0 point-to-point, 1 point-to-plane */,
+            const double *init /* 16, row-major, ON THE HOST, or NULL = identity */,
+            int max_iteration, double relative_fitness, double relative_rmse,
+            int *correspondence /* (ns) */, double *result /* (20) */, double *trace /* (max_iteration+1, 20) or NULL */,
+            int *header /* (8) */, void *workspace, size_t workspace_bytes, void *stream);
+int pn2_transform_points(int n, const float *points, const double *transform /* 16, host */, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,10 +6,11 @@ from . import _lib  # noqa: F401  (fails loudly if the HIP extension is missing)
 from . import tf_ops, util  # noqa: F401
 from . import model, runtime, dist, train, dataset, downsample, predict, preprocess  # noqa: F401
 from .preprocess import parse_text, read_semantic3d_txt, load_labels, point_cloud_txt_to_pcd  # noqa: F401
-from . import scene_io, kitti_predict, render, cluster, plane, neighbors  # noqa: F401
+from . import scene_io, kitti_predict, render, cluster, plane, neighbors, icp  # noqa: F401
 from .cluster import euclidean_clusters, cluster_colors, Clusters, describe_clusters, box_wireframe, Boxes  # noqa: F401
 from .neighbors import (radius_neighborhoods, estimate_normals, remove_radius_outlier, normal_colors,  # noqa: F401
                         Neighborhoods)
+from .icp import registration_icp, evaluate_registration, transform_points, RegistrationResult  # noqa: F401
 from .plane import segment_plane, segment_planes, score_planes, Plane  # noqa: F401
 from .scene_io import format_ints, write_labels, write_point_cloud_pcd, read_point_cloud_pcd  # noqa: F401
 from .scene_io import write_point_cloud_ply, read_point_cloud_ply, read_point_cloud  # noqa: F401

@@ -19,7 +19,8 @@ SOURCES = ["pn2_abi.hip", "pn2_sampling.hip", "pn2_grouping.hip", "pn2_interpola
            "pn2_bn.hip", "pn2_scene.hip", "pn2_train.hip", "pn2_mlp_wide.hip", "pn2_pool.hip", "pn2_hoist.hip",
            "pn2_coarse_geometry.hip", "pn2_bwd_fused.hip", "pn2_metric.hip", "pn2_dataset.hip", "pn2_text.hip",
            "pn2_scene_io.hip", "pn2_augment.hip", "pn2_store.hip", "pn2_frame.hip", "pn2_tile.hip", "pn2_soft_vote.hip",
-           "pn2_records.hip", "pn2_render.hip", "pn2_cluster.hip", "pn2_plane.hip", "pn2_describe.hip", "pn2_neighbors.hip"]
+           "pn2_records.hip", "pn2_render.hip", "pn2_cluster.hip", "pn2_plane.hip", "pn2_describe.hip", "pn2_neighbors.hip",
+           "pn2_icp.hip"]
 # per-file additions.  pn2_sa_fused.hip: MFMA results in VGPRs where they fit (the fused chains feed every accumulator back into
 # the next layer's MFMA as an A / B operand, which must be an arch VGPR: with AGPR accumulators each of those 128 values per
 # tile costs a v_accvgpr_read, and non-MFMA instructions cost their full issue time on a SIMD whose matrix pipe is busy)

@@ -1,4 +1,4 @@
-// pn2_cell_grid.h -- the sorted-key cell grid of the per-point neighbourhood passes (pn2_cluster.hip, pn2_neighbors.hip), in one
+// pn2_cell_grid.h -- the sorted-key cell grid of the per-point neighbourhood passes (pn2_cluster.hip, pn2_neighbors.hip, pn2_icp.hip), in one
 // copy: the minimum of the valid points, the 63-bit cell key of every point, and the search in the sorted keys.  The host half
 // of a caller queues  its own init kernel (GridScal's fields as cluster_init_kernel sets them), cluster_min_kernel,
 // cluster_key_kernel and one radix sort (pn2_sort.h) of (key, point index) pairs on key bits [0, 64).

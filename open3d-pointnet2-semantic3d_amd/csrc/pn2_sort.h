@@ -1,5 +1,5 @@
 // pn2_sort.h -- "sort (key, row index) pairs with the library's radix sort", the host half, in one copy: pn2_store.hip,
-// pn2_scene.hip (voxels), pn2_tile.hip, pn2_cluster.hip, pn2_neighbors.hip, pn2_grid_knn.h and pn2_fps_bucket.hip.  The key kernels of the callers
+// pn2_scene.hip (voxels), pn2_tile.hip, pn2_cluster.hip, pn2_neighbors.hip, pn2_icp.hip, pn2_grid_knn.h and pn2_fps_bucket.hip.  The key kernels of the callers
 // write vals_in[i] = i themselves.  The sort is stable: equal keys keep ascending row index.
 #pragma once
 #include <hipcub/hipcub.hpp>

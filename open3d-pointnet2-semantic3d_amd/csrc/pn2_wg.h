@@ -1,5 +1,5 @@
 // pn2_wg.h -- the workgroup primitives of the data-path kernels (pn2_scene.hip, pn2_dataset.hip, pn2_frame.hip, pn2_tile.hip,
-// pn2_store.hip, pn2_cluster.hip, pn2_plane.hip, pn2_describe.hip, pn2_neighbors.hip) and the workspace carving of every host half that takes a
+// pn2_store.hip, pn2_cluster.hip, pn2_plane.hip, pn2_describe.hip, pn2_neighbors.hip, pn2_icp.hip) and the workspace carving of every host half that takes a
 // workspace (those, and pn2_text.hip, pn2_scene_io.hip, pn2_grid_knn.h, pn2_fps_bucket.hip, pn2_augment.hip; pn2_sort.h carves the
 // radix sort's share).
 // One copy of each.

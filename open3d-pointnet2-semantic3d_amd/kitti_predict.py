@@ -12,6 +12,7 @@ the Predictor is used as it is.  After the frame's construction nothing on this 
 import torch
 
 from .cluster import _device_of, describe_clusters, euclidean_clusters
+from .icp import registration_icp
 from .neighbors import estimate_normals
 from .plane import segment_plane
 from .predict import Predictor, _on_device
@@ -74,6 +75,24 @@ class PredictInterpolator:
         neighbors.estimate_normals with the viewpoint at the sensor, (0,0,0), so every normal faces it -> (n,3) float32, NaN
         where fewer than min_neighbors points lie within the radius.  Eager."""
         return estimate_normals(file_data.points, radius, viewpoint=(0.0, 0.0, 0.0), min_neighbors=min_neighbors)
+
+    def align_frames(self, prev_file_data, file_data, max_distance, estimation="point_to_point", init=None, normal_radius=None,
+                     prev_dense_labels=None, dense_labels=None, classes=None, max_iteration=30, relative_fitness=1e-6,
+                     relative_rmse=1e-6, trace=False):
+        """(extension) the rigid motion that lays file_data.points (the source) onto prev_file_data.points (the target):
+        icp.registration_icp.  estimation "point_to_plane" takes the target's normals from normals_for_frame(prev_file_data,
+        normal_radius), normal_radius defaulting to 2 * max_distance.  classes: register on these classes of the two frames'
+        dense labels only -- the static ones, so that moving objects do not drag the pose.  -> icp.RegistrationResult;
+        .transformation maps this frame into the previous one's coordinates.  Eager."""
+        if (classes is not None) and (prev_dense_labels is None or dense_labels is None):
+            raise ValueError("classes: needs prev_dense_labels and dense_labels")
+        normals = None
+        if estimation == "point_to_plane":
+            normals = self.normals_for_frame(prev_file_data, 2.0 * max_distance if normal_radius is None else normal_radius)
+        return registration_icp(file_data.points, prev_file_data.points, max_distance, init=init, estimation=estimation,
+                                target_normals=normals, max_iteration=max_iteration, relative_fitness=relative_fitness,
+                                relative_rmse=relative_rmse, source_labels=dense_labels, target_labels=prev_dense_labels,
+                                classes=classes, trace=trace)
 
     def ground_for_frame(self, file_data, distance_threshold, trials=1024, seed=0, max_angle=15.0, dense_labels=None, classes=None):
         """(extension) the ground of file_data.points: plane.segment_plane with the axis (0,0,1), the normal within max_angle
