@@ -191,6 +191,22 @@ def launch(name, where, *args, may_refuse=False, stream=True):
     return True
 
 
+def aligned(nbytes, device):
+    """a uint8 device buffer of nbytes whose first byte is 256-aligned (what every workspace argument asks for; the text kernels
+    load 16 bytes at a time)"""
+    raw = torch.empty((nbytes + 256,), dtype=torch.uint8, device=device)
+    off = (-raw.data_ptr()) % 256
+    return raw[off:off + nbytes]
+
+
+def workspace(query, dev, *size_args):
+    """the workspace of one call: the size query `query` (..., &bytes) is asked with `size_args` and a 256-aligned uint8 view of
+    that many bytes on `dev` comes back, to be passed as ptr(ws), ws.numel()"""
+    need = u64_array([0])  # written by the query
+    launch(query, dev, *size_args, need, stream=False)
+    return aligned(int(need[0]), dev)
+
+
 def nbytes(t):
     return t.numel() * t.element_size()
 

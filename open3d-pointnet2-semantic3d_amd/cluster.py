@@ -14,13 +14,12 @@ The number of clusters is data-dependent and is read by the host once (the heade
 stream.  Nothing in a result depends on the order in which threads arrive.
 """
 import collections
-import ctypes
 import math
 
 import numpy as np
 import torch
 
-from ._lib import launch, ptr, require_cuda
+from ._lib import launch, ptr, require_cuda, workspace
 from .predict import _on_device
 
 # the status word of pn2_cluster_points (include/pn2_abi.h), the convention of downsample.STATUS_NAMES
@@ -105,12 +104,9 @@ def euclidean_clusters(points, eps, labels=None, classes=None, min_points=1, max
     if n == 0:
         return empty  # nothing is launched: the entry point refuses n == 0
     header = torch.zeros((8,), dtype=torch.int32, device=dev)
-    nbytes = ctypes.c_ulonglong(0)
-    launch("pn2_cluster_workspace_size", dev, n, ctypes.byref(nbytes), stream=False)
-    ws = torch.empty((int(nbytes.value) + 255,), dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
-    launch("pn2_cluster_points", dev, n, ptr(points), ptr(labels), eps, min_points, max_points, ptr(ids), ptr(header),
-           ws.data_ptr() + off, ws.numel() - off)
+    ws = workspace("pn2_cluster_workspace_size", dev, n)
+    launch("pn2_cluster_points", dev, n, ptr(points), ptr(labels), eps, min_points, max_points, ptr(ids), ptr(header), ptr(ws),
+           ws.numel())
     status, count = header[:2].tolist()  # the one host read
     if status:
         raise ValueError("pn2_cluster_points: %s" % STATUS_NAMES[status])
@@ -200,12 +196,9 @@ def describe_clusters(points, clusters, upright=False):
     ids = _on_device(ids, torch.int32, dev)
     moments = torch.empty((count, 12), dtype=torch.int64, device=dev)
     desc = torch.empty((count, 24), dtype=torch.float64, device=dev)
-    nbytes = ctypes.c_ulonglong(0)
-    launch("pn2_cluster_describe_workspace_size", dev, count, ctypes.byref(nbytes), stream=False)
-    ws = torch.empty((int(nbytes.value) + 255,), dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
-    launch("pn2_cluster_describe", dev, n, count, ptr(points), ptr(ids), 1 if upright else 0, ptr(moments), ptr(desc),
-           ws.data_ptr() + off, ws.numel() - off)
+    ws = workspace("pn2_cluster_describe_workspace_size", dev, count)
+    launch("pn2_cluster_describe", dev, n, count, ptr(points), ptr(ids), 1 if upright else 0, ptr(moments), ptr(desc), ptr(ws),
+           ws.numel())
     return _boxes_of(moments, desc)
 
 

@@ -3,13 +3,12 @@
 // tests/cluster_ref.py is their numpy model, and everything here is compared with it for equality.
 //
 // pn2_cluster_points queues, on the caller's stream (eager only: the host half of the caller reads the header afterwards):
-//   1 cluster_init_kernel    : the scalars (ordered minima, counters, status).
-//   2 cluster_min_kernel     : the minimum x, y, z of the valid points as ordered uint32 (a float32 minimum is exact), one atomicMin
-//                              per axis per wave; the count of valid points.
-//   3 cluster_key_kernel     : the cell of every valid point and its 63-bit key, x lowest; an invalid point gets the key ~0, which
-//                              sorts last and is never visited.  A cell coordinate >= 2^21 raises the status.
-//   4 hipcub radix sort      : (key, point index) pairs.
-//   5 cluster_gather_kernel  : the sorted points as (x, y, z, label) rows; parent[i] = i, csize[i] = 0.
+//   1 cluster_init_kernel    : the scalars (ordered minima, counters, status); parent[i] = i, csize[i] = 0.
+//   2 .. 5 CellGrid::build   : pn2_cell_grid.h -- grid_min_kernel (the minimum x, y, z of the valid points as ordered uint32: a
+//                              float32 minimum is exact; the count of valid points), grid_key_kernel (the cell of every valid
+//                              point and its 63-bit key, x lowest; an invalid point gets the key ~0, which sorts last and is never
+//                              visited; a cell coordinate >= 2^21 raises the status), the radix sort of (key, point index) pairs,
+//                              grid_gather_kernel (the sorted points as (x, y, z, label) rows).
 //   6 cluster_union_kernel   : one sorted point per lane.  It visits the points IN FRONT of it in the sorted order that lie in the
 //                              27 cells around its own -- five key ranges, because x is the lowest key field: the three rows
 //                              (y-1, y, y+1) of the layer z-1, the row y-1 of its own layer, and its own row up to itself -- and
@@ -34,11 +33,10 @@
 //   * parent[] is read with relaxed agent-scope atomic loads.  A stale value is an ancestor of an earlier time: it lengthens a walk
 //     or fails a swap, and no loop's exit rests on it -- find ends on its own decreasing index, unite on the swap's answer.
 // No kernel waits for another workgroup.
-#include "pn2_cell_grid.h"  // kT, kW, kCellBits, kCellLimit, kInvalidKey, GridScal, cluster_min_kernel, cluster_key_kernel, lower_bound_key
+#include "pn2_cell_grid.h"  // kT, kW, kCellBits, kCellLimit, kInvalidKey, GridScal, grid_scal_reset, lower_bound_key, CellGrid
 #include "pn2_common.h"
 #include "pn2_ordered.h"  // ordered_key32, ordered_to_float
-#include "pn2_sort.h"     // IndexSort
-#include "pn2_wg.h"       // wg_excl_scan_flag, wg_excl_scan_int, wg_sum, point_valid, WsCarver
+#include "pn2_wg.h"       // wg_excl_scan_flag, wg_excl_scan_int, wg_sum, point_valid, blocks_of, refuse_capture, WsCarver
 
 namespace {
 
@@ -48,44 +46,34 @@ struct Scal : GridScal {
     int nkeptpts;         // points in kept clusters
 };
 
-inline int scan_blocks(int n) { return (int)(((long long)n + kT - 1) / kT); }
-
 struct Ws {  // workspace carve-up
     Scal* scal;
-    IndexSort<unsigned long long> sort;
-    float4* spts;
+    CellGrid grid;
     int *parent, *csize, *root, *number, *bcount;
 };
 inline int ws_layout(int n, WsCarver& c, Ws* w) {
     const size_t N = (size_t)n;
     w->scal = c.take<Scal>(1);
-    w->sort.carve(c, N);
-    w->spts = c.take<float4>(N);
+    w->grid.carve(c, N);
     w->parent = c.take<int>(N);
     w->csize = c.take<int>(N);
     w->root = c.take<int>(N);
     w->number = c.take<int>(N);
-    w->bcount = c.take<int>((size_t)scan_blocks(n));
-    return w->sort.carve_tmp(c, n, 0, 64);
-}
-
-__global__ void cluster_init_kernel(Scal* __restrict__ s) {
-    if (threadIdx.x == 0) {
-        s->min_key[0] = s->min_key[1] = s->min_key[2] = 0xFFFFFFFFu;
-        s->status = s->nvalid = s->ncomp = s->nkeptpts = 0;
-    }
+    w->bcount = c.take<int>((size_t)blocks_of(n, kT));
+    return w->grid.carve_tmp(c, n);
 }
 
 __global__ void __launch_bounds__(kT)
-cluster_gather_kernel(int n, const float* __restrict__ points, const int* __restrict__ labels, const int* __restrict__ order,
-                      float4* __restrict__ spts, int* __restrict__ parent, int* __restrict__ csize) {
-    const long long t = (long long)blockIdx.x * kT + threadIdx.x;
-    if (t >= n) return;
-    parent[t] = (int)t;
-    csize[t] = 0;
-    const int i = order[t];
-    const float* p = points + (size_t)i * 3;
-    spts[t] = make_float4(p[0], p[1], p[2], __int_as_float(labels ? labels[i] : 0));
+cluster_init_kernel(int n, Scal* __restrict__ s, int* __restrict__ parent, int* __restrict__ csize) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    if (i == 0) {
+        grid_scal_reset(s);
+        s->ncomp = s->nkeptpts = 0;
+    }
+    if (i < n) {
+        parent[i] = (int)i;
+        csize[i] = 0;
+    }
 }
 
 __device__ __forceinline__ int load_parent(const int* parent, int x) {
@@ -134,7 +122,9 @@ cluster_union_kernel(int n, const unsigned long long* __restrict__ keys, const i
     const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
     const int label = __float_as_int(p.w);
     const int i = order[me];
-    // the rows in front of this point: (z-1; y-1, y, y+1), (z; y-1), (z; y) up to the point itself
+    // the rows in front of this point: (z-1; y-1, y, y+1), (z; y-1), (z; y) up to the point itself.  The first five rows of
+    // grid_walk_rows' order with end = me, written out: through the walker (row = r / 3, r % 3) this kernel measured 4 % slower
+    // on a 1.5 M-point scene (EXPERIMENTS.md r13), so the loop keeps the shape it had
     for (int r = 0; r < 5; ++r) {
         const int z = r < 3 ? cz - 1 : cz;
         const int y = r < 3 ? cy - 1 + r : (r == 3 ? cy - 1 : cy);
@@ -342,24 +332,16 @@ extern "C" int pn2_cluster_points(int n, const float* points, const int* labels,
     const int rc = ws_layout(n, c, &w);  // too small: refused before the sort is asked for its share
     if (rc != PN2_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // eager by nature: the caller reads the header (the number of clusters sizes what follows).  Refused on a capturing stream.
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    hipError_t e = hipStreamIsCapturing(st, &capturing);
-    if (e != hipSuccess) return (int)e;
-    if (capturing != hipStreamCaptureStatusNone) return PN2_EUNSUP;
+    // eager by nature: the caller reads the header (the number of clusters sizes what follows)
+    if (const int refused = refuse_capture(st)) return refused;
 
-    const double h = (double)eps * (1.0 + 1.0 / 1048576.0);
     const double eps2 = (double)eps * (double)eps;
-    const int blocks = scan_blocks(n);
+    const int blocks = blocks_of(n, kT);
 
-    cluster_init_kernel<<<1, 64, 0, st>>>(w.scal);
-    cluster_min_kernel<<<blocks, kT, 0, st>>>(n, points, labels, w.scal);
-    cluster_key_kernel<<<blocks, kT, 0, st>>>(n, points, labels, h, w.scal, w.sort.keys_in, w.sort.vals_in);
-    PN2_RETURN_IF_LAUNCH_FAILED();
-    e = w.sort.run(n, 0, 64, st);
-    if (e != hipSuccess) return (int)e;
-    cluster_gather_kernel<<<blocks, kT, 0, st>>>(n, points, labels, w.sort.vals_out, w.spts, w.parent, w.csize);
-    cluster_union_kernel<<<blocks, kT, 0, st>>>(n, w.sort.keys_out, w.sort.vals_out, w.spts, eps2, w.scal, w.parent);
+    cluster_init_kernel<<<blocks, kT, 0, st>>>(n, w.scal, w.parent, w.csize);
+    const int built = w.grid.build(n, points, labels, eps, false, w.scal, st);
+    if (built != PN2_OK) return built;
+    cluster_union_kernel<<<blocks, kT, 0, st>>>(n, w.grid.keys(), w.grid.order(), w.grid.spts, eps2, w.scal, w.parent);
     cluster_flatten_kernel<<<blocks, kT, 0, st>>>(n, points, labels, w.parent, w.scal, w.root, w.csize);
     cluster_flag_kernel<<<blocks, kT, 0, st>>>(n, w.root, w.csize, min_points, max_points, w.scal, w.bcount);
     cluster_offsets_kernel<<<1, kT, 0, st>>>(blocks, w.bcount, w.scal, header);
@@ -379,9 +361,9 @@ extern "C" int pn2_cluster_stats(int n, int nclusters, const float* points, cons
         return PN2_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     unsigned* box = reinterpret_cast<unsigned*>(bbox);
-    const int cblocks = scan_blocks(nclusters);
+    const int cblocks = blocks_of(nclusters, kT);
     stats_init_kernel<<<cblocks, kT, 0, st>>>(nclusters, first, size, box);
-    stats_points_kernel<<<scan_blocks(n), kT, 0, st>>>(n, nclusters, points, ids, first, size, box);
+    stats_points_kernel<<<blocks_of(n, kT), kT, 0, st>>>(n, nclusters, points, ids, first, size, box);
     stats_finish_kernel<<<cblocks, kT, 0, st>>>(n, nclusters, labels, first, label, box);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
@@ -391,7 +373,7 @@ extern "C" int pn2_cluster_colors(int n, const int* ids, uint8_t* rgb, void* str
     if (n <= 0) return PN2_EINVAL;
     if (!ids || !rgb) return PN2_ENULL;
     if (((uintptr_t)ids & 3) != 0) return PN2_EINVAL;
-    cluster_colors_kernel<<<scan_blocks(n), kT, 0, static_cast<hipStream_t>(stream)>>>(n, ids, rgb);
+    cluster_colors_kernel<<<blocks_of(n, kT), kT, 0, static_cast<hipStream_t>(stream)>>>(n, ids, rgb);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

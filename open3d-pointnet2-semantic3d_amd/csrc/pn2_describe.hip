@@ -33,7 +33,7 @@
 #include "pn2_common.h"
 #include "pn2_eig3.h"     // jacobi_rotate, fix_sign, eig3_axes
 #include "pn2_ordered.h"  // ordered_key32, ordered_to_float, ordered_key, ordered_to_double
-#include "pn2_wg.h"       // finite32, WsCarver
+#include "pn2_wg.h"       // finite32, blocks_of, refuse_capture, WsCarver
 
 namespace {
 
@@ -74,8 +74,6 @@ inline void ws_layout(int nclusters, WsCarver& c, Ws* w) {
     w->lat = c.take<Lat>(C);
     w->ext = c.take<Ext>(C);
 }
-
-inline int blocks_of(long long items) { return (int)((items + kT - 1) / kT); }
 
 // a MEMBER of cluster c: ids[i] == c, 0 <= c < nclusters, three finite coordinates.  -> c, or -1
 __device__ __forceinline__ int member_of(int n, int nclusters, const float* __restrict__ points, const int* __restrict__ ids,
@@ -397,13 +395,10 @@ extern "C" int pn2_cluster_describe(int n, int nclusters, const float* points, c
     if (!c.fits()) return PN2_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // capturable by construction, but nothing captures it yet: refused until a change lifts this together with a capture test
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    const hipError_t e = hipStreamIsCapturing(st, &capturing);
-    if (e != hipSuccess) return (int)e;
-    if (capturing != hipStreamCaptureStatusNone) return PN2_EUNSUP;
+    if (const int refused = refuse_capture(st)) return refused;
 
     const Peel peel = {g_describe_rounds, g_describe_min_lanes};
-    const int pblocks = blocks_of(n), cblocks = blocks_of(nclusters);
+    const int pblocks = blocks_of(n, kT), cblocks = blocks_of(nclusters, kT);
     describe_clear_kernel<<<cblocks, kT, 0, st>>>(nclusters, w.acc, w.ext);
     describe_box_kernel<<<pblocks, kT, 0, st>>>(n, nclusters, peel, points, ids, w.acc);
     describe_lattice_kernel<<<cblocks, kT, 0, st>>>(nclusters, w.acc, w.lat);
@@ -422,7 +417,7 @@ extern "C" int pn2_box_wireframe(int nclusters, const double* desc, int per_edge
     if (total >= (1ll << 31)) return PN2_ERANGE;
     if (!desc || !points || !owner) return PN2_ENULL;
     if (((uintptr_t)desc & 7) != 0 || (((uintptr_t)points | (uintptr_t)owner) & 3) != 0) return PN2_EINVAL;
-    box_wireframe_kernel<<<blocks_of(total), kT, 0, static_cast<hipStream_t>(stream)>>>((int)total, per_edge, desc, points, owner);
+    box_wireframe_kernel<<<blocks_of(total, kT), kT, 0, static_cast<hipStream_t>(stream)>>>((int)total, per_edge, desc, points, owner);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

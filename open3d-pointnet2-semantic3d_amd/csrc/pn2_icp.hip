@@ -8,24 +8,23 @@
 //   2 icp_count_kernel     : the valid source points.
 //   3 icp_labels_kernel    : point-to-plane only -- the target's labels with -1 where a normal is not finite, so that the grid
 //                            below sees the VALID rule of this call through its one `labels` argument.
-//   4 cluster_min_kernel, cluster_key_kernel, one radix sort (pn2_cell_grid.h, pn2_sort.h): the TARGET's grid at cell edge
-//     max_distance * (1 + 2^-20), built once.
-//   5 icp_gather_kernel    : the sorted target points as (x, y, z, original index) rows.
-//   6 K + 1 times: icp_match_kernel (THE HOT ONE), icp_step_kernel (one workgroup).
+//   4 CellGrid::build      : pn2_cell_grid.h -- grid_min_kernel, grid_key_kernel, one radix sort, grid_gather_kernel: the TARGET's
+//                            grid at cell edge max_distance * (1 + 2^-20), built once; the sorted target points as (x, y, z,
+//                            original index) rows.
+//   5 K + 1 times: icp_match_kernel (THE HOT ONE), icp_step_kernel (one workgroup).
 // Nothing is read by the host: the stop is a `done` word in the scalars, and every launch behind the stop returns at once.
 //
 // THE MATCH.  One lane owns one source point, in the source's own order (lane = block * 256 + thread: the sums are a fixed tree
 // over that index, so nothing is sorted on this side).  The lane transforms its point, walks the nine key ranges around its cell
-// of the target's grid (the lane path (a) of pn2_neighbors.hip: one binary search and one stream of 16-byte loads per range),
+// of the target's grid (pn2_cell_grid.h's grid_walk_rows with nrows = 9, end = nt, as the lane path (a) of pn2_neighbors.hip),
 // keeps the nearest candidate in registers, and forms its row of the normal equations in registers (17 doubles point-to-point,
 // 29 point-to-plane).  The rows are added in float64: xor butterflies inside the wave, ((w0 + w1) + w2) + w3 across the four
 // waves through LDS, one row of partials per workgroup; icp_step_kernel adds those rows in ascending order.  No atomic on a sum.
 // The two estimators are two instantiations, so that the point-to-point kernel does not carry the other's registers.
-#include "pn2_cell_grid.h"  // kT, kW, kCellBits, kCellLimit, GridScal, cluster_min_kernel, cluster_key_kernel, lower_bound_key
+#include "pn2_cell_grid.h"  // kT, kW, kCellLimit, GridScal, grid_scal_reset, grid_walk_rows, CellGrid
 #include "pn2_common.h"
 #include "pn2_eig4.h"       // eig4_largest
-#include "pn2_sort.h"       // IndexSort
-#include "pn2_wg.h"         // WsCarver, point_valid, finite32
+#include "pn2_wg.h"         // WsCarver, point_valid, finite32, blocks_of, finite_host, refuse_capture
 
 namespace {
 
@@ -49,26 +48,23 @@ struct Init {
 struct Ws {
     Scal* scal;
     int* eff;  // the target's labels of a point-to-plane call
-    IndexSort<unsigned long long> sort;
-    float4* spts;
+    CellGrid grid;  // the target's
     double* partials;
 };
-inline int blocks_of(int n) { return (int)(((long long)n + kT - 1) / kT); }
 inline int ws_layout(int ns, int nt, WsCarver& c, Ws* w) {
     w->scal = c.take<Scal>(1);
     w->eff = c.take<int>((size_t)nt);
-    w->sort.carve(c, (size_t)nt);
-    w->spts = c.take<float4>((size_t)nt);
-    w->partials = c.take<double>((size_t)blocks_of(ns) * kRow);
-    return w->sort.carve_tmp(c, nt, 0, 64);
+    w->grid.carve(c, (size_t)nt);
+    w->partials = c.take<double>((size_t)blocks_of(ns, kT) * kRow);
+    return w->grid.carve_tmp(c, nt);
 }
 
 __global__ void __launch_bounds__(kT)
 icp_init_kernel(Scal* __restrict__ s, Init init, double* __restrict__ trace, long long trace_doubles) {
     const long long i = (long long)blockIdx.x * kT + threadIdx.x;
     if (i == 0) {
-        s->min_key[0] = s->min_key[1] = s->min_key[2] = 0xFFFFFFFFu;
-        s->status = s->nvalid = s->ns_valid = s->done = s->updates = s->converged = 0;
+        grid_scal_reset(s);
+        s->ns_valid = s->done = s->updates = s->converged = 0;
         for (int j = 0; j < 16; ++j) s->T[j] = init.T[j];
         s->prev_fitness = s->prev_rmse = 0.0;
     }
@@ -89,20 +85,6 @@ icp_labels_kernel(int n, const int* __restrict__ labels, const float* __restrict
     const float* v = normals + (size_t)i * 3;
     eff[i] = finite32(v[0]) && finite32(v[1]) && finite32(v[2]) ? (labels ? labels[i] : 0) : -1;
 }
-
-__global__ void __launch_bounds__(kT)
-icp_gather_kernel(int n, const float* __restrict__ points, const int* __restrict__ order, float4* __restrict__ spts) {
-    const long long t = (long long)blockIdx.x * kT + threadIdx.x;
-    if (t >= n) return;
-    const int i = order[t];
-    const float* p = points + (size_t)i * 3;
-    spts[t] = make_float4(p[0], p[1], p[2], __int_as_float(i));
-}
-
-__device__ __forceinline__ unsigned long long row_key(int y, int z) {
-    return ((unsigned long long)z << (2 * kCellBits)) | ((unsigned long long)y << kCellBits);
-}
-__device__ __forceinline__ bool cell_in(int c) { return c >= 0 && c < kCellLimit; }
 
 // the TRANSFORMED SOURCE POINT of the header: float64, rounded to float32 once
 __device__ __forceinline__ float transform_axis(const double* __restrict__ T, int a, double x, double y, double z) {
@@ -145,22 +127,14 @@ icp_match_kernel(int ns, const float* __restrict__ source, const int* __restrict
     int bi = 0x7FFFFFFF;     // its target index
     float bx = 0.0f, by = 0.0f, bz = 0.0f;
     if (search) {
-        const int x0 = cell[0] > 0 ? cell[0] - 1 : 0, x1 = cell[0] < kCellLimit - 1 ? cell[0] + 1 : kCellLimit - 1;
-        for (int r = 0; r < 9; ++r) {
-            const int z = cell[2] - 1 + r / 3, y = cell[1] - 1 + r % 3;
-            if (!cell_in(z) || !cell_in(y)) continue;
-            const unsigned long long row = row_key(y, z);
-            const unsigned long long klo = row | (unsigned long long)x0, khi = row | (unsigned long long)x1;
-            for (int u = lower_bound_key(keys, nt, klo); u < nt && keys[u] <= khi; ++u) {
-                const float4 q = spts[u];
-                const double dx = (double)q.x - sx, dy = (double)q.y - sy, dz = (double)q.z - sz;
-                const double d2 = (dx * dx + dy * dy) + dz * dz;
-                const int idx = __float_as_int(q.w);
-                if (d2 < bd || (d2 == bd && idx < bi)) {
-                    bd = d2; bi = idx; bx = q.x; by = q.y; bz = q.z;
-                }
+        grid_walk_rows(keys, nt, spts, cell[0], cell[1], cell[2], 9, [&](int, const float4& q) {
+            const double dx = (double)q.x - sx, dy = (double)q.y - sy, dz = (double)q.z - sz;
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            const int idx = __float_as_int(q.w);
+            if (d2 < bd || (d2 == bd && idx < bi)) {
+                bd = d2; bi = idx; bx = q.x; by = q.y; bz = q.z;
             }
-        }
+        });
     }
     const bool paired = bi != 0x7FFFFFFF;
     if (i < ns) corr[i] = paired ? bi : -1;
@@ -375,7 +349,6 @@ transform_points_kernel(int n, const float* points, Init T, float* out) {
     out[(size_t)i * 3 + 2] = r2;
 }
 
-inline bool finite_host(double v) { return v - v == 0.0; }
 inline bool finite16(const double* T) {
     for (int j = 0; j < 16; ++j)
         if (!finite_host(T[j])) return false;
@@ -415,16 +388,13 @@ extern "C" int pn2_icp(int ns, const float* source, const int* source_labels, in
     if (rc != PN2_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // the loop's length is data, so a capture would record all max_iteration + 1 rounds; nothing in the project captures it
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    hipError_t e = hipStreamIsCapturing(st, &capturing);
-    if (e != hipSuccess) return (int)e;
-    if (capturing != hipStreamCaptureStatusNone) return PN2_EUNSUP;
+    if (const int refused = refuse_capture(st)) return refused;
 
     Init T0;
     for (int j = 0; j < 16; ++j) T0.T[j] = init ? init[j] : (j % 5 == 0 ? 1.0 : 0.0);
     const double r = (double)max_distance;
-    const double cell = r * (1.0 + 1.0 / 1048576.0);
-    const int bs = blocks_of(ns), bt = blocks_of(nt);
+    const double cell = CellGrid::edge(max_distance);
+    const int bs = blocks_of(ns, kT), bt = blocks_of(nt, kT);
     const long long trace_doubles = trace ? ((long long)max_iteration + 1) * 20 : 0;
     const int binit = trace_doubles > kT ? (int)((trace_doubles + kT - 1) / kT) : 1;
     const int* tlabels = target_labels;
@@ -435,18 +405,14 @@ extern "C" int pn2_icp(int ns, const float* source, const int* source_labels, in
         icp_labels_kernel<<<bt, kT, 0, st>>>(nt, target_labels, target_normals, w.eff);
         tlabels = w.eff;
     }
-    cluster_min_kernel<<<bt, kT, 0, st>>>(nt, target, tlabels, w.scal);
-    cluster_key_kernel<<<bt, kT, 0, st>>>(nt, target, tlabels, cell, w.scal, w.sort.keys_in, w.sort.vals_in);
-    PN2_RETURN_IF_LAUNCH_FAILED();
-    e = w.sort.run(nt, 0, 64, st);
-    if (e != hipSuccess) return (int)e;
-    icp_gather_kernel<<<bt, kT, 0, st>>>(nt, target, w.sort.vals_out, w.spts);
+    const int built = w.grid.build(nt, target, tlabels, max_distance, true, w.scal, st);
+    if (built != PN2_OK) return built;
     for (int k = 0; k <= max_iteration; ++k) {
         if (estimation == 0)
-            icp_match_kernel<0><<<bs, kT, 0, st>>>(ns, source, source_labels, nt, w.sort.keys_out, w.spts, target_normals, r * r, cell,
+            icp_match_kernel<0><<<bs, kT, 0, st>>>(ns, source, source_labels, nt, w.grid.keys(), w.grid.spts, target_normals, r * r, cell,
                                                    w.scal, correspondence, w.partials);
         else
-            icp_match_kernel<1><<<bs, kT, 0, st>>>(ns, source, source_labels, nt, w.sort.keys_out, w.spts, target_normals, r * r, cell,
+            icp_match_kernel<1><<<bs, kT, 0, st>>>(ns, source, source_labels, nt, w.grid.keys(), w.grid.spts, target_normals, r * r, cell,
                                                    w.scal, correspondence, w.partials);
         icp_step_kernel<<<1, 64, 0, st>>>(k, max_iteration, estimation, bs, relative_fitness, relative_rmse, w.partials, w.scal, result,
                                           trace, header);
@@ -461,7 +427,7 @@ extern "C" int pn2_transform_points(int n, const float* points, const double* tr
     if (!finite16(transform) || (((uintptr_t)points | (uintptr_t)out) & 3) != 0) return PN2_EINVAL;
     Init T;
     for (int j = 0; j < 16; ++j) T.T[j] = transform[j];
-    transform_points_kernel<<<blocks_of(n), kT, 0, static_cast<hipStream_t>(stream)>>>(n, points, T, out);
+    transform_points_kernel<<<blocks_of(n, kT), kT, 0, static_cast<hipStream_t>(stream)>>>(n, points, T, out);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;
 }

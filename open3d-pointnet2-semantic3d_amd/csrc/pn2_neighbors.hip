@@ -6,11 +6,10 @@
 //
 // pn2_radius_neighborhoods queues, on the caller's stream (eager only), six launches and one radix sort:
 //   1 radius_init_kernel   : the scalars (a workspace arrives uninitialised; no memset node).
-//   2 cluster_min_kernel   : pn2_cell_grid.h -- the minimum of the valid points, their number.
-//   3 cluster_key_kernel   : pn2_cell_grid.h -- the 63-bit cell key of every point at cell edge radius * (1 + 2^-20), x lowest; ~0
-//                            for an invalid point; status 1 for a cell coordinate >= 2^21.
-//   4 hipcub radix sort    : (key, point index) pairs.
-//   5 radius_gather_kernel : the sorted points as (x, y, z, 0) rows.
+//   2 .. 5 CellGrid::build : pn2_cell_grid.h -- grid_min_kernel (the minimum of the valid points, their number), grid_key_kernel
+//                            (the 63-bit cell key of every point at cell edge radius * (1 + 2^-20), x lowest; ~0 for an invalid
+//                            point; status 1 for a cell coordinate >= 2^21), the radix sort of (key, point index) pairs,
+//                            grid_gather_kernel (the sorted points as (x, y, z, index) rows; the fourth word is never read here).
 //   6 radius_scan_kernel   : THE HOT ONE, below.
 //   7 radius_header_kernel : the header from the scalars.
 //
@@ -21,7 +20,7 @@
 // set: a candidate from further away fails the test and changes nothing.  Two ways to enumerate one:
 //   (a) the lane path.  Each lane walks the nine key ranges of its own cell: the rows y-1 .. y+1 of the layers z-1 .. z+1, x from
 //       cx-1 to cx+1 (x is the lowest key field, so a row's three cells are one range of the sorted keys).  One binary search
-//       and one stream of 16-byte loads per lane and range.
+//       and one stream of 16-byte loads per lane and range: pn2_cell_grid.h's grid_walk_rows with nrows = 9, end = n.
 //   (b) the wave-uniform path, for a wave whose valid lanes lie in ONE row (cy, cz) with cx_max - cx_min <= kSpan (the sorted
 //       order makes that common in a dense cloud: 64 consecutive keys).  The nine ranges are then the wave's own, x from
 //       cx_min-1 to cx_max+1: lanes 0 .. 17 do the eighteen binary searches side by side, and the candidates are read in chunks
@@ -32,11 +31,11 @@
 //   A wave that is not eligible takes (a) as a whole.  Both give the same bits: the same tests on a superset, integer sums.
 // In the loop the snap to the lattice multiplies by 1 / h (a power of two: exact) and rounds to nearest-even; |q| <= 2^20 fits
 // an int32, so the six products are v_mad_i64_i32.
-#include "pn2_cell_grid.h"  // kT, kCellBits, kCellLimit, kInvalidKey, GridScal, cluster_min_kernel, cluster_key_kernel, lower_bound_key
+#include "pn2_cell_grid.h"  // kT, kCellBits, kCellLimit, kInvalidKey, GridScal, grid_scal_reset, key_cell, row_key, cell_in,
+                            // lower_bound_key, grid_walk_rows, CellGrid
 #include "pn2_common.h"
 #include "pn2_eig3.h"       // eig3_axes, fix_sign
-#include "pn2_sort.h"       // IndexSort
-#include "pn2_wg.h"         // WsCarver
+#include "pn2_wg.h"         // blocks_of, finite_host, refuse_capture, WsCarver
 
 namespace {
 
@@ -63,31 +62,19 @@ struct Params {
 
 struct Ws {
     Scal* scal;
-    IndexSort<unsigned long long> sort;
-    float4* spts;
+    CellGrid grid;
 };
 inline int ws_layout(int n, WsCarver& c, Ws* w) {
     w->scal = c.take<Scal>(1);
-    w->sort.carve(c, (size_t)n);
-    w->spts = c.take<float4>((size_t)n);
-    return w->sort.carve_tmp(c, n, 0, 64);
+    w->grid.carve(c, (size_t)n);
+    return w->grid.carve_tmp(c, n);
 }
-
-inline int blocks_of(int n) { return (int)(((long long)n + kT - 1) / kT); }
 
 __global__ void radius_init_kernel(Scal* __restrict__ s) {
     if (threadIdx.x == 0) {
-        s->min_key[0] = s->min_key[1] = s->min_key[2] = 0xFFFFFFFFu;
-        s->status = s->nvalid = s->nok = s->maxcount = 0;
+        grid_scal_reset(s);
+        s->nok = s->maxcount = 0;
     }
-}
-
-__global__ void __launch_bounds__(kT)
-radius_gather_kernel(int n, const float* __restrict__ points, const int* __restrict__ order, float4* __restrict__ spts) {
-    const long long t = (long long)blockIdx.x * kT + threadIdx.x;
-    if (t >= n) return;
-    const float* p = points + (size_t)order[t] * 3;
-    spts[t] = make_float4(p[0], p[1], p[2], 0.0f);
 }
 
 // the count and the sums of one lane's own point
@@ -110,11 +97,6 @@ __device__ __forceinline__ void test_candidate(bool valid, double px, double py,
     }
 }
 
-__device__ __forceinline__ unsigned long long row_key(int y, int z) {
-    return ((unsigned long long)z << (2 * kCellBits)) | ((unsigned long long)y << kCellBits);
-}
-__device__ __forceinline__ bool cell_in(int c) { return c >= 0 && c < kCellLimit; }
-
 __global__ void __launch_bounds__(kT)
 radius_scan_kernel(int n, const unsigned long long* __restrict__ keys, const int* __restrict__ order,
                    const float4* __restrict__ spts, Params P, Scal* __restrict__ s, int* __restrict__ count,
@@ -125,8 +107,7 @@ radius_scan_kernel(int n, const unsigned long long* __restrict__ keys, const int
     const bool in = t < n;
     const unsigned long long key = in ? keys[t] : kInvalidKey;
     const bool valid = key != kInvalidKey && s->status == 0;  // (the status is the same for every thread)
-    const int cx = (int)(key & (kCellLimit - 1)), cy = (int)((key >> kCellBits) & (kCellLimit - 1)),
-              cz = (int)((key >> (2 * kCellBits)) & (kCellLimit - 1));
+    const Cell own = key_cell(key);
     float4 p = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (valid) p = spts[t];
     const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
@@ -174,17 +155,8 @@ radius_scan_kernel(int n, const unsigned long long* __restrict__ keys, const int
         }
     } else if (valid) {
         // (a) the nine rows around this lane's own cell, whole
-        const int x0 = cx > 0 ? cx - 1 : 0, x1 = cx < kCellLimit - 1 ? cx + 1 : cx;
-        for (int r = 0; r < 9; ++r) {
-            const int z = cz - 1 + r / 3, y = cy - 1 + r % 3;
-            if (!cell_in(z) || !cell_in(y)) continue;
-            const unsigned long long row = row_key(y, z);
-            const unsigned long long klo = row | (unsigned long long)x0, khi = row | (unsigned long long)x1;
-            for (int u = lower_bound_key(keys, n, klo); u < n && keys[u] <= khi; ++u) {
-                const float4 q = spts[u];
-                test_candidate(true, px, py, pz, q.x, q.y, q.z, P.r2, P.inv_h, a);
-            }
-        }
+        grid_walk_rows(keys, n, spts, own.x, own.y, own.z, 9,
+                       [&](int, const float4& q) { test_candidate(true, px, py, pz, q.x, q.y, q.z, P.r2, P.inv_h, a); });
     }
 
     // the tail: covariance and axes of the lane's own sums (include/pn2_abi.h: m = count, upright = 0)
@@ -247,8 +219,6 @@ __global__ void radius_header_kernel(const Scal* __restrict__ s, int Q, int x, i
     }
 }
 
-inline bool finite_host(double v) { return v - v == 0.0; }
-
 }  // namespace
 
 #ifdef PN2_TUNING_HOOKS
@@ -286,10 +256,7 @@ extern "C" int pn2_radius_neighborhoods(int n, const float* points, const int* l
     hipStream_t st = static_cast<hipStream_t>(stream);
     // it allocates nothing and would be capturable, but nothing in the project captures it: refused until a later change lifts
     // this together with a capture test
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    hipError_t e = hipStreamIsCapturing(st, &capturing);
-    if (e != hipSuccess) return (int)e;
-    if (capturing != hipStreamCaptureStatusNone) return PN2_EUNSUP;
+    if (const int refused = refuse_capture(st)) return refused;
 
     // THE LATTICE of this call: radius = f * 2^x, f in [0.5, 1); h = 2^(x - Q)
     int bitlen = 0;
@@ -308,18 +275,12 @@ extern "C" int pn2_radius_neighborhoods(int n, const float* points, const int* l
     P.min_neighbors = min_neighbors;
     P.variant = g_radius_variant;
     P.span = g_radius_span;
-    const double cell = (double)radius * (1.0 + 1.0 / 1048576.0);
-    const int blocks = blocks_of(n);
 
     radius_init_kernel<<<1, 64, 0, st>>>(w.scal);
-    cluster_min_kernel<<<blocks, kT, 0, st>>>(n, points, labels, w.scal);
-    cluster_key_kernel<<<blocks, kT, 0, st>>>(n, points, labels, cell, w.scal, w.sort.keys_in, w.sort.vals_in);
-    PN2_RETURN_IF_LAUNCH_FAILED();
-    e = w.sort.run(n, 0, 64, st);
-    if (e != hipSuccess) return (int)e;
-    radius_gather_kernel<<<blocks, kT, 0, st>>>(n, points, w.sort.vals_out, w.spts);
-    radius_scan_kernel<<<blocks, kT, 0, st>>>(n, w.sort.keys_out, w.sort.vals_out, w.spts, P, w.scal, count, moments, normals,
-                                              curvature, variance);
+    const int built = w.grid.build(n, points, labels, radius, true, w.scal, st);
+    if (built != PN2_OK) return built;
+    radius_scan_kernel<<<blocks_of(n, kT), kT, 0, st>>>(n, w.grid.keys(), w.grid.order(), w.grid.spts, P, w.scal, count, moments,
+                                                        normals, curvature, variance);
     radius_header_kernel<<<1, 64, 0, st>>>(w.scal, Q, x, header);
     PN2_RETURN_IF_LAUNCH_FAILED();
     return PN2_OK;

@@ -27,7 +27,7 @@
 // same launches and writes the outputs of its status.
 #include "pn2_common.h"
 #include "pn2_rng.h"
-#include "pn2_wg.h"  // wg_excl_scan_flag, wg_excl_scan_int, finite64, point_valid, WsCarver
+#include "pn2_wg.h"  // wg_excl_scan_flag, wg_excl_scan_int, finite64, point_valid, blocks_of, refuse_capture, WsCarver
 
 namespace {
 
@@ -48,8 +48,6 @@ struct Scal {
     double win[6];            // the winner's plane as scored
 };
 
-inline int scan_blocks(int n) { return (int)(((long long)n + kT - 1) / kT); }
-
 struct Ws {  // workspace carve-up
     Scal* scal;
     int *bcount, *valid;
@@ -59,7 +57,7 @@ struct Ws {  // workspace carve-up
 inline size_t ws_layout(int n, int trials, unsigned char* base, Ws* w) {
     WsCarver c{base};
     w->scal = c.take<Scal>(1);
-    w->bcount = c.take<int>((size_t)scan_blocks(n));
+    w->bcount = c.take<int>((size_t)blocks_of(n, kT));
     w->valid = c.take<int>((size_t)n);
     w->planes = c.take<double>((size_t)trials * 6);
     w->counts = c.take<int>((size_t)trials);
@@ -273,14 +271,6 @@ plane_mask_kernel(int n, const float* __restrict__ points, const int* __restrict
 
 inline bool thr_ok(float thr) { return thr > 0.0f && thr <= 3.402823466e38f; }
 
-// PN2_OK when the stream is not capturing
-inline int refuse_capture(hipStream_t st) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    const hipError_t e = hipStreamIsCapturing(st, &capturing);
-    if (e != hipSuccess) return (int)e;
-    return capturing != hipStreamCaptureStatusNone ? PN2_EUNSUP : PN2_OK;
-}
-
 }  // namespace
 
 extern "C" int pn2_plane_score(int n, const float* points, const int* labels, int nplanes, const double* planes, float thr,
@@ -327,7 +317,7 @@ extern "C" int pn2_plane_ransac(int n, const float* points, const int* labels, f
     const int rc = refuse_capture(st);  // as pn2_plane_score
     if (rc != PN2_OK) return rc;
 
-    const int blocks = scan_blocks(n), tblocks = (trials + kT - 1) / kT;
+    const int blocks = blocks_of(n, kT), tblocks = blocks_of(trials, kT);
 
     plane_flag_kernel<<<blocks, kT, 0, st>>>(n, points, labels, w.bcount);
     plane_offsets_kernel<<<1, kT, 0, st>>>(blocks, w.bcount, w.scal);

@@ -29,7 +29,7 @@
 #include "pn2_common.h"
 #include "pn2_ordered.h"  // ordered_key, ordered_to_double
 #include "pn2_sort.h"     // IndexSort
-#include "pn2_wg.h"       // wg_sum, wg_excl_scan_flag, wg_excl_scan_int, finite64, WsCarver
+#include "pn2_wg.h"       // wg_sum, wg_excl_scan_flag, wg_excl_scan_int, finite64, finite_host, WsCarver
 
 namespace {
 
@@ -312,8 +312,6 @@ tv_labels_kernel(int n, int num_class, const int* __restrict__ votes, int* __res
     }
     labels[i] = best;
 }
-
-inline bool finite_host(double v) { return v == v && v - v == 0.0; }
 
 }  // namespace
 

@@ -1,7 +1,9 @@
 // pn2_wg.h -- the workgroup primitives of the data-path kernels (pn2_scene.hip, pn2_dataset.hip, pn2_frame.hip, pn2_tile.hip,
 // pn2_store.hip, pn2_cluster.hip, pn2_plane.hip, pn2_describe.hip, pn2_neighbors.hip, pn2_icp.hip) and the workspace carving of every host half that takes a
 // workspace (those, and pn2_text.hip, pn2_scene_io.hip, pn2_grid_knn.h, pn2_fps_bucket.hip, pn2_augment.hip; pn2_sort.h carves the
-// radix sort's share).
+// radix sort's share, pn2_cell_grid.h the cell grid's), and the prologue of the eager entry points: the block count
+// (pn2_cluster.hip, pn2_neighbors.hip, pn2_icp.hip, pn2_plane.hip, pn2_describe.hip, pn2_cell_grid.h), the finite test of a host
+// argument (pn2_neighbors.hip, pn2_icp.hip, pn2_tile.hip) and the refusal of a capturing stream (the first five).
 // One copy of each.
 //
 // W is the number of waves of the CALLING workgroup (its threads / 64): a template parameter, because every file names its own
@@ -16,6 +18,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../../include/pn2_abi.h"  // PN2_OK, PN2_EUNSUP
 #include "pn2_wave.h"
 
 // ---- scans and sums ----------------------------------------------------------------------------------------------------------
@@ -118,6 +121,23 @@ __device__ __forceinline__ bool finite32(float f) { return (__float_as_uint(f) &
 __device__ __forceinline__ bool point_valid(const float* __restrict__ points, const int* __restrict__ labels, long long i) {
     const float* p = points + (size_t)i * 3;
     return finite32(p[0]) && finite32(p[1]) && finite32(p[2]) && (!labels || labels[i] >= 0);
+}
+
+// ---- host: the prologue of an eager entry point --------------------------------------------------------------------------------
+// workgroups of `threads` that cover `items`
+inline int blocks_of(long long items, int threads) { return (int)((items + threads - 1) / threads); }
+
+// neither an infinity nor a NaN (a NaN fails the comparison)
+inline bool finite_host(double v) { return v - v == 0.0; }
+
+// PN2_OK when `st` is not capturing, PN2_EUNSUP when it is, or the query's hipError_t: the first act of an entry point that is
+// eager only (pn2_cluster.hip, pn2_neighbors.hip, pn2_icp.hip, pn2_plane.hip, pn2_describe.hip), behind its argument checks and
+// in front of its first launch.  Each call site says why it refuses.
+inline int refuse_capture(hipStream_t st) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(st, &capturing);
+    if (e != hipSuccess) return (int)e;
+    return capturing != hipStreamCaptureStatusNone ? PN2_EUNSUP : PN2_OK;
 }
 
 // ---- host: workspace carving ---------------------------------------------------------------------------------------------------

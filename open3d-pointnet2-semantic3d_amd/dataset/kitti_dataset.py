@@ -19,20 +19,13 @@ import os
 import numpy as np
 import torch
 
-from .._lib import launch, ptr, u64_array
-from ..preprocess import _aligned
+from .._lib import launch, ptr, workspace
 
 # KittiFileData.__init__ :15-16 of the reference: the z range of the region of interest
 MIN_Z, MAX_Z = -2, 5
 LABELS_NAMES = ["unlabeled", "man-made terrain", "natural terrain", "high vegetation", "low vegetation", "buildings", "hard scape",
                 "scanning artifact", "cars"]
 _INGEST_RES = 12  # int64 words pn2_scene_ingest reports into: z range (2), label histogram (9), status (1)
-
-
-def _workspace(query, n, dev):
-    need = u64_array([0])
-    launch(query, dev, n, need, stream=False)
-    return _aligned(int(need[0]), dev)
 
 
 class KittiFileData:
@@ -69,7 +62,7 @@ class KittiFileData:
             cropped = torch.empty((n, 3), dtype=torch.float64, device=dev)
             src = torch.empty((n,), dtype=torch.int32, device=dev)
             count = torch.empty((1,), dtype=torch.int32, device=dev)
-            ws = _workspace("pn2_frame_crop_workspace_size", n, dev)
+            ws = workspace("pn2_frame_crop_workspace_size", dev, n)
             launch("pn2_frame_crop", dev, n, ptr(frame), int(frame.stride(0)), -box_size_x / 2.0, -box_size_y / 2.0, float(MIN_Z),
                    box_size_x / 2.0, box_size_y / 2.0, float(MAX_Z), ptr(cropped), ptr(src), ptr(count), ptr(ws), ws.numel())
             cnt = int(count.item())  # the one host read of the frame
@@ -79,7 +72,7 @@ class KittiFileData:
             perm = torch.empty((cnt,), dtype=torch.int32, device=dev)
             labels_u8 = torch.empty((cnt,), dtype=torch.uint8, device=dev)
             res = torch.empty((_INGEST_RES,), dtype=torch.int64, device=dev)
-            ws = _workspace("pn2_scene_ingest_workspace_size", cnt, dev)
+            ws = workspace("pn2_scene_ingest_workspace_size", dev, cnt)
             # (its status flags non-finite coordinates and labels: the crop has dropped the first, there are none of the second)
             launch("pn2_scene_ingest", dev, cnt, ptr(cropped), None, None, ptr(self.points), None, ptr(labels_u8), ptr(perm),
                    ptr(res[0:2]), ptr(res[2:11]), ptr(res[11:12]), ptr(ws), ws.numel())
@@ -87,7 +80,7 @@ class KittiFileData:
             self.labels = torch.zeros((cnt,), dtype=torch.int32, device=dev)
             self.colors = torch.zeros((cnt, 3), dtype=torch.float64, device=dev)
             self._counter = torch.zeros((1,), dtype=torch.int64, device=dev)
-            self._sample_ws = _workspace("pn2_frame_sample_workspace_size", cnt, dev)
+            self._sample_ws = workspace("pn2_frame_sample_workspace_size", dev, cnt)
         self.num_frame_points = n
         self.last_status = self.last_sel = None
 

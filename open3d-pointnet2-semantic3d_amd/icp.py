@@ -19,7 +19,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import launch, ptr
+from ._lib import launch, ptr, workspace
 from .cluster import _check_cloud, _device_cloud, _on_device
 from .neighbors import _radius
 
@@ -108,13 +108,9 @@ def registration_icp(source, target, max_correspondence_distance, init=None, est
     # result (20 doubles) and header (8 int32) carved from one buffer: one copy to the host
     out = torch.zeros((24,), dtype=torch.float64, device=dev)
     rows = torch.empty((max_iteration + 1, 20), dtype=torch.float64, device=dev) if trace else None
-    nbytes = ctypes.c_ulonglong(0)
-    launch("pn2_icp_workspace_size", dev, ns, nt, max_iteration, ctypes.byref(nbytes), stream=False)
-    ws = torch.empty((int(nbytes.value) + 255,), dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    ws = workspace("pn2_icp_workspace_size", dev, ns, nt, max_iteration)
     launch("pn2_icp", dev, ns, ptr(source), ptr(source_labels), nt, ptr(target), ptr(target_labels), ptr(normals), radius, est, T0,
-           max_iteration, relative_fitness, relative_rmse, ptr(corr), ptr(out), ptr(rows), ptr(out, 160), ws.data_ptr() + off,
-           ws.numel() - off)
+           max_iteration, relative_fitness, relative_rmse, ptr(corr), ptr(out), ptr(rows), ptr(out, 160), ptr(ws), ws.numel())
     host = out.cpu().numpy()  # the one host read
     h = host[20:].view(np.int32)
     status, updates = int(h[0]), int(h[4])

@@ -17,7 +17,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import launch, ptr
+from ._lib import launch, ptr, workspace
 from .cluster import _check_cloud, _device_cloud
 
 # the status word of pn2_radius_neighborhoods (include/pn2_abi.h), the convention of cluster.STATUS_NAMES
@@ -84,12 +84,9 @@ def radius_neighborhoods(points, radius, labels=None, classes=None, min_neighbor
     if n == 0:
         return Neighborhoods(count, normals, curvature, var, mom, (0, 0), 0, 0)  # nothing is launched: the entry point refuses n == 0
     header = torch.zeros((8,), dtype=torch.int32, device=dev)
-    nbytes = ctypes.c_ulonglong(0)
-    launch("pn2_radius_workspace_size", dev, n, ctypes.byref(nbytes), stream=False)
-    ws = torch.empty((int(nbytes.value) + 255,), dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    ws = workspace("pn2_radius_workspace_size", dev, n)
     launch("pn2_radius_neighborhoods", dev, n, ptr(points), ptr(labels), radius, min_neighbors, view, ptr(count), ptr(mom),
-           ptr(normals), ptr(curvature), ptr(var), ptr(header), ws.data_ptr() + off, ws.numel() - off)
+           ptr(normals), ptr(curvature), ptr(var), ptr(header), ptr(ws), ws.numel())
     h = header.tolist()  # the one host read
     return Neighborhoods(count, normals, curvature, var, mom, (h[4], h[5]), h[1], h[0])
 

@@ -20,7 +20,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import launch, ptr
+from ._lib import launch, ptr, workspace
 from .cluster import _check_cloud, _device_cloud
 from .predict import _on_device
 
@@ -89,12 +89,9 @@ def _ransac(dev, points, labels, thr, trials, seed, axis, cos2):
     inlier = torch.empty((n,), dtype=torch.uint8, device=dev)
     raw = torch.empty((4,), dtype=torch.float64, device=dev)
     header = torch.empty((8,), dtype=torch.int32, device=dev)
-    nbytes = ctypes.c_ulonglong(0)
-    launch("pn2_plane_workspace_size", dev, n, trials, ctypes.byref(nbytes), stream=False)
-    ws = torch.empty((int(nbytes.value) + 255,), dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    ws = workspace("pn2_plane_workspace_size", dev, n, trials)
     launch("pn2_plane_ransac", dev, n, ptr(points), ptr(labels), thr, trials, seed, axis, cos2, ptr(inlier), ptr(raw), ptr(header),
-           ws.data_ptr() + off, ws.numel() - off)
+           ptr(ws), ws.numel())
     status, count, trial, s0, s1, s2, valid, _ = header.tolist()  # the one host read
     if status:
         return _no_plane(n, dev, status, valid)

@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import ABI, int_array, launch, ptr, u64_array
+from ._lib import ABI, aligned as _aligned, int_array, launch, ptr, workspace
 
 F64, I32, TRUNC_I32, SKIP = (ABI.constants["PN2_TEXT_" + k] for k in ("F64", "I32", "TRUNC_I32", "SKIP"))
 MALFORMED = ABI.constants["PN2_TEXT_MALFORMED"]
@@ -97,20 +97,11 @@ def _device_chunks(text, chunk_bytes):
         pos = end
 
 
-def _aligned(nbytes, device, align=256):
-    """a uint8 device buffer of nbytes whose first byte is `align`-aligned (the kernels load 16 bytes at a time)"""
-    raw = torch.empty((nbytes + align,), dtype=torch.uint8, device=device)
-    off = (-raw.data_ptr()) % align
-    return raw[off:off + nbytes]
-
-
 def index_lines(text, line_cap=None):
     """text: uint8 device tensor (16-byte aligned, whole lines) -> line_start int32 (nlines + 1,): line i is
     text[line_start[i] : line_start[i + 1] - 1].  Synchronises (the number of lines sizes what follows)."""
     nbytes, dev = text.numel(), text.device
-    need = u64_array([0])  # written by the query
-    launch("pn2_text_index_workspace_bytes", dev, nbytes, need, stream=False)
-    ws = _aligned(int(need[0]), dev)
+    ws = workspace("pn2_text_index_workspace_bytes", dev, nbytes)
     count = torch.zeros((1,), dtype=torch.int32, device=dev)
     if line_cap is None:  # from the density of '\n' at the front of the chunk, with room to spare
         head = text[:65536]

@@ -301,6 +301,18 @@ def test_status_too_many_cells(pn2, cuda):
     assert _check(pn2, cuda, pts, 0.1)[1].tolist() == [0, 2, 2, 2, 2, 0, 0, 0]
 
 
+def test_linked_pair_in_the_last_two_cells_of_every_axis(pn2, cuda):
+    """the top edge of the grid: with eps = 1 and the minimum pinned at the origin, cell c of an axis is [c * h, (c + 1) * h),
+    h = 1 + 2^-20, so 2097152.75 lies in cell 2^21 - 2 and 2097153.25 in cell 2^21 - 1, the last one (float32 resolves 0.25
+    there); the diagonal pair is 0.5 * sqrt(3) apart: linked, and the walk of the later point clamps x at the grid's edge"""
+    a, b = 2097152.75, 2097153.25
+    pts = np.array([[0, 0, 0], [a, a, a], [b, b, b]], dtype=np.float32)
+    cells = np.floor(pts.astype(np.float64) / (1.0 + 2.0 ** -20))
+    assert (cells[1] == 2 ** 21 - 2).all() and (cells[2] == 2 ** 21 - 1).all()
+    ids, hdr = _check(pn2, cuda, pts, 1.0)
+    assert ids.tolist() == [0, 1, 1] and hdr.tolist() == [0, 2, 2, 3, 3, 0, 0, 0]
+
+
 def test_refusals_leave_the_outputs_untouched(pn2, cuda):
     import torch
     lib, K = pn2._lib, pn2._lib.ABI.constants

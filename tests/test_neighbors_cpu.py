@@ -169,6 +169,22 @@ def test_model_hand_made_cases():
     assert N.neighborhoods(np.array([[0, 0, 0], [2e6, 0, 0]], dtype=np.float32), 1.0, None, 1).header[0] == 0
 
 
+def test_models_place_a_pair_in_the_last_two_cells():
+    """the input of the GPU tests of the grid's top edge: with an edge of 1 * (1 + 2^-20) and the minimum at the origin,
+    2097152.75 is in cell 2^21 - 2 and 2097153.25 in cell 2^21 - 1 on every axis; both models accept the cloud (status 0) and
+    link the pair"""
+    import cluster_ref as C
+    a, b = 2097152.75, 2097153.25
+    pts = np.array([[0, 0, 0], [a, a, a], [b, b, b]], dtype=np.float32)
+    assert pts[1, 0] == a and pts[2, 0] == b  # float32 resolves 0.25 there
+    cells = np.floor(pts.astype(np.float64) / (1.0 + 2.0 ** -20))
+    assert (cells[1] == 2 ** 21 - 2).all() and (cells[2] == 2 ** 21 - 1).all()
+    out = N.neighborhoods(pts, 1.0, None, 1)
+    assert out.header[:4].tolist() == [0, 3, 3, 2] and out.count.tolist() == [1, 2, 2]
+    ids, hdr = C.cluster(pts, 1.0, None, 1, 0)
+    assert ids.tolist() == [0, 1, 1] and hdr.tolist() == [0, 2, 2, 3, 3, 0, 0, 0]
+
+
 # ---- the ABI -------------------------------------------------------------------------------------------------------------------
 def test_header_declares_the_entry_points(pn2):
     fns = pn2._lib.ABI.functions
@@ -187,10 +203,21 @@ def test_header_declares_the_entry_points(pn2):
         with open(os.path.join(csrc, name)) as src:
             assert "pn2_grid_knn.h" not in src.read(), name
     # the shared pieces exist once
-    for name, owner in (("cluster_key_kernel(", "pn2_cell_grid.h"), ("lower_bound_key(const", "pn2_cell_grid.h"),
+    for name, owner in (("grid_min_kernel(", "pn2_cell_grid.h"), ("grid_key_kernel(", "pn2_cell_grid.h"),
+                        ("grid_gather_kernel(", "pn2_cell_grid.h"), ("lower_bound_key(const", "pn2_cell_grid.h"),
+                        ("void grid_walk_rows(", "pn2_cell_grid.h"), ("unsigned long long row_key(", "pn2_cell_grid.h"),
+                        ("bool cell_in(", "pn2_cell_grid.h"), ("Cell key_cell(", "pn2_cell_grid.h"),
+                        ("void grid_scal_reset(", "pn2_cell_grid.h"), ("struct CellGrid", "pn2_cell_grid.h"),
                         ("void jacobi_rotate(", "pn2_eig3.h"), ("void fix_sign(", "pn2_eig3.h")):
         holders = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")) and name in open(os.path.join(csrc, f)).read()]
         assert holders == [owner], (name, holders)
+    # no grid kernel is launched, and no row searched, outside the grid's header -- but for the wave-uniform path's own search
+    # and clustering's written-out walk in front of a point
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".hip"):
+            text = open(os.path.join(csrc, f)).read()
+            assert not any("grid_%s_kernel<<<" % k in text for k in ("min", "key", "gather")), f
+            assert text.count("lower_bound_key(") == (1 if f in ("pn2_neighbors.hip", "pn2_cluster.hip") else 0), f
     for name in ("radius_neighborhoods", "estimate_normals", "remove_radius_outlier", "normal_colors", "Neighborhoods"):
         assert getattr(pn2, name) is getattr(pn2.neighbors, name), name
     assert pn2.Neighborhoods._fields == ("count", "normals", "curvature", "variance", "moments", "lattice", "valid", "status")

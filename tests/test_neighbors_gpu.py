@@ -109,6 +109,18 @@ def _in_cell(rs, m, cell, radius, fill=0.9):
 ORIGIN = np.zeros((1, 3))  # a point at the grid's minimum, so that the cells of _in_cell are what they say
 
 
+# ---- the wrappers' workspace ---------------------------------------------------------------------------------------------------
+def test_lib_workspace_is_aligned_and_large_enough(pn2, cuda):
+    """_lib.workspace: the size query asked through launch, a 256-aligned uint8 view of at least that many bytes"""
+    import torch
+    for n in (1, 1000):
+        nbytes = ctypes.c_ulonglong(0)
+        pn2._lib.launch("pn2_radius_workspace_size", cuda, n, ctypes.byref(nbytes), stream=False)
+        ws = pn2._lib.workspace("pn2_radius_workspace_size", cuda, n)
+        assert ws.dtype == torch.uint8 and ws.device == torch.device(cuda) and ws.dim() == 1
+        assert ws.data_ptr() % 256 == 0 and ws.numel() >= int(nbytes.value) > 0
+
+
 # ---- the wave-uniform path: chunk edges ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("m", [1, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 1])
 def test_chunk_edges_of_the_uniform_path(pn2, cuda, m):
@@ -289,6 +301,19 @@ def test_status_1_for_a_cloud_too_wide_for_the_grid(pn2, cuda):
     pts[17, 1] = -3e6
     assert _check(pn2, cuda, pts, 1.0).header[0] == 1
     assert _check(pn2, cuda, np.array([[0, 0, 0], [2e6, 0, 0]]), 1.0, min_neighbors=1).header[0] == 0  # 2 * 10^6 cells: still fine
+
+
+def test_neighbours_in_the_last_two_cells_of_every_axis(pn2, cuda):
+    """the top edge of the grid: with radius = 1 and the minimum pinned at the origin, cell c of an axis is [c * h, (c + 1) * h),
+    h = 1 + 2^-20, so 2097152.75 lies in cell 2^21 - 2 and 2097153.25 in cell 2^21 - 1, the last one (float32 resolves 0.25
+    there); the diagonal pair is 0.5 * sqrt(3) apart: neighbours, found by a walk whose x range is clamped at the grid's edge
+    (three points in three rows: the lane path)"""
+    a, b = 2097152.75, 2097153.25
+    pts = np.array([[0, 0, 0], [a, a, a], [b, b, b]], dtype=np.float32)
+    cells = np.floor(pts.astype(np.float64) / (1.0 + 2.0 ** -20))
+    assert (cells[1] == 2 ** 21 - 2).all() and (cells[2] == 2 ** 21 - 1).all()
+    want = _check(pn2, cuda, pts, 1.0, min_neighbors=1)
+    assert want.header[:4].tolist() == [0, 3, 3, 2] and want.count.tolist() == [1, 2, 2]
 
 
 # ---- the viewpoint ---------------------------------------------------------------------------------------------------------------

@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import pn2_amd as pn2  # noqa: E402
 
-GRID = ("cluster_init", "cluster_min", "cluster_key", "cluster_gather")
+GRID = ("cluster_init", "grid_min", "grid_key", "grid_gather")  # the last three: pn2_cell_grid.h
 NUMBER = ("cluster_flatten", "cluster_flag", "cluster_offsets", "cluster_number", "cluster_ids")
 
 

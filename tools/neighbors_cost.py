@@ -31,7 +31,7 @@ import pn2_amd as pn2  # noqa: E402
 import cluster_cost  # noqa: E402
 
 RADIUS = {"frame": 0.5, "scene": 0.1}
-GRID = ("radius_init", "cluster_min", "cluster_key", "radius_gather")
+GRID = ("radius_init", "grid_min", "grid_key", "grid_gather")  # the last three: pn2_cell_grid.h
 HOOK_VARIANT, HOOK_SPAN = 21, 22  # pn2_debug_set of the tuning build (csrc/pn2_neighbors.hip)
 SHIPPED_SPAN = 8                  # kSpan there
 T0 = time.perf_counter()
